@@ -11,9 +11,19 @@ step, odfmax = maximum(mean(odf, dims=4)) (gqi.jl:164), is a 2-float all-reduce(
 odfmax on every rank.  Strong scaling: the total work is fixed.  `value` is whole-job Mvoxels/s with inputs in HBM.
 
 Output: ONE final stdout line, JSON, <= 6 KB (compact_line below: the contract's keys, `roofline`, `cpu_baseline` and a
-number-only `extra` per leg).  Everything else the run measured (tools/bench_legs.py: the other BASELINE configs, host-tier
-stages, energy components, clocks) goes to bench_extra.json next to this file and to an earlier stdout line that starts
-with `bench_extra ` -- never into the result line (round 5's 25 KB line could not be parsed by the driver)."""
+number-only `extra` per leg).
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: set-up, warm-up, the K timed steps, the
+outputs of the last step when `--dump-outputs DIR` is given, the result line (`roofline` from the timed steps' own kernel events,
+`cpu_baseline` null, `extra` empty).  `--full` adds everything else: the step's other launches, the CPU baselines and the legs of
+tools/bench_legs.py (the other BASELINE configs, host-tier stages, energy components, clocks); all of it goes to bench_extra.json next
+to this file and to an earlier stdout line that starts with `bench_extra `, and a number-only few into the line's `extra` -- never
+more (round 5's 25 KB line could not be parsed by the driver).  `--no-cpu-baseline` / `--no-extra` trim a `--full` run.
+
+`--dump-outputs DIR`: what the timed path returned in its last timed step, as DIR/<name>.npy (float32; the voxel indices float64):
+odf [nvert, S] (nvert = 321: sphere_642 folded), peak1..3 [3, S], qa1..3 [S] for a fixed, seeded sample of S = min(16384, voxels)
+voxels (voxel_index.npy: their indices into the whole volume, ascending), and odfmax [2].  About 21 MB at S = 16384; the inputs are
+seeded, so runs with the same arguments can be compared output for output."""
 import argparse
 import json
 import os
@@ -217,6 +227,43 @@ def launch_ranks(n, argv):
     return 0
 
 
+# ---- --dump-outputs ----------------------------------------------------------------------------------------------------------------
+DUMP_VOXELS = 16384          # odf sample = 321 x 16384 float32 = 21 MB; the whole dump stays well under 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_sample(nvox):
+    """the fixed voxel sample of --dump-outputs: min(DUMP_VOXELS, nvox) distinct indices into the whole volume, ascending"""
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.choice(nvox, size=min(DUMP_VOXELS, nvox), replace=False))
+
+
+def dump_outputs(dirname, out, nvox, v0, v1, multi, rank):
+    """DIR/<name>.npy from the GQI step's output dict (odf [nvert, nloc], peak[k] [3, nloc], qa[k] [nloc], odfmax [2]) at the sampled
+    voxels.  With several ranks each gathers the sampled voxels of its slab [v0, v1) and rank 0 writes (slabs ascend with the rank,
+    so the concatenation keeps the sample's order)."""
+    import torch
+    idx = dump_sample(nvox)
+    sel = torch.from_numpy(idx[(idx >= v0) & (idx < v1)] - v0).to(out["odf"].device)
+    part = dict(odf=out["odf"].index_select(1, sel).cpu().numpy())
+    for k in range(3):
+        part["peak%d" % (k + 1)] = out["peak"][k].index_select(1, sel).cpu().numpy()
+        part["qa%d" % (k + 1)] = out["qa"][k].index_select(0, sel).cpu().numpy()
+    parts = [part]
+    if multi:
+        import torch.distributed as dist
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, part)
+    if rank != 0:
+        return
+    arrays = {k: np.concatenate([p[k] for p in parts], axis=-1).astype(np.float32) for k in part}
+    arrays["odfmax"] = out["odfmax"].cpu().numpy().astype(np.float32)
+    arrays["voxel_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 # ---- the result line ---------------------------------------------------------------------------------------------------------------
 # what the line keeps of each leg of `extra` (tools/bench_legs.py returns more; all of it is in bench_extra.json): numbers only
 KEEP = {
@@ -288,7 +335,7 @@ def compact_line(full):
         elif leg in KEEP:
             ex[leg] = {k: rec[k] for k in KEEP[leg] if rec.get(k) is not None}
     line["extra"] = ex
-    line["extra_file"] = "bench_extra.json"
+    line["extra_file"] = full.get("extra_file", "bench_extra.json")
     return _r(line)
 
 
@@ -297,9 +344,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure the CPU baselines and every leg beyond the headline (bench_extra.json)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the legs beyond the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (a seeded voxel sample) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- `--gpus N` means N ranks.  Under a launcher (WORLD_SIZE set: the driver's torch.distributed.run) this process is one of
     # them.  Without one and N > 1 the N ranks are started here as CHILD processes of torch.distributed.run, before this process has
@@ -430,13 +481,17 @@ def main():
 
     dt = timed(gqi_step, args.steps, args.warmup, only="odf_gemm")      # the timed steps bracket the roofline's kernel only
     gemm_ms, gemm_n = prof_get("odf_gemm")
-    # the step's other launches, from a few more steps with every kernel bracketed (outside the timed region)
-    L.fib_profile_enable(1); L.fib_profile_reset()
-    for _ in range(5):
-        gqi_step()
-    sync()
-    L.fib_profile_enable(0)
-    other_ms = sum(prof_get(k)[0] for k in ("odf_peaks", "odf_post", "mask_compact", "qa_normalize")) / 5.0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, nvox, v0, v1, multi, rank)
+    other_ms = None
+    if args.full:
+        # the step's other launches, from a few more steps with every kernel bracketed (outside the timed region)
+        L.fib_profile_enable(1); L.fib_profile_reset()
+        for _ in range(5):
+            gqi_step()
+        sync()
+        L.fib_profile_enable(0)
+        other_ms = sum(prof_get(k)[0] for k in ("odf_peaks", "odf_post", "mask_compact", "qa_normalize")) / 5.0
     value = nvox * args.steps / dt / 1e6
     step_ms = dt / args.steps * 1e3
 
@@ -463,7 +518,8 @@ def main():
     else:
         roofline = dict(bound="mfma", kernel="odf_gemm_kernel<10,1> (v_mfma_f32_32x32x2_f32) + separate peak kernel", achieved=tfs, peak=PEAK_F32_TFLOPS,
                         unit="TFLOP/s", frac=tfs / PEAK_F32_TFLOPS, hbm_frac=gbs / PEAK_HBM_GBS)
-    roofline.update(algorithmic_bytes=gemm_bytes, avg_kernel_ms=gemm_avg_ms, launches=gemm_n, traffic=None, step_launches_ms=gemm_avg_ms + other_ms)
+    roofline.update(algorithmic_bytes=gemm_bytes, avg_kernel_ms=gemm_avg_ms, launches=gemm_n, traffic=None,
+                    step_launches_ms=gemm_avg_ms + other_ms if other_ms is not None else None)
     if world == 1 and shape == SHAPE:
         tj = legs.stored_traffic()                            # STORED: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE, separate passes (tools/collect_profiles.sh)
         roofline["traffic"] = tj.get("odf_gemm_bytes_per_launch")
@@ -484,7 +540,8 @@ def main():
             extra[name] = dict(error="%s: %s" % (type(e).__name__, e))
             sys.stderr.write("bench.py: leg %s failed: %s\n" % (name, e))
 
-    if not args.no_extra and world == 1:
+    run_extra = args.full and not args.no_extra
+    if run_extra and world == 1:
         leg("host_tier", lambda: legs.host_tier(ctx))                                 # (first: see its docstring)
         if hasattr(legs, "pipeline"):
             leg("pipeline", lambda: legs.pipeline(ctx))
@@ -494,7 +551,7 @@ def main():
         except Exception as e:                                                       # noqa: BLE001
             roofline["power"] = dict(error=str(e))
         leg("gqi_variants", lambda: legs.gqi_variants(ctx, plan, dwi, out, step_ms), into=extra)
-    if not args.no_extra:
+    if run_extra:
         if multi:
             del out, dwi
             torch.cuda.empty_cache()
@@ -507,9 +564,9 @@ def main():
         leg("c5", lambda: legs.c5(ctx), into=extra)
         torch.cuda.empty_cache()
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_gqi(bval, bvec, sph, seed=3)    # (rank 0 only; at N > 1 the other ranks wait at the barrier below)
-        if not args.no_extra and world == 1:
+        if run_extra and world == 1:
             b2, g2 = phantom.scheme_dti(60, 4, 1000.0, seed=2)
             b5, g5 = phantom.scheme_dsi()
             extra["cpu_baselines"] = dict(dti_fit=cpu_baseline_dti(b2, g2), dsi_rec=cpu_baseline_dsi(b5, g5, sph), stream=cpu_baseline_stream())
@@ -526,12 +583,15 @@ def main():
                                 voxels=nvox, voxels_per_gpu=nloc, frames=nvol, odf_vertices=nvert,
                                 parallelism="z-slabs over the ranks (gqi.jl:132) + 2-float all-reduce(MAX) of odfmax (gqi.jl:164)" if world > 1 else "single GPU"),
                     preconditioning_s=PRECOND_S, roofline=roofline, cpu_baseline=cpu, extra=extra)
-        try:
-            with open(os.path.join(ROOT, "bench_extra.json"), "w") as f:
-                json.dump(full, f, indent=1)
-        except OSError as e:
-            sys.stderr.write("bench.py: cannot write bench_extra.json: %s\n" % e)
-        print("bench_extra " + json.dumps(full), flush=True)      # (an EARLIER line that does not start with `{`)
+        if args.full:
+            try:
+                with open(os.path.join(ROOT, "bench_extra.json"), "w") as f:
+                    json.dump(full, f, indent=1)
+            except OSError as e:
+                sys.stderr.write("bench.py: cannot write bench_extra.json: %s\n" % e)
+            print("bench_extra " + json.dumps(full), flush=True)      # (an EARLIER line that does not start with `{`)
+        else:
+            full["extra_file"] = None                                 # (a plain run writes no bench_extra.json)
         text = json.dumps(compact_line(full))
         if len(text) > MAX_LINE:                                  # never again a line the driver cannot parse: drop the extras before the contract's keys
             small = compact_line(dict(full, extra={}))

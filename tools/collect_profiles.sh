@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 # (200 timed steps: the kernel's average over the whole run is then the steady state's, comparable with the line's hipEvent average -- the
 # preconditioning and warm-up steps in front of the timed region run while the chip still leaves its idle power state)
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/bench -o bench -- python3 bench.py --no-cpu-baseline --no-extra --steps 200 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats -f csv -d $OUT/benchfull -o benchfull -- python3 bench.py --no-cpu-baseline > $OUT/benchfull.json 2> $OUT/benchfull.err
+rocprofv3 --kernel-trace --stats -f csv -d $OUT/benchfull -o benchfull -- python3 bench.py --full --no-cpu-baseline > $OUT/benchfull.json 2> $OUT/benchfull.err
 for what in gqi dti stream dsi c5; do
   rocprofv3 --kernel-trace --stats -f csv -d $OUT/$what -o $what -- python3 tools/prof_step.py $what 5 > $OUT/$what.log 2>&1
 done
