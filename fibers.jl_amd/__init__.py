@@ -11,7 +11,7 @@ from .dti import DTI, DtiPlan, adc_fit, adc_fit_device, dti_fit, dti_fit_device 
 from .gqi import (DSI, GQI, OdfPlan, dsi_rec, find_peaks, find_peaks_device, find_peaks_work, gqi_rec, odf_rec_device,  # noqa: F401
                   qa_normalize_device)
 from .rumba import RUMBASD, RumbaPlan, rumba_rec, rumba_rec_device  # noqa: F401
-from .structens import st_eigen, st_eigen_device  # noqa: F401
+from .structens import st_eigen, st_eigen_device, st_recon, st_recon_device, st_recon_halo  # noqa: F401
 from .tract import Tract  # noqa: F401
 from .stream import (StreamBuffers, StreamWorkspace, angles_to_vectors, angles_to_vectors_device, make_sublist, stream,  # noqa: F401
                      stream_device, stream_device_run, stream_device_run_enqueue, stream_field_device)

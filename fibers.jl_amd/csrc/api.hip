@@ -487,6 +487,48 @@ extern "C" int fib_st_eigen(int device, const float *const S[6], int64_t nvox, f
     return FIB_OK;
 } FIB_API_CATCH
 
+// st_recon host form: z-slabs of the volume, each uploaded with its halo; a slab's outputs scatter into the [nx,ny,nz,...] arrays
+extern "C" int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sigma, float rho, float *eigvec, float *eigval) try {
+    FIB_CHECK(vol && eigvec && eigval, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "nx, ny, nz must be positive");
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "st_recon runs on one device (FIB_DEVICE_ALL is not supported)");
+    int halo = 0;
+    RC(fib_st_recon_halo(sigma, rho, &halo));
+    fib::DeviceGuard guard;
+    RC(fib::use_device(device));
+    const size_t plane = (size_t)nx * ny;
+    int nzs = 0;
+    if (const char *e = fib::env("FIBERS_ST_RECON_SLAB")) nzs = atoi(e);
+    if (nzs <= 0) {                     // half the free memory: per output plane 4 (vol) + 12 (gradients) + 48 (outputs) bytes a voxel
+        size_t fr = 0, tot = 0;
+        FIB_HIP(hipMemGetInfo(&fr, &tot));
+        const double planes = (double)(fr / 2) / (double)plane - 16.0 * 2 * halo;   // less the halos of vol and of the gradients
+        nzs = planes / 64.0 >= nz ? nz : (int)(planes / 64.0);
+        FIB_CHECK(nzs >= 1, FIB_ERR_NOMEM, "st_recon: one %d x %d plane with its halo does not fit in device memory", nx, ny);
+    }
+    if (nzs > nz) nzs = nz;
+    size_t work_bytes = 0;
+    RC(fibd_st_recon_work_size(nx, ny, nzs, sigma, rho, &work_bytes));
+    const int nzin_max = std::min(nz, nzs + 2 * halo);
+    fib::DevBuf<float> d_vol, d_out;
+    fib::DevBuf<char> d_work;
+    RC(d_vol.alloc(plane * nzin_max));
+    RC(d_out.alloc(plane * nzs * 12));
+    RC(d_work.alloc(work_bytes));
+    const size_t nvox = plane * nz;
+    for (int z0 = 0; z0 < nz; z0 += nzs) {
+        const int z1 = std::min(nz, z0 + nzs), zin0 = std::max(0, z0 - halo), zin1 = std::min(nz, z1 + halo);
+        const size_t nout = plane * (z1 - z0);
+        RC(h2d(d_vol.p, vol + plane * zin0, sizeof(float) * plane * (zin1 - zin0)));
+        RC(fibd_st_recon(d_vol.p, nx, ny, nz, zin0, zin1 - zin0, z0, z1, sigma, rho, d_out.p, d_out.p + 9 * nout, nullptr,
+                         d_work.p, work_bytes, nullptr));
+        FIB_HIP(hipDeviceSynchronize());
+        for (int k = 0; k < 9; k++) RC(d2h(eigvec + k * nvox + plane * z0, d_out.p + k * nout, sizeof(float) * nout));
+        for (int k = 0; k < 3; k++) RC(d2h(eigval + k * nvox + plane * z0, d_out.p + (9 + k) * nout, sizeof(float) * nout));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // gqi_rec / dsi_rec
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@
 #ifndef FIBERS_HIP_H
 #define FIBERS_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -149,6 +150,18 @@ int fibd_adc_fit(const fib_dti_plan *plan, const float *dwi, const uint8_t *mask
  * S = {Sxx, Sxy, Sxz, Syy, Syz, Szz}, each [nvox]; eigval [nvox*3] ascending (eigval[ix,iy,iz,k]);
  * eigvec [nvox*9], component i of eigenvector j at (i + 3*j)*nvox + vox (eigvec[ix,iy,iz,i,j]). */
 int fibd_st_eigen(const float *const S[6], int64_t nvox, float *eigvec, float *eigval, void *stream);
+/* st_recon (structens.jl:40-88): G_sigma smoothing (skipped when sigma <= 0), Scharr gradients, the six products, G_rho smoothing
+ * (skipped when rho <= 0), eigen(Symmetric(S, :L)); every filter is imfilter(..., "reflect").  Radii 2*ceil(sigma) and
+ * 2*ceil(rho) up to 16 (sigma, rho <= 8); larger ones are FIB_ERR_UNSUPPORTED.
+ * vol: planes [zin0, zin0 + nzin) of an nx*ny*nz float volume, x fastest.  Writes output planes [z0, z1); vol must hold
+ * [max(0, z0-H), min(nz, z1+H)) with H = fib_st_recon_halo(sigma, rho) (reflection is taken against the whole volume).
+ * eigvec [9][nvox_out], eigval [3][nvox_out] in fibd_st_eigen's layout, nvox_out = nx*ny*(z1-z0).  S_out: NULL, or six [nvox_out]
+ * volumes that receive the smoothed tensor (Sxx Sxy Sxz Syy Syz Szz) that was decomposed.  work: device scratch of at least
+ * fibd_st_recon_work_size(nx, ny, z1 - z0, ...) bytes (the gradients). */
+int fib_st_recon_halo(float sigma, float rho, int *halo);
+int fibd_st_recon_work_size(int nx, int ny, int nz_out, float sigma, float rho, size_t *bytes);
+int fibd_st_recon(const float *vol, int nx, int ny, int nz, int zin0, int nzin, int z0, int z1, float sigma, float rho,
+                  float *eigvec, float *eigval, float *const *S_out, void *work, size_t work_bytes, void *stream);
 /* number of voxels the last fibd_dti_fit/fibd_adc_fit call on this plan sent through the
  * per-voxel pinv branch (dti.jl:297-298, 206-207); synchronises `stream`. */
 int fibd_dti_last_partial_count(const fib_dti_plan *plan, void *stream, int64_t *count);
@@ -376,6 +389,11 @@ int fib_dti_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
 /* adc_fit(dwi::MRI, mask::MRI) (dti.jl:164) */
 /* host-buffer form of fibd_st_eigen (structens.jl:13-37) */
 int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigvec, float *eigval);
+/* host-buffer form of fibd_st_recon: eigvec [nx,ny,nz,3,3], eigval [nx,ny,nz,3] as st_recon returns them (column-major).  The volume
+ * goes through in z-slabs sized to half the free device memory (FIBERS_ST_RECON_SLAB=<planes> overrides), each with its halo, so a
+ * volume larger than the device's memory still goes through; results do not depend on the slab thickness.  FIB_DEVICE_ALL:
+ * FIB_ERR_UNSUPPORTED. */
+int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sigma, float rho, float *eigvec, float *eigval);
 int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, float *adc, float *s0);
 /* gqi_rec(dwi, mask, odf_dirs, sigma)::GQI (gqi.jl:109) */

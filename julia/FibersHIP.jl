@@ -159,6 +159,16 @@ function st_eigen(Sxx::Array{Float32,3}, Sxy::Array{Float32,3}, Sxz::Array{Float
   return eigvec, eigval
 end
 
+"st_recon(vol, sigma, rho) — replaces structens.jl:40-88 (sigma, rho <= 8; each stage skipped when <= 0)"
+function st_recon(vol::Array{Float32,3}, sigma::Number, rho::Number; device::Integer=0)
+  nx, ny, nz = size(vol)
+  eigvec = Array{Float32,5}(undef, nx, ny, nz, 3, 3)
+  eigval = Array{Float32,4}(undef, nx, ny, nz, 3)
+  GC.@preserve vol eigvec eigval fib_check(ccall((:fib_st_recon, libfibers), Cint,
+      (Cint, Ptr{Cfloat}, Cint, Cint, Cint, Cfloat, Cfloat, Ptr{Cfloat}, Ptr{Cfloat}), device, vol, nx, ny, nz, sigma, rho, eigvec, eigval))
+  return eigvec, eigval
+end
+
 "rumba_rec(dwi, mask, odf_dirs, niter, ...) — replaces rusd.jl:419-636"
 function rumba_rec(dwi::MRI, mask::MRI, odf_dirs::ODF=sphere_724, niter::Integer=600, λ_para::Float32=Float32(1.7e-3),
                    λ_perp::Float32=Float32(0.2e-3), λ_csf::Float32=Float32(3.0e-3), λ_gm::Float32=Float32(0.8e-4),
