@@ -18,3 +18,4 @@ from .stream import (StreamBuffers, StreamWorkspace, angles_to_vectors, angles_t
 from .nifti import (dsi_write, dti_write, gqi_write, load_nifti, mri_read, mri_read_bfiles, mri_write, rumba_write,  # noqa: F401
                     read_struct)
 from .trk import str_add, stream_to_trk, tract_header, trk_read, trk_write  # noqa: F401
+from .xform import Xform, str_merge, str_xform, xfm_apply, xfm_compose, xfm_inv, xfm_read, xfm_rotate  # noqa: F401

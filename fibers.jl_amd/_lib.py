@@ -91,6 +91,9 @@ _PROTOS = {
     "fibd_stream_ws_destroy": (None, [vp]),
     "fibd_stream_pack": (i32, [vp, vp, vp, vp, vp]),
     "fibd_stream_pack_trk": (i32, [vp, C.POINTER(C.c_float * 3), vp, vp]),
+    "fibd_stream_pack_trk_xfm": (i32, [vp, C.POINTER(C.c_float * 16), C.POINTER(C.c_float * 3), vp, vp]),
+    "fibd_xfm_apply": (i32, [C.POINTER(C.c_float * 16), vp, vp, i64, vp]),
+    "fib_xfm_apply": (i32, [i32, C.POINTER(C.c_float * 16), vp, vp, i64]),
     "fibd_stream_trace_lcm": (i32, [C.POINTER(StreamParams), vp, vp, f32, i32, i32, C.c_uint64, vp, i64, vp, i32, vp,
                                     C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]),
     "fibd_stream_pack_flags": (i32, [vp, vp, vp, vp, vp, vp]),

@@ -487,6 +487,30 @@ extern "C" int fib_st_eigen(int device, const float *const S[6], int64_t nvox, f
     return FIB_OK;
 } FIB_API_CATCH
 
+// xfm_apply host form: the 3 npoints floats are one planar row of 3 npoints "voxels" for the chunk pipeline (no mask).  Chunks and
+// worker slabs start at multiples of 3 floats: the chunk is 3 * 2^17 floats, so its 1/8, 1/4, 1/2 lead-in pieces (host_tier.h:
+// chunk_schedule) are multiples of 96, and the slabs are cut at whole points.
+extern "C" int fib_xfm_apply(int device, const float vox2vox[16], const float *in, float *out, int64_t npoints) try {
+    FIB_CHECK(npoints >= 0, FIB_ERR_INVALID, "npoints must not be negative");
+    if (npoints == 0) return FIB_OK;
+    FIB_CHECK(vox2vox && in && out, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(in == out || in + 3 * npoints <= out || out + 3 * npoints <= in, FIB_ERR_INVALID, "in and out must be the same array or not overlap");
+    const int64_t nf = 3 * npoints;
+    std::vector<Worker> ws;
+    RC(workers_for(device, ws));
+    const std::vector<Rows> ins = {{in, nullptr, 1}};
+    const std::vector<Rows> outs = {{nullptr, out, 1}};
+    constexpr int64_t chunk = (int64_t)3 << 17;
+    return for_each_worker(ws, [&](int i, DevState &d) -> int {
+        const int64_t n = (int64_t)ws.size();
+        const int64_t v0 = 3 * (npoints * i / n), v1 = 3 * (npoints * (i + 1) / n);
+        return run_chunks(d, v0, v1, nf, ins, nullptr, 0, outs, chunk,
+                          [&](int, int64_t, int64_t nd, const float *din, const uint8_t *, float *dout, hipStream_t st) -> int {
+                              return fibd_xfm_apply(vox2vox, din, dout, nd / 3, st);
+                          });
+    });
+} FIB_API_CATCH
+
 // st_recon host form: z-slabs of the volume, each uploaded with its halo; a slab's outputs scatter into the [nx,ny,nz,...] arrays
 extern "C" int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sigma, float rho, float *eigvec, float *eigval) try {
     FIB_CHECK(vol && eigvec && eigval, FIB_ERR_INVALID, "NULL argument");

@@ -302,7 +302,8 @@ enum Event { E_IN = 0, E_CMP = 1, E_OUT = 2 };           // per ring slot: uploa
 //   int   fail(int code, const char *msg)               records the message for fib_last_error(), returns code
 //   std::string last_error() / void set_error(const std::string &)   hand a worker thread's message to the calling thread
 //
-// voxels [vbeg, vend) of a volume of nvox voxels.  Blocking.  lm != NULL: only the voxels inside the mask travel (LiveMap); the fit then
+// voxels [vbeg, vend) of a volume of nvox voxels.  Blocking.  mask == NULL (and lm == NULL): no mask bytes are gathered or uploaded,
+// the fit's mask pointer is not to be read.  lm != NULL: only the voxels inside the mask travel (LiveMap); the fit then
 // sees dense chunks whose mask is all ones (padded with voxels outside to a multiple of 32) and `rel` counts voxels inside the mask.
 // outputs_zeroed (FIB_MASK_OUTPUTS_ZEROED): the caller's output arrays are zero already -- the gaps between the runs are left alone.
 // nt: the row copies of the packed form and the scatter of whole rows use streaming stores (copy_stream / zero_stream).
@@ -382,7 +383,7 @@ int run_chunks(Dev &dev, CopyPool &pool_in, CopyPool &pool_out, int64_t vbeg, in
                 for (auto &r : ins) for (int i = 0; i < r.nrows; i++) { rows.emplace_back(dst, r.in + (int64_t)i * nvox + v0); dst += n; }
                 pool_in.run((int)rows.size() + 1, [&](int i) {
                     if (i < (int)rows.size()) memcpy(rows[i].first, rows[i].second, (size_t)n * 4);
-                    else if (!mask_convert_range(mask, mask_dtype, v0, n, false, m8)) mok = false;
+                    else if (mask && !mask_convert_range(mask, mask_dtype, v0, n, false, m8)) mok = false;
                 });
             } else {
                 for (auto &r : ins) for (int i = 0; i < r.nrows; i++) { rows.emplace_back(dst, r.in + (int64_t)i * nvox); dst += nd; }
@@ -397,7 +398,7 @@ int run_chunks(Dev &dev, CopyPool &pool_in, CopyPool &pool_out, int64_t vbeg, in
         }
         dev.prof("host_gather", ms(tg1, clk::now()));
         dev.prof("host_gather_wait", ms(tg0, tg1));
-        const size_t ib = (size_t)rin * nd * 4 + (size_t)nd;
+        const size_t ib = (size_t)rin * nd * 4 + (mask ? (size_t)nd : 0);   // (no mask: nothing to upload after the rows)
         int rc;
         // device buffers of this ring slot: the kernels of chunk k - NBUF have read the input, its download has read the output
         if (k >= NBUF) {

@@ -794,6 +794,8 @@ __global__ __launch_bounds__(SCAN_T) void scan_totals_kernel(Pair *block_tot, in
     }
 }
 
+#include "xfm_apply.inc"
+
 struct PackArgs {
     const float *scratch;
     const int32_t *npts, *nfwd;
@@ -812,6 +814,7 @@ struct PackArgs {
     // the 17 ms of the 2048^2 benchmark section)
     int lcm;
     uint8_t *out_flags;
+    XfmMat xf;                  // the pack kernels' XF variant (fibd_stream_pack_trk_xfm): vox2vox applied before the .trk epilogue
 };
 
 // One wave per scratch tile (16 lines), four independent waves per workgroup: no workgroup barriers.  A chunk = 16 slots of
@@ -821,6 +824,9 @@ struct PackArgs {
 // backward slots follow (stream.jl:652).
 constexpr int PK_LINES = SCR_TILE, PK_SLOTS = 16, PK_ROW = 52, PK_WAVES = 4;
 static_assert(PK_LINES == 16, "the pack kernel maps 16 lanes to the 16 lines of a tile");
+// XF (with a.trk): str_xform's xfm_apply (trk.jl:345, util.jl:401-420) on every point before the .trk epilogue; XF = false is the
+// kernel fibd_stream_pack / fibd_stream_pack_trk have always run
+template <bool XF = false>
 __global__ __launch_bounds__(PK_WAVES * 64) void stream_pack_kernel(const PackArgs a) {
     __shared__ __attribute__((aligned(16))) float tile[PK_WAVES][2][PK_SLOTS * PK_ROW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -896,7 +902,12 @@ __global__ __launch_bounds__(PK_WAVES * 64) void stream_pack_kernel(const PackAr
                 struct P3 { float x, y, z; };
                 const float *t = T + pt * PK_ROW + tl * 3;
                 float *d = a.out_xyz + wp0[j] + p * 3;
-                if (a.trk)                                      // T.((xyz .+ .5) .* voxel_size), Float64 arithmetic (trk.jl:475-476)
+                if (XF) {                                       // xfm_apply, then the epilogue below (always .trk)
+                    const float3 r = xfm_point(a.xf, t[0], t[1], t[2]);
+                    *reinterpret_cast<P3 *>(d) =
+                        P3{(float)(((double)r.x + 0.5) * (double)a.vs[0]), (float)(((double)r.y + 0.5) * (double)a.vs[1]),
+                           (float)(((double)r.z + 0.5) * (double)a.vs[2])};
+                } else if (a.trk)                               // T.((xyz .+ .5) .* voxel_size), Float64 arithmetic (trk.jl:475-476)
                     *reinterpret_cast<P3 *>(d) =
                         P3{(float)(((double)t[0] + 0.5) * (double)a.vs[0]), (float)(((double)t[1] + 0.5) * (double)a.vs[1]),
                            (float)(((double)t[2] + 0.5) * (double)a.vs[2])};
@@ -914,7 +925,8 @@ __global__ __launch_bounds__(PK_WAVES * 64) void stream_pack_kernel(const PackAr
 // out with 16-byte stores aligned to the output address (fill-like: 12-byte stores in 192-byte runs reached 2.7 TB/s,
 // aligned 16-byte stores of whole lines reach twice that).  LDS = 16 (len_max + 2) points; longer lines than the LDS
 // holds go through stream_pack_kernel above.
-template <int TL, int SPC>   // TL lines per tile (a whole fraction of a scratch row); SPC slots per pass of the workgroup's SPC x TL threads
+template <int TL, int SPC, bool XF = false>   // TL lines per tile (a whole fraction of a scratch row); SPC slots per pass of the workgroup's
+                                              // SPC x TL threads; XF: as stream_pack_kernel's
 __global__ __launch_bounds__(SPC * TL) void stream_pack_tile_kernel(const PackArgs a) {
     extern __shared__ __attribute__((aligned(16))) float obuf[];
     __shared__ int s_nf[TL], s_nb[TL], s_bs[TL], s_o[TL];   // per line: forward / backward counts (0 if dropped), first backward slot, offset in obuf
@@ -991,7 +1003,11 @@ __global__ __launch_bounds__(SPC * TL) void stream_pack_tile_kernel(const PackAr
         for (int i = 0; i < 4; i++) {
             if (pos[i] < 0) continue;
             float *d = obuf + o + pos[i] * 3;
-            if (a.trk) {                                        // T.((xyz .+ .5) .* voxel_size), Float64 arithmetic (trk.jl:475-476)
+            if (XF) {                                           // xfm_apply, then the epilogue below (always .trk)
+                const float3 r = xfm_point(a.xf, v[i].x, v[i].y, v[i].z);
+                d[0] = (float)(((double)r.x + 0.5) * (double)a.vs[0]); d[1] = (float)(((double)r.y + 0.5) * (double)a.vs[1]);
+                d[2] = (float)(((double)r.z + 0.5) * (double)a.vs[2]);
+            } else if (a.trk) {                                        // T.((xyz .+ .5) .* voxel_size), Float64 arithmetic (trk.jl:475-476)
                 d[0] = (float)(((double)v[i].x + 0.5) * (double)a.vs[0]); d[1] = (float)(((double)v[i].y + 0.5) * (double)a.vs[1]);
                 d[2] = (float)(((double)v[i].z + 0.5) * (double)a.vs[2]);
             } else if (a.lcm) {
@@ -1487,6 +1503,7 @@ __global__ __launch_bounds__(256) void stream_unpack_flags_kernel(float *xyz, ui
 static int pack_plain(fib_stream_job *job, int32_t *npts, int64_t *seed_index, float *xyz, uint8_t *flags, bool *flags_done, void *stream);
 
 // whole-tile kernel while 16 (len_max + 2) points (+ the .trk headers and the alignment slack) fit in LDS
+template <bool XF = false>
 static int launch_pack_n(const PackArgs &pa_in, int64_t nlines, int stride, hipStream_t st, bool *flags_done = nullptr) {
     PackArgs pa = pa_in;
     const size_t smem = ((size_t)PK_LINES * stride * 3 + PK_LINES + 8) * sizeof(float) + (pa.lcm ? (((size_t)PK_LINES * stride + 15) & ~(size_t)15) : 0);
@@ -1494,16 +1511,17 @@ static int launch_pack_n(const PackArgs &pa_in, int64_t nlines, int stride, hipS
     if (smem > 120 * 1024) { pa.lcm = 0; pa.out_flags = nullptr; }
     if (smem <= 120 * 1024) {
         if (smem > 48 * 1024)
-            FIB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_pack_tile_kernel<PK_LINES, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL((stream_pack_tile_kernel<PK_LINES, 16>), dim3((unsigned)fib::cdiv(nlines, PK_LINES)), dim3(16 * PK_LINES), smem, st, pa);
+            FIB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_pack_tile_kernel<PK_LINES, 16, XF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        hipLaunchKernelGGL((stream_pack_tile_kernel<PK_LINES, 16, XF>), dim3((unsigned)fib::cdiv(nlines, PK_LINES)), dim3(16 * PK_LINES), smem, st, pa);
     } else
-        hipLaunchKernelGGL(stream_pack_kernel, dim3((unsigned)fib::cdiv(nlines, PK_LINES * PK_WAVES)), dim3(PK_WAVES * 64), 0, st, pa);
+        hipLaunchKernelGGL(stream_pack_kernel<XF>, dim3((unsigned)fib::cdiv(nlines, PK_LINES * PK_WAVES)), dim3(PK_WAVES * 64), 0, st, pa);
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 }
+template <bool XF = false>
 static int launch_pack(fib_stream_job *job, const PackArgs &pa, hipStream_t st, bool *flags_done = nullptr) {
     job->last_stream = st;
-    return launch_pack_n(pa, job->nlines, job->stride, st, flags_done);
+    return launch_pack_n<XF>(pa, job->nlines, job->stride, st, flags_done);
 }
 
 extern "C" int fibd_stream_pack_flags(fib_stream_job *job, int32_t *npts, int64_t *seed_index, float *xyz, uint8_t *flags, void *stream) try {
@@ -1543,7 +1561,8 @@ static int pack_plain(fib_stream_job *job, int32_t *npts, int64_t *seed_index, f
     return FIB_OK;                                      // (LCM jobs whose lines do not fit the tile kernel: x still carries the flag bit; the caller strips it)
 }
 
-extern "C" int fibd_stream_pack_trk(fib_stream_job *job, const float voxel_size[3], void *body, void *stream) try {
+// fibd_stream_pack_trk and fibd_stream_pack_trk_xfm (vox2vox != NULL: the XF variant of the pack kernels)
+static int pack_trk(fib_stream_job *job, const float *vox2vox, const float voxel_size[3], void *body, void *stream) {
     FIB_CHECK(job != nullptr && voxel_size != nullptr, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(!job->lcm, FIB_ERR_UNSUPPORTED, "the .trk body serialiser does not carry the per-point scalars of an LCM run");
     if (job->kept_lines == 0) return FIB_OK;
@@ -1558,10 +1577,20 @@ extern "C" int fibd_stream_pack_trk(fib_stream_job *job, const float voxel_size[
     pa.stride = job->stride; pa.nslots = job->nslots; pa.len_min = job->prm.len_min;
     pa.scratch_plain = fib::ab_env("FIBERS_STREAM_PACK_PLAIN") != nullptr;
     pa.trk = 1; pa.vs[0] = voxel_size[0]; pa.vs[1] = voxel_size[1]; pa.vs[2] = voxel_size[2];
-    fib::ProfScope prof("stream_pack_trk", (hipStream_t)stream);
-    { const int rcl = launch_pack(job, pa, (hipStream_t)stream); if (rcl != FIB_OK) return rcl; }
+    if (vox2vox) memcpy(pa.xf.m, vox2vox, sizeof pa.xf.m);
+    fib::ProfScope prof(vox2vox ? "stream_pack_trk_xfm" : "stream_pack_trk", (hipStream_t)stream);
+    { const int rcl = vox2vox ? launch_pack<true>(job, pa, (hipStream_t)stream) : launch_pack(job, pa, (hipStream_t)stream); if (rcl != FIB_OK) return rcl; }
     FIB_HIP(hipGetLastError());
     return FIB_OK;
+}
+
+extern "C" int fibd_stream_pack_trk(fib_stream_job *job, const float voxel_size[3], void *body, void *stream) try {
+    return pack_trk(job, nullptr, voxel_size, body, stream);
+} FIB_API_CATCH
+
+extern "C" int fibd_stream_pack_trk_xfm(fib_stream_job *job, const float vox2vox[16], const float voxel_size[3], void *body, void *stream) try {
+    FIB_CHECK(vox2vox != nullptr, FIB_ERR_INVALID, "NULL argument");
+    return pack_trk(job, vox2vox, voxel_size, body, stream);
 } FIB_API_CATCH
 
 // stream (stream.jl:730-790) in ONE call, straight into the caller's buffers (no second call, no allocation by the library):

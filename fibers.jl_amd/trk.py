@@ -9,6 +9,7 @@ pack kernel writes the file body (Int32 npts + npts x 3 Float32 per line) in HBM
 prepends the 1000-byte header."""
 import ctypes as C
 import struct
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -180,10 +181,11 @@ def _download_and_write(path, header: bytes, body, piece: int = 32 << 20):
         os.close(fd)
 
 
-def stream_to_trk(outfile, field, shape, seeds, sublist, ref: MRI, stream=None, timings=None, **kw) -> dict:
+def stream_to_trk(outfile, field, shape, seeds, sublist, ref: MRI, stream=None, timings=None, xfm=None, **kw) -> dict:
     """GPU path: trace, then let the pack kernel emit the .trk body directly (device tier: fibd_stream_pack_trk, trk.jl:471-482), downloaded
     in pieces through pinned staging buffers while the previous piece is written.  timings (optional dict): perf_counter stamps `device_done` (trace + pack finished)
-    and `file_done`."""
+    and `file_done`.  xfm (an `Xform`): the file is trk_write(str_xform(xfm, tr)) -- the pack kernel applies xfm.vox2vox to every point
+    on its way out (fibd_stream_pack_trk_xfm) and the header carries the output space (outsize, outres, outvox2ras)."""
     import time
     import torch
     from .stream import _params, default_workspace
@@ -199,8 +201,15 @@ def stream_to_trk(outfile, field, shape, seeds, sublist, ref: MRI, stream=None, 
                                    sublist.data_ptr(), sublist.shape[0], sp, C.byref(job), C.byref(nl), C.byref(npnt)))
     try:
         body = torch.empty(nl.value + 3 * npnt.value, dtype=torch.float32, device=field.device)
-        vs = (C.c_float * 3)(*[float(np.float32(v)) for v in ref.volres[:3]])
-        _lib.check(L.fibd_stream_pack_trk(job, C.byref(vs), body.data_ptr(), sp))
+        if xfm is None:
+            vs = (C.c_float * 3)(*[float(np.float32(v)) for v in ref.volres[:3]])
+            _lib.check(L.fibd_stream_pack_trk(job, C.byref(vs), body.data_ptr(), sp))
+        else:
+            from .xform import _row_major
+            vs = (C.c_float * 3)(*[float(v) for v in xfm.outres])
+            _lib.check(L.fibd_stream_pack_trk_xfm(job, _row_major(xfm), C.byref(vs), body.data_ptr(), sp))
+            ref = SimpleNamespace(volsize=tuple(int(v) for v in xfm.outsize), volres=tuple(float(v) for v in xfm.outres),
+                                  vox2ras=xfm.outvox2ras)
         _sync(stream)                                   # the pack ran on `stream`: a copy only orders against the current one
         if timings is not None:
             timings["device_done"] = time.perf_counter()

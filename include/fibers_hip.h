@@ -346,6 +346,12 @@ int fibd_stream_pack_flags(fib_stream_job *job, int32_t *npts, int64_t *seed_ind
  * trk_write emits it, trk.jl:469-485): per line Int32 npts then npts x 3 Float32 = (xyz + .5) * voxel_size.
  * body: device buffer of 4*nlines + 12*npoints bytes. */
 int fibd_stream_pack_trk(fib_stream_job *job, const float voxel_size[3], void *body, void *stream);
+/* the .trk body of str_xform(xfm, tr) (trk.jl:316-347) for the lines of `job`, straight from the tracer's scratch: every point goes
+ * through xfm_apply (util.jl:401-420, vox2vox as in fibd_xfm_apply, applied to stream's 1-based coordinates as they are) and then
+ * the same epilogue, (p + .5) * voxel_size with voxel_size = xfm.outres.  LCM jobs: FIB_ERR_UNSUPPORTED, as fibd_stream_pack_trk. */
+int fibd_stream_pack_trk_xfm(fib_stream_job *job, const float vox2vox[16], const float voxel_size[3], void *body, void *stream);
+/* fib_xfm_apply's device form: in / out are device buffers, asynchronous on `stream`.  One streaming kernel (24 B per point). */
+int fibd_xfm_apply(const float vox2vox[16], const float *in, float *out, int64_t npoints, void *stream);
 /* per-(seed,sub) point counts of every traced line, incl. those dropped by len_min: int32 [nseed*nsub] */
 int fibd_stream_all_npts(fib_stream_job *job, int32_t *all_npts, void *stream);
 void fib_stream_job_destroy(fib_stream_job *job);
@@ -394,6 +400,14 @@ int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigve
  * volume larger than the device's memory still goes through; results do not depend on the slab thickness.  FIB_DEVICE_ALL:
  * FIB_ERR_UNSUPPORTED. */
 int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sigma, float rho, float *eigvec, float *eigval);
+/* xfm_apply(xfm, point) (util.jl:385-420) on npoints float32 points [npoints][3] (x, y, z of a point adjacent, as the 3N vector the
+ * reference takes).  vox2vox is ROW-major: vox2vox[4 * i + j] = xfm.vox2vox[i + 1, j + 1] (Julia passes permutedims(vox2vox)).
+ * Per point, in float32 with every multiply and add rounded on its own, in the reference's order: w = 0 + m41 x + m42 y + m43 z + m44,
+ * then for each row i (0 + mi1 x + mi2 y + mi3 z + mi4) / w with an IEEE division, also for affine matrices (a non-finite input
+ * gives a NaN triplet, as in the reference).  in == out is allowed; other overlaps are FIB_ERR_INVALID.  Points need only be 4-byte
+ * aligned.  Host-buffer form: the points go through the host tier's chunk pipeline; FIB_DEVICE_ALL splits them over the device set.
+ * npoints == 0 does nothing. */
+int fib_xfm_apply(int device, const float vox2vox[16], const float *in, float *out, int64_t npoints);
 int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, float *adc, float *s0);
 /* gqi_rec(dwi, mask, odf_dirs, sigma)::GQI (gqi.jl:109) */

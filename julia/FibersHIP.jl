@@ -289,3 +289,35 @@ function stream(ovec::Union{MRI,Vector{MRI}}; f::Union{MRI,Vector{MRI},Nothing}=
   str_add!(tr, str, flag)                                             # stream.jl:784-787
   return tr
 end
+
+"xfm_apply(xfm, point) — replaces util.jl:385-420 for Float32 points (a 3N vector or 3 x N matrix); vox2vox goes to the C ABI row-major"
+function xfm_apply(xfm::Xform{Float32}, point::Array{Float32}; device::Integer=0)
+  length(point) % 3 == 0 || error("xfm_apply takes 3N coordinates")
+  newpoint = similar(point)
+  m = Matrix{Float32}(permutedims(xfm.vox2vox))
+  GC.@preserve m point newpoint fib_check(ccall((:fib_xfm_apply, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64), device, m, point, newpoint, length(point) ÷ 3))
+  return newpoint
+end
+
+"str_xform(xfm, tr) — replaces trk.jl:316-347: the points of every line go through ONE fib_xfm_apply call, packed and unpacked"
+function str_xform(xfm::Xform{Float32}, tr::Tract{Float32}; device::Integer=0)
+  trnew = Tract{Float32}()
+  for var in setdiff(fieldnames(Tract), (:dim, :voxel_size, :vox_to_ras, :image_orientation_patient, :xyz))
+    setfield!(trnew, var, getfield(tr, var))
+  end
+  trnew.dim = Int16.(xfm.outsize)
+  trnew.voxel_size = Float32.(xfm.outres)
+  trnew.vox_to_ras = Float32.(xfm.outvox2ras)
+  orient = vox2ras_to_orient(trnew.vox_to_ras)
+  trnew.voxel_order          = vcat(UInt8.(collect(orient)), UInt8(0))
+  trnew.voxel_order_original = trnew.voxel_order
+  p2s = [-1 0 0; 0 -1 0; 0 0 1] * trnew.vox_to_ras[1:3, 1:2] * Diagonal([1, 1]./trnew.voxel_size[1:2])
+  trnew.image_orientation_patient = Float32.(p2s[:])
+  n   = [size(x, 2) for x in tr.xyz]
+  off = cumsum(vcat(0, n))
+  packed = isempty(n) ? Matrix{Float32}(undef, 3, 0) : reduce(hcat, tr.xyz)          # 3 x total: x, y, z of a point adjacent
+  moved  = xfm_apply(xfm, packed; device=device)
+  trnew.xyz = [moved[:, off[i]+1:off[i+1]] for i in 1:length(n)]
+  return trnew
+end
