@@ -92,19 +92,30 @@ class RumbaPlan:
 
 
 def rumba_rec_device(plan: RumbaPlan, dwi, mask, shape, niter=600, ncoils=1, coil_combine="SMF-SENSE", ipat_factor=1,
-                     use_tv=True, stream=None):
+                     use_tv=True, stream=None, out=None):
     """dwi: float32 CUDA [nvol, nvox]; mask uint8 [nvox]; shape = (nx, ny, nz).  Returns dict(fodf [nvert,nvox], fgm, fcsf,
-    gfa, var [nvox], peak [5][3,nvox], snr_mean, snr_std)."""
+    gfa, var [nvox], peak [5][3,nvox], snr_mean, snr_std).  out: such a dict of tensors to write into (every element is
+    written: zeros outside the mask)."""
     import torch
     _chk_dev(dwi, torch.float32, "dwi")
     _chk_dev(mask, torch.uint8, "mask")
     nx, ny, nz = shape
     nvox = nx * ny * nz
+    if dwi.dim() != 2 or dwi.shape[1] != nvox or dwi.shape[0] != plan.nvol or mask.numel() != nvox:
+        raise ValueError("dwi must be [%d, %d] and mask [%d] for shape %s" % (plan.nvol, nvox, nvox, tuple(shape)))
     dev = dwi.device
-    out = dict(fodf=torch.empty((plan.nvert, nvox), dtype=torch.float32, device=dev),
-               fgm=torch.empty(nvox, dtype=torch.float32, device=dev), fcsf=torch.empty(nvox, dtype=torch.float32, device=dev),
-               gfa=torch.empty(nvox, dtype=torch.float32, device=dev), var=torch.empty(nvox, dtype=torch.float32, device=dev),
-               peak=[torch.empty((3, nvox), dtype=torch.float32, device=dev) for _ in range(5)])
+    if out is None:
+        out = dict(fodf=torch.empty((plan.nvert, nvox), dtype=torch.float32, device=dev),
+                   fgm=torch.empty(nvox, dtype=torch.float32, device=dev), fcsf=torch.empty(nvox, dtype=torch.float32, device=dev),
+                   gfa=torch.empty(nvox, dtype=torch.float32, device=dev), var=torch.empty(nvox, dtype=torch.float32, device=dev),
+                   peak=[torch.empty((3, nvox), dtype=torch.float32, device=dev) for _ in range(5)])
+    else:
+        want = dict(fodf=(plan.nvert, nvox), fgm=(nvox,), fcsf=(nvox,), gfa=(nvox,), var=(nvox,))
+        for k, shp in want.items():
+            if tuple(_chk_dev(out[k], torch.float32, "out['%s']" % k).shape) != shp:
+                raise ValueError("out['%s'] must have shape %s" % (k, shp))
+        if len(out["peak"]) != 5 or any(tuple(_chk_dev(t, torch.float32, "out['peak']").shape) != (3, nvox) for t in out["peak"]):
+            raise ValueError("out['peak'] must be five [3, %d] tensors" % nvox)
     ro = _lib.RumbaOut(out["fodf"].data_ptr(), out["fgm"].data_ptr(), out["fcsf"].data_ptr(), out["gfa"].data_ptr(),
                        out["var"].data_ptr(), (C.c_void_p * 5)(*[t.data_ptr() for t in out["peak"]]))
     sm, ss = C.c_float(0), C.c_float(0)

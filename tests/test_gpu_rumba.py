@@ -76,3 +76,481 @@ def test_rumba_single_fibre_recovery(fj):
     nearest = np.abs(np.einsum("xyzc,vc->xyzv", ax, H)).max(3)       # best any vertex can do
     assert (cosang > nearest - 0.02).all()
     assert (r.fgm.vol[..., 0] + r.fcsf.vol[..., 0] < 0.2).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The HIP path against the float64 restatement (tests/rumba_ref.py).  Tolerance rule, per case and output field:
+#     |gpu - ref64| <= C max|ref32 - ref64| + floor,   C = 4,   floor = 1e-6 max|ref64|
+# ref32 is the same restatement in float32: the allowance is what a legitimate float32 implementation of the case deviates.  The
+# kernel differs from it in accumulation order and in its rcp / rsq factors (each within 1 ulp, rumba.hip:108-111), and its split
+# contraction is closer to float64 than an f32 fma chain.  A differing peak vertex must be a tie or a marginal peak test in
+# ref64's fODF within the fODF's tolerance (no allowance by count).
+# ------------------------------------------------------------------------------------------------------------------------------
+import itertools                                                                        # noqa: E402
+
+import rumba_ref as R                                                                   # noqa: E402
+
+C_TOL = 4.0
+FIELDS = ("fodf", "fgm", "fcsf", "gfa", "var")
+SPHERES = ("sphere_724", "sphere_642", "sphere_362")
+
+
+def _refs(dwi, mask, bval, K, verts, niter, **kw):
+    return (R.rumba_ref(dwi, mask, bval, K, verts, niter, dtype=np.float64, **kw),
+            R.rumba_ref(dwi, mask, bval, K, verts, niter, dtype=np.float32, **kw))
+
+
+def _host(fj, dwi, mask, bval, bvec, sph, niter, **kw):
+    r = fj.rumba_rec(fj.MRI(dwi, bval, bvec), fj.MRI(mask), sph, niter=niter, **kw)
+    return dict(fodf=r.fodf.vol, fgm=r.fgm.vol[..., 0], fcsf=r.fcsf.vol[..., 0], gfa=r.gfa.vol[..., 0], var=r.var.vol[..., 0],
+                peak=[p.vol for p in r.peak], snr_mean=r.snr_mean, snr_std=r.snr_std)
+
+
+def _from_device(d, shape):
+    """rumba_rec_device's planar tensors -> the host layout ([nx,ny,nz(,k)], Fortran voxel order)"""
+    f = lambda t: t.cpu().numpy().reshape(-1, *shape[::-1]).transpose(3, 2, 1, 0).squeeze(-1) if t.dim() == 1 else \
+        t.cpu().numpy().reshape(-1, *shape[::-1]).transpose(3, 2, 1, 0)                 # noqa: E731
+    out = {k: f(d[k]) for k in FIELDS}
+    out["fodf"] = f(d["fodf"])
+    out["peak"] = [f(p) for p in d["peak"]]
+    out["snr_mean"], out["snr_std"] = d["snr_mean"], d["snr_std"]
+    return out
+
+
+def _allow(r64, r32, k):
+    """C max|ref32 - ref64| + floor.  The yardstick is a maximum over the mask's voxels; a mask of a few voxels gives a few draws of
+    the float32 rounding, which can all land near 0 (measured: one voxel at niter = 1, fcsf, 1e-10 of the maximum while the kernel
+    is 1.3e-6 off).  Below 64 voxels the floor is therefore C x 1.5e-6 of the maximum: 1.5e-6 is ref32's deviation over the full
+    70 x 6 x 5 volume of the same case."""
+    a64, a32 = np.asarray(r64[k], np.float64), np.asarray(r32[k], np.float64)
+    floor = 1e-6 if r64["ind"].size >= 64 else C_TOL * 1.5e-6
+    return C_TOL * np.abs(a32 - a64).max() + floor * np.abs(a64).max()
+
+
+def _peak_vertices(peak, H):
+    """vertex index of each peak vector (-1: none) [nvox, 5]"""
+    out = []
+    for p in peak:
+        p = np.asarray(p, np.float64).reshape(-1, 3, order="F") if p.ndim == 4 else p
+        n = np.linalg.norm(p, axis=1)
+        v = np.argmax(np.abs((p / np.maximum(n, 1e-30)[:, None]) @ H.T), axis=1)
+        out.append(np.where(n > 0, v, -1))
+    return np.stack(out, 1)
+
+
+def _ranks_match(col, want, got, slack):
+    for w, g in zip(want, got):
+        if w != g and abs((col[w] if w >= 0 else 0.0) - (col[g] if g >= 0 else 0.0)) > slack:
+            return False
+    return True
+
+
+def check_rumba(got, r64, r32, mask, sph, label=""):
+    """the tolerance rule above on every field of one case; got in the host layout"""
+    m = np.asarray(mask).reshape(-1, order="F") > 0
+    nv = sph.nvert
+    for k in FIELDS:
+        g = np.asarray(got[k], np.float64)
+        err = np.abs(g - np.asarray(r64[k], np.float64))
+        allow = _allow(r64, r32, k)
+        assert err.max() <= allow, "%s %s: max |gpu - ref64| %.3g > %.3g (= %g x max|ref32 - ref64| + floor)" % (
+            label, k, err.max(), allow, C_TOL)
+        flat = g.reshape(-1, nv, order="F") if k == "fodf" else g.reshape(-1, order="F")
+        assert (flat[~m] == 0).all(), "%s %s: non-zero outside the mask" % (label, k)
+    # snr_mean / snr_std are statistics of snr = 1 / sqrt(var) over the whole mask: a single number whose ref32 deviation can be
+    # small by chance, and which moves with every in-tolerance difference of the var field.  So (a) they are the float64 statistics
+    # of the returned var (snr_vec in float32, as the kernel forms it), and (b) they meet ref64 by the rule above widened by exactly
+    # what the returned var moves them: |mean(d)| and the (n - 1)-norm of d = snr(gpu var) - snr(ref64 var) (a std's triangle inequality)
+    if r64["snr_mean"] != 0:
+        vg = np.asarray(got["var"], np.float32).reshape(-1, order="F")[m]
+        sg = (np.float32(1) / np.sqrt(vg)).astype(np.float64)
+        s64 = 1.0 / np.sqrt(np.asarray(r64["var"], np.float64).reshape(-1, order="F")[m])
+        d = sg - s64
+        n = sg.size
+        stats = dict(snr_mean=(sg.mean(), abs(d.mean())),
+                     snr_std=(sg.std(ddof=1) if n > 1 else 0.0, np.sqrt((d * d).sum() / (n - 1)) if n > 1 else 0.0))
+    else:
+        stats = dict(snr_mean=(0.0, 0.0), snr_std=(0.0, 0.0))
+    for k in ("snr_mean", "snr_std"):
+        own, moved = stats[k]
+        assert abs(got[k] - own) <= 1e-6 * abs(own), "%s %s: %r, but the returned var gives %r" % (label, k, got[k], own)
+        allow = C_TOL * abs(r32[k] - r64[k]) + 1e-6 * abs(r64[k]) + moved
+        assert abs(got[k] - r64[k]) <= allow, "%s %s: %r vs ref64 %r (allowed %.3g)" % (label, k, got[k], r64[k], allow)
+    # peaks: vertices per rank, then amplitudes where the vertex lists agree
+    H = np.asarray(sph.vertices, np.float64)[:nv]
+    ind = r64["ind"]
+    gv = _peak_vertices(got["peak"], H)[ind]
+    rv, r32v = r64["peak_vertex"], r32["peak_vertex"]
+    slack = _allow(r64, r32, "fodf")
+    differ = np.flatnonzero((gv != rv).any(1))
+    for i in differ:
+        col, mg = r64["odf"][i].astype(np.float64), r64["peak_margin"][i].astype(np.float64)
+        if _ranks_match(col, rv[i], gv[i], slack):
+            continue
+        certain = [v for v in range(nv) if mg[v] > slack]
+        marginal = [v for v in range(nv) if abs(mg[v]) <= slack]
+        msg = "%s voxel %d: peaks %s (ref64) vs %s" % (label, ind[i], list(rv[i]), list(gv[i]))
+        assert len(marginal) <= 10, msg + " with %d marginal vertices" % len(marginal)
+        ok = False
+        for n in range(len(marginal) + 1):
+            for sub in itertools.combinations(marginal, n):
+                cand = sorted(certain + list(sub), key=lambda v: (-col[v], v))[:5]
+                if _ranks_match(col, cand + [-1] * (5 - len(cand)), gv[i], slack):
+                    ok = True
+                    break
+            if ok:
+                break
+        assert ok, msg + ": neither a tie nor a marginal peak test within %.3g" % slack
+    same = (gv == rv).all(1)
+    cal = (r32v == rv).all(1)                                                        # the yardstick: voxels where ref32 picks ref64's vertices
+    for k in range(5):
+        g = np.asarray(got["peak"][k], np.float64).reshape(-1, 3, order="F")[ind]
+        a64 = np.asarray(r64["peak"][k], np.float64).reshape(-1, 3, order="F")[ind]
+        a32 = np.asarray(r32["peak"][k], np.float64).reshape(-1, 3, order="F")[ind]
+        dev = np.abs(a32 - a64)[cal].max() if cal.any() else 0.0
+        allow = C_TOL * dev + 1e-6 * max(np.abs(a64).max(), 1e-30)
+        err = np.abs(g - a64)[same]
+        assert err.size == 0 or err.max() <= allow, "%s peak %d: %.3g > %.3g" % (label, k, err.max(), allow)
+    return len(differ)
+
+
+@pytest.fixture(scope="module")
+def scheme61():
+    from fibers_jl_amd import phantom
+    return phantom.scheme_gqi(3, 30, (1000.0, 2500.0), 3)
+
+
+@pytest.fixture(scope="module")
+def plans61(fj, scheme61):
+    bval, bvec = scheme61
+    ps = {s: fj.RumbaPlan(bval, bvec, getattr(fj, s)) for s in SPHERES}
+    yield ps
+    for p in ps.values():
+        p.close()
+
+
+@pytest.fixture(scope="module")
+def wide(scheme61):
+    """70 x 6 x 5: x-runs of 70 voxels cross the 64-lane waves and the 256-column blocks; six masks"""
+    from fibers_jl_amd import phantom
+    bval, bvec = scheme61
+    shape = (70, 6, 5)
+    dwi, _, _ = phantom.make_volume(shape, bval, bvec, 11, noise_frac=0.03, crossing=True)
+    rng = np.random.default_rng(12)
+    x, y, z = np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")
+    order = rng.permutation(int(np.prod(shape)))
+    def first(n):                                                                    # noqa: E306
+        m = np.zeros(int(np.prod(shape)), np.uint8)
+        m[order[:n]] = 1
+        return np.asfortranarray(m.reshape(shape, order="F"))
+    one = np.zeros(shape, np.uint8); one[33, 2, 3] = 1
+    masks = dict(full=np.ones(shape, np.uint8), random85=(rng.random(shape) < 0.85).astype(np.uint8),
+                 checker=((x + y + z) % 2 == 0).astype(np.uint8), one=one, n256=first(256), n257=first(257))
+    return dwi, masks
+
+
+@pytest.mark.parametrize("sphere", SPHERES)
+def test_rumba_early_iterations_vs_float64(fj, scheme61, plans61, wide, sphere):
+    """niter 1-3 x TV on / off x ipat 1 / 2 on the 70 x 6 x 5 volume, the six masks taken in turn (niter = 1 sees only the mask
+    boundary in the TV term, the initial fODF being uniform; niter >= 2 sees real gradients)"""
+    bval, bvec = scheme61
+    dwi, masks = wide
+    sph = getattr(fj, sphere)
+    K = plans61[sphere].kernel()
+    names = list(masks)
+    for i, (niter, use_tv, ipat) in enumerate(itertools.product((1, 2, 3), (True, False), (1, 2))):
+        mname = names[(i + SPHERES.index(sphere)) % len(names)]
+        mask = masks[mname]
+        kw = dict(use_tv=use_tv, ipat_factor=ipat)
+        r64, r32 = _refs(dwi, mask, bval, K, sph.vertices, niter, **kw)
+        got = _host(fj, dwi, mask, bval, bvec, sph, niter, **kw)
+        check_rumba(got, r64, r32, mask, sph, "%s niter=%d tv=%s ipat=%d mask=%s" % (sphere, niter, use_tv, ipat, mname))
+
+
+def test_rumba_long_run_crossing_vs_float64(fj):
+    """40 iterations with TV on a crossing phantom"""
+    from fibers_jl_amd import phantom
+    bval, bvec = phantom.scheme_gqi(3, 30, (1000.0, 2500.0), 5)
+    shape = (12, 10, 8)
+    dwi, _, _ = phantom.make_volume(shape, bval, bvec, 5, noise_frac=0.03, crossing=True)
+    mask = (np.random.default_rng(4).random(shape) < 0.9).astype(np.uint8)
+    sph = fj.sphere_724
+    plan = fj.RumbaPlan(bval, bvec, sph)
+    K = plan.kernel()
+    plan.close()
+    r64, r32 = _refs(dwi, mask, bval, K, sph.vertices, 40)
+    check_rumba(_host(fj, dwi, mask, bval, bvec, sph, 40), r64, r32, mask, sph, "niter=40")
+
+
+@pytest.fixture(scope="module")
+def sharp_case(fj):
+    """noise-free single fibres along the half-sphere vertices farthest from vertices 1-16, 80 iterations: the fODF's first
+    compartments (the contraction's first k-stage, KT = 16) fall far below each column's maximum"""
+    from fibers_jl_amd import phantom
+    bval, bvec = phantom.scheme_gqi(3, 30, (1000.0, 2500.0), 5)
+    sph = fj.sphere_724
+    H = sph.vertices[:sph.nvert]
+    far = np.argsort(np.abs(H @ H[:16].T).max(1))[:40]
+    shape = (10, 8, 6)
+    ax = H[far[np.random.default_rng(1).integers(0, 40, shape)]]
+    dwi = phantom.signal(bval, bvec, [ax], [np.ones(shape)], 1000.0, floor=1.0)
+    mask = np.ones(shape, np.uint8)
+    plan = fj.RumbaPlan(bval, bvec, sph)
+    K = plan.kernel()
+    plan.close()
+    r64, r32 = _refs(dwi, mask, bval, K, sph.vertices, 80)
+    return dwi, mask, bval, bvec, sph, r64, r32
+
+
+@pytest.mark.parametrize("fmt", ["fp16x2", "bf16x3", "f32"])
+def test_rumba_operand_formats_vs_float64(fj, sharp_case, fmt, monkeypatch):
+    """every operand format of the three contractions; in ref64's final fODF the first 16 compartments of the columns hold less than
+    2^-9 of the column's maximum, which sends the fp16x2 path into its per-voxel exponent-lowering branch (odf_gemm3.inc)"""
+    from fibers_jl_amd import _lib
+    monkeypatch.delenv("FIBERS_ODF_FORMAT", raising=False)
+    if fmt != "fp16x2":
+        monkeypatch.setenv("FIBERS_ODF_FORMAT", fmt)
+    assert _lib.lib().fib_odf_default_format() == fj.gqi.ODF_FORMATS[fmt]
+    dwi, mask, bval, bvec, sph, r64, r32 = sharp_case
+    f = r64["fodf_mat"]
+    low = f[:16].max(0) < 2.0 ** -9 * f.max(0)
+    assert low.mean() > 0.5, "only %d of %d columns take the lowering branch" % (low.sum(), low.size)
+    check_rumba(_host(fj, dwi, mask, bval, bvec, sph, 80), r64, r32, mask, sph, fmt)     # (the host tier plans under fmt)
+
+
+def _tile_rule(M, split):
+    """finish_plan's (MB, NX) (odf.hip): minimise ntile (64 MB + 4 NX) over MB = 10|11 .. 5, NX in {0, 1} (NX = 1 only for MB <= 10)"""
+    best = None
+    for mb in range(10 if split else 11, 4, -1):
+        for nx in (0, 1):
+            if nx and mb > 10:
+                continue
+            nt = -(-M // (mb * 32 + nx))
+            cost = nt * (64 * mb + 4 * nx)
+            if best is None or cost < best[0]:
+                best = (cost, mb, nx)
+    return best[1:]
+
+
+@pytest.mark.parametrize("ndw,nb0,sphere", [(80, 1, "sphere_642"), (96, 2, "sphere_362")])
+def test_rumba_nx1_tiles_vs_float64(fj, ndw, nb0, sphere):
+    """ndir = 161 and 193 signal rows: the K-plan (M = ndir) gets an MB x 32 + 1 row tile with one VALU row -- (5, 1) for 161
+    rows (one tile of 161, cost 324 against 384 for (6, 0)) and (6, 1) for 193 (388 against 448 for (7, 0))"""
+    from fibers_jl_amd import phantom
+    bval, bvec = phantom.scheme_gqi(nb0, ndw, (1000.0, 2500.0), 7)
+    ndir = 2 * ndw + 1
+    assert _tile_rule(ndir, True) == {161: (5, 1), 193: (6, 1)}[ndir]
+    sph = getattr(fj, sphere)
+    shape = (20, 6, 5)
+    dwi, _, _ = phantom.make_volume(shape, bval, bvec, 9, noise_frac=0.03, crossing=True)
+    mask = (np.random.default_rng(9).random(shape) < 0.85).astype(np.uint8)
+    plan = fj.RumbaPlan(bval, bvec, sph)
+    K = plan.kernel()
+    plan.close()
+    assert K.shape == (ndir, sph.nvert + 2)
+    for niter, use_tv in ((3, True), (12, False)):
+        r64, r32 = _refs(dwi, mask, bval, K, sph.vertices, niter, use_tv=use_tv)
+        check_rumba(_host(fj, dwi, mask, bval, bvec, sph, niter, use_tv=use_tv), r64, r32, mask, sph, "ndir=%d niter=%d" % (ndir, niter))
+
+
+def test_rumba_sos_grappa_vs_float64(fj, scheme61, plans61, wide):
+    """coil_combine = SoS-GRAPPA sets n_order = ncoils (the Bessel ratio's order and the sigma^2 normaliser, rusd.jl:429-435); with
+    one coil it is SMF-SENSE to the bit"""
+    bval, bvec = scheme61
+    dwi, masks = wide
+    sph = fj.sphere_642
+    K = plans61["sphere_642"].kernel()
+    mask = masks["random85"]
+    for ncoils, niter in ((1, 3), (4, 3), (8, 3), (8, 10)):
+        kw = dict(ncoils=ncoils, coil_combine="SoS-GRAPPA")
+        r64, r32 = _refs(dwi, mask, bval, K, sph.vertices, niter, **kw)
+        got = _host(fj, dwi, mask, bval, bvec, sph, niter, **kw)
+        check_rumba(got, r64, r32, mask, sph, "ncoils=%d niter=%d" % (ncoils, niter))
+    a = _host(fj, dwi, mask, bval, bvec, sph, 5, ncoils=1, coil_combine="SoS-GRAPPA")
+    b = _host(fj, dwi, mask, bval, bvec, sph, 5, ncoils=7, coil_combine="SMF-SENSE")       # ncoils has no effect under SMF-SENSE
+    for k in FIELDS:
+        assert np.array_equal(a[k].view(np.int32), b[k].view(np.int32)), k
+    assert all(np.array_equal(p.view(np.int32), q.view(np.int32)) for p, q in zip(a["peak"], b["peak"]))
+    assert (a["snr_mean"], a["snr_std"]) == (b["snr_mean"], b["snr_std"])
+
+
+def _nan_out(plan, nvox, dev):
+    import torch
+    nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)       # noqa: E731
+    return dict(fodf=nan(plan.nvert, nvox), fgm=nan(nvox), fcsf=nan(nvox), gfa=nan(nvox), var=nan(nvox),
+                peak=[nan(3, nvox) for _ in range(5)])
+
+
+def _dev_equal(a, b, fields=FIELDS):
+    import torch
+    for k in fields:
+        assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), k
+    for p, q in zip(a["peak"], b["peak"]):
+        assert torch.equal(p.view(torch.int32), q.view(torch.int32)), "peak"
+
+
+def test_rumba_device_tier_matches_host_bitwise(fj, scheme61, plans61, wide):
+    """rumba_rec_device on a stream that is not the current one, into NaN-filled outputs, is the host rumba_rec to the bit (the host
+    given its DWI in Fortran and in C memory order); outside the mask every output comes back 0"""
+    import torch
+    bval, bvec = scheme61
+    dwi, masks = wide
+    sph, plan = fj.sphere_724, plans61["sphere_724"]
+    shape = dwi.shape[:3]
+    nvox = int(np.prod(shape))
+    mask = masks["random85"]
+    m = torch.from_numpy(mask.reshape(-1, order="F").copy()).cuda()
+    d = torch.from_numpy(np.ascontiguousarray(dwi.reshape(nvox, -1, order="F").T)).cuda()
+    for niter, use_tv, ipat in ((4, True, 2), (4, False, 1), (3, True, 1)):
+        kw = dict(use_tv=use_tv, ipat_factor=ipat)
+        s = torch.cuda.Stream()
+        out = _nan_out(plan, nvox, d.device)
+        torch.cuda.synchronize()
+        r = fj.rumba_rec_device(plan, d, m, shape, niter=niter, stream=s, out=out, **kw)
+        s.synchronize()
+        assert r["fodf"] is out["fodf"]
+        got = _from_device(r, shape)
+        for order in ("F", "C"):
+            host = _host(fj, np.asarray(dwi, order=order), mask, bval, bvec, sph, niter, **kw)
+            for k in FIELDS:
+                assert np.array_equal(got[k].view(np.int32), host[k].view(np.int32)), "%s %s" % (order, k)
+            assert all(np.array_equal(p.view(np.int32), q.view(np.int32)) for p, q in zip(got["peak"], host["peak"]))
+            assert (got["snr_mean"], got["snr_std"]) == (host["snr_mean"], host["snr_std"])
+        out_m = torch.from_numpy(mask.reshape(-1, order="F") == 0).cuda()
+        for t in [r[k] for k in FIELDS] + r["peak"]:
+            assert (t.reshape(-1, nvox)[:, out_m] == 0).all()
+
+
+def test_rumba_plan_reuse_bitwise(fj, scheme61, wide):
+    """one plan: large -> small -> large calls of different shapes and masks, then niter = 0 and an empty mask, each equal to the bit
+    to a fresh plan's result (work buffers grow and are kept; the contraction's column list is rebuilt on a call's first iteration)"""
+    import torch
+    from fibers_jl_amd import phantom
+    bval, bvec = scheme61
+    dwi_w, masks = wide
+    sph = fj.sphere_362
+    small_shape = (9, 7, 3)
+    dwi_s, _, _ = phantom.make_volume(small_shape, bval, bvec, 21, noise_frac=0.03, crossing=True)
+    mask_s = (np.random.default_rng(21).random(small_shape) < 0.7).astype(np.uint8)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a.reshape(-1, a.shape[3], order="F").T)).cuda()   # noqa: E731
+    md = lambda a: torch.from_numpy(a.reshape(-1, order="F").copy()).cuda()                               # noqa: E731
+    calls = [(dwi_w, masks["full"], 4, True, 2), (dwi_s, mask_s, 4, True, 2), (dwi_w, masks["checker"], 3, True, 2),
+             (dwi_s, mask_s, 3, False, 1), (dwi_w, masks["random85"], 0, True, 1), (dwi_w, np.zeros_like(masks["full"]), 3, True, 2),
+             (dwi_w, masks["n257"], 3, True, 2)]
+    shared = fj.RumbaPlan(bval, bvec, sph)
+    for dwi, mask, niter, use_tv, ipat in calls:
+        shape = dwi.shape[:3]
+        kw = dict(niter=niter, use_tv=use_tv, ipat_factor=ipat)
+        a = fj.rumba_rec_device(shared, dev(dwi), md(mask), shape, out=_nan_out(shared, int(np.prod(shape)), "cuda"), **kw)
+        fresh = fj.RumbaPlan(bval, bvec, sph)
+        b = fj.rumba_rec_device(fresh, dev(dwi), md(mask), shape, **kw)
+        torch.cuda.synchronize()
+        fresh.close()
+        _dev_equal(a, b)
+        assert (a["snr_mean"], a["snr_std"]) == (b["snr_mean"], b["snr_std"])
+        if not mask.any():                                                           # empty mask: zeros, snr 0, FIB_OK
+            assert all(float(a[k].abs().max()) == 0 for k in FIELDS) and all(float(p.abs().max()) == 0 for p in a["peak"])
+            assert a["snr_mean"] == 0 and a["snr_std"] == 0
+        if niter == 0:                                                               # uniform fODF, var = 1/225, no peaks
+            mm = md(mask).bool()
+            assert torch.allclose(a["fodf"][:, mm], torch.full_like(a["fodf"][:, mm], 1.0 / sph.nvert), rtol=1e-5, atol=0)
+            assert torch.allclose(a["var"][mm], torch.full_like(a["var"][mm], 1.0 / 225.0), rtol=1e-6, atol=0)
+            assert all(float(p.abs().max()) == 0 for p in a["peak"]) and a["snr_mean"] == 0
+    shared.close()
+
+
+@pytest.mark.parametrize("shape", [(1, 9, 7), (9, 1, 7), (9, 7, 1), (1, 1, 5), (2, 9, 7)])
+def test_rumba_singleton_axes_vs_float64(fj, scheme61, plans61, shape):
+    """an axis of length 1 (the reference throws BoundsError in sd_div!; here the axis adds nothing to the divergence)
+    and one of length 2, with TV"""
+    from fibers_jl_amd import phantom
+    bval, bvec = scheme61
+    dwi, _, _ = phantom.make_volume(shape, bval, bvec, 31, noise_frac=0.03, crossing=True)
+    mask = (np.random.default_rng(31).random(shape) < 0.9).astype(np.uint8)
+    sph = fj.sphere_642
+    K = plans61["sphere_642"].kernel()
+    for niter, ipat in ((3, 1), (5, 2)):
+        r64, r32 = _refs(dwi, mask, bval, K, sph.vertices, niter, ipat_factor=ipat)
+        check_rumba(_host(fj, dwi, mask, bval, bvec, sph, niter, ipat_factor=ipat), r64, r32, mask, sph, "%s niter=%d" % (shape, niter))
+
+
+@pytest.fixture(scope="module")
+def big(fj):
+    """96 x 96 x 48 x 64 frames (442 368 columns), built on the GPU"""
+    import torch
+    from fibers_jl_amd import phantom
+    bval, bvec = phantom.scheme_gqi(4, 30, (1000.0, 2500.0), 13)
+    shape = (96, 96, 48)
+    d, _ = phantom.make_dwi_torch(shape, bval, bvec, seed=13, device=torch.device("cuda"))
+    mask = torch.ones(int(np.prod(shape)), dtype=torch.uint8, device="cuda")
+    mask[:5000] = 0                                                                  # (a partly empty first slab)
+    return bval, bvec, shape, d, mask
+
+
+def test_rumba_scale_columns_are_independent_without_tv(fj, big):
+    """without TV every column is independent (the fp16x2 scaling depends on the voxel's own samples only): 2000 voxels of the full
+    run, packed into a 2000 x 1 x 1 volume and run again, give the same bits, and that sample meets ref64"""
+    import torch
+    bval, bvec, shape, d, mask = big
+    sph = fj.sphere_724
+    plan = fj.RumbaPlan(bval, bvec, sph)
+    niter = 6
+    full = fj.rumba_rec_device(plan, d, mask, shape, niter=niter, use_tv=False)
+    live = torch.nonzero(mask).squeeze(1).cpu().numpy()
+    pick = np.sort(np.random.default_rng(5).choice(live, 2000, replace=False))
+    pi = torch.from_numpy(pick).cuda()
+    ds = d[:, pi].contiguous()
+    sub = fj.rumba_rec_device(plan, ds, torch.ones(2000, dtype=torch.uint8, device="cuda"), (2000, 1, 1), niter=niter, use_tv=False)
+    torch.cuda.synchronize()
+    for k in FIELDS:
+        t = full[k]
+        assert torch.equal((t[:, pi] if t.dim() == 2 else t[pi]).view(torch.int32), sub[k].view(torch.int32)), k
+    for p, q in zip(full["peak"], sub["peak"]):
+        assert torch.equal(p[:, pi].view(torch.int32), q.view(torch.int32))
+    K = plan.kernel()
+    plan.close()
+    dwi = np.asfortranarray(ds.cpu().numpy().T.reshape(2000, 1, 1, -1))
+    m1 = np.ones((2000, 1, 1), np.uint8)
+    r64, r32 = _refs(dwi, m1, bval, K, sph.vertices, niter, use_tv=False)
+    check_rumba(_from_device(sub, (2000, 1, 1)), r64, r32, m1, sph, "2000-voxel sample")
+
+
+def test_rumba_scale_tv_crop_and_snr(fj, big):
+    """with TV and ipat = 2 an iteration reads neighbours at most one voxel away per axis: after n iterations a 40^3 crop run on its
+    own equals the full run to the bit more than n voxels from the crop's faces, and the crop meets ref64.  ipat = 1: snr_mean /
+    snr_std are the float64 statistics of 1 / sqrt(var) over the mask (no bitwise case there: lambda rests on a double atomic sum)"""
+    import torch
+    bval, bvec, shape, d, mask = big
+    sph = fj.sphere_362
+    plan = fj.RumbaPlan(bval, bvec, sph)
+    n = 2
+    full = fj.rumba_rec_device(plan, d, mask, shape, niter=n, use_tv=True, ipat_factor=2)
+    nx, ny, nz = shape
+    x0, y0, z0, c = 30, 41, 5, 40
+    d5 = d.view(-1, nz, ny, nx)
+    crop = d5[:, z0:z0 + c, y0:y0 + c, x0:x0 + c].reshape(d.shape[0], -1).contiguous()
+    mc = mask.view(nz, ny, nx)[z0:z0 + c, y0:y0 + c, x0:x0 + c].reshape(-1).contiguous()
+    assert bool(mc.all())
+    sub = fj.rumba_rec_device(plan, crop, mc, (c, c, c), niter=n, use_tv=True, ipat_factor=2)
+    torch.cuda.synchronize()
+    inner = slice(n + 1, c - n - 1)
+    def sel_full(t):                                                                 # noqa: E306
+        return t.view(-1, nz, ny, nx)[:, z0:z0 + c, y0:y0 + c, x0:x0 + c][:, inner, inner, inner]
+    def sel_crop(t):                                                                 # noqa: E306
+        return t.view(-1, c, c, c)[:, inner, inner, inner]
+    for k in FIELDS:
+        assert torch.equal(sel_full(full[k]).view(torch.int32), sel_crop(sub[k]).view(torch.int32)), k
+    for p, q in zip(full["peak"], sub["peak"]):
+        assert torch.equal(sel_full(p).view(torch.int32), sel_crop(q).view(torch.int32))
+    K = plan.kernel()
+    dwi = np.asfortranarray(crop.cpu().numpy().T.reshape(c, c, c, -1, order="F"))
+    mk = np.ones((c, c, c), np.uint8)
+    r64, r32 = _refs(dwi, mk, bval, K, sph.vertices, n, ipat_factor=2)
+    check_rumba(_from_device(sub, (c, c, c)), r64, r32, mk, sph, "40^3 crop")
+    del r64, r32
+    one = fj.rumba_rec_device(plan, d, mask, shape, niter=3, use_tv=True, ipat_factor=1)
+    plan.close()
+    mm = mask.bool()
+    snr = (np.float32(1) / np.sqrt(one["var"][mm].cpu().numpy())).astype(np.float64)   # snr_vec in float32, its statistics in float64
+    assert abs(one["snr_mean"] - snr.mean()) <= 1e-6 * snr.mean()
+    assert abs(one["snr_std"] - snr.std(ddof=1)) <= 1e-6 * snr.std(ddof=1)
