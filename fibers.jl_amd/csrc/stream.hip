@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 
 #include "common.h"
@@ -99,7 +100,7 @@ struct TraceArgs {
     int norm_generic;           // diagnostic build only (FIBERS_STREAM_NORM_GENERIC): normalise3's generic expansion for every vector
     int lcm_plain;              // LCM runs: lcm_thresh >= 2^-40 (every entry of the thresholded matrices is 0 or at least that)
     int dbg;                    // diagnostic build only (FIBERS_STREAM_DBG bit mask; WRONG RESULTS, timing experiments): 1 = no gather after the seed's, 2 = no point stores
-    // FUSED (fibd_stream_run): the block that traced 256 lines also packs them -- a decoupled look-back over the blocks' kept-line / point
+    // FUSED (fibd_stream_run): the block that traced 512 lines also packs them -- a decoupled look-back over the blocks' kept-line / point
     // totals gives it its place in the output
     unsigned long long *fstate; // [blocks] granules: status << 62 | kept lines << 36 | points (zeroed before the launch)
     int32_t *out_npts;
@@ -1039,13 +1040,13 @@ __global__ __launch_bounds__(SPC * TL) void stream_pack_tile_kernel(const PackAr
     }
 }
 
-// ---- [r5] FUSED: the block that traced 256 lines packs them (fibd_stream_run) --------------------------------------
+// ---- [r5] FUSED: the block that traced 512 lines packs them (fibd_stream_run) --------------------------------------
 // After its trace loop a block knows its kept lines and points; a decoupled look-back over the blocks' totals (one 64-bit granule per
 // block: status | kept lines | points -- the data is the flag, agent-scope atomics, no fence; blocks are dispatched in order, so every
-// block a block waits for is running or done) gives it its place in the packed output, and it then packs its own 16 scratch tiles
+// block a block waits for is running or done) gives it its place in the packed output, and it then packs its own 32 scratch tiles
 // exactly as stream_pack_tile_kernel does: the tile's kept lines are ONE contiguous output range, assembled in LDS and streamed out with
-// aligned 16-byte non-temporal stores.  No scan kernels, no pack launch; the scratch is still written and read back (256 lines x 144
-// slots x 12 B = 442 KB per block: it does not stay on chip), but blocks that pack overlap with blocks that still trace.
+// aligned 16-byte non-temporal stores.  No scan kernels, no pack launch; the scratch is still written and read back (512 lines x 144
+// slots x 12 B = 885 KB per block: it does not stay on chip), but blocks that pack overlap with blocks that still trace.
 constexpr unsigned long long FG_PTS_MASK = (1ull << 36) - 1ull, FG_VAL_MASK = (1ull << 62) - 1ull;
 __device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int off) {
     return ((unsigned long long)(unsigned)__shfl_up((int)(v >> 32), off) << 32) | (unsigned)__shfl_up((int)(unsigned)v, off);
@@ -1061,7 +1062,7 @@ __device__ void fused_pack_block(const TraceArgs &a, int64_t b, int64_t li, bool
     __shared__ int64_t f_p0[FUSED_BLOCK];
     constexpr int FB = FUSED_BLOCK, FW = FB / 64;
     __shared__ unsigned long long f_wsum[FW], f_base;
-    constexpr int FT = FUSED_TILE, FSL = FB / FT;                               // lines per tile; slots a pass of the 256 threads covers
+    constexpr int FT = FUSED_TILE, FSL = FB / FT;                               // lines per tile; slots a pass of the 512 threads covers
     __shared__ int t_nf[FT], t_nb[FT], t_bs[FT], t_o[FT], t_cnt[4];
     __shared__ int64_t t_g0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1207,8 +1208,7 @@ __global__ __launch_bounds__(256) void copy_i32_kernel(const int32_t *src, int32
 }  // namespace
 
 // Caller-owned, grow-only scratch arena of the tracer (fib_stream_params::ws): avoids a multi-GB hipMalloc/hipFree per job.
-// One job at a time uses it; the job that releases it records an event on its stream and the next user waits for that
-// event on its own stream, so a pack kernel still reading the arena is never overtaken.
+// A job holds it through a ScratchLease (below), which is the only code that takes, grows and gives back the arena.
 struct fib_stream_ws {
     int device = 0;
     std::mutex mu;
@@ -1241,17 +1241,99 @@ extern "C" void fibd_stream_ws_destroy(fib_stream_ws *ws) try {
     delete ws;
 } FIB_API_CATCH_VOID
 
+namespace {
+// The scratch of nlines lines of up to len_max points: ONE block of device memory, each region rounded up to 256 bytes -- the point
+// rows (TraceArgs::scratch), npts and nfwd [nlines] int32, the scan's exclusive prefixes [nlines] Pair (the fused kernel's look-back
+// granules instead), the scan blocks' totals [nblocks] Pair and the call's totals (one Pair).
+struct ScratchLayout {
+    struct Regions { float *points; int32_t *npts, *nfwd; Pair *excl, *block_tot, *total; };
+    int64_t nlines = 0;
+    int stride = 0, nslots = 0, nblocks = 0;
+    size_t off_npts = 0, off_nfwd = 0, off_excl = 0, off_btot = 0, off_total = 0, bytes = 0;   // byte offsets (the points at 0); the size
+    ScratchLayout() = default;
+    ScratchLayout(int64_t nl, int len_max)
+        : nlines(nl), stride(len_max + 2),
+          nslots((len_max + 4 + 3) & ~3),   // trips of a line's loop: <= len_max + 1 points + two failed steps; whole groups of four (the tracer stores four slots together)
+          nblocks((int)fib::cdiv(nl, SCAN_B)) {
+        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        off_npts = up((size_t)fib::cdiv(nl, SCR_ROW) * SCR_ROW * nslots * 3 * sizeof(float));
+        off_nfwd = off_npts + up((size_t)nl * sizeof(int32_t));
+        off_excl = off_nfwd + up((size_t)nl * sizeof(int32_t));
+        off_btot = off_excl + up((size_t)nl * sizeof(Pair));
+        off_total = off_btot + up((size_t)nblocks * sizeof(Pair));
+        bytes = off_total + up(sizeof(Pair));
+    }
+    Regions at(void *base) const {
+        char *b = static_cast<char *>(base);
+        return {reinterpret_cast<float *>(b), reinterpret_cast<int32_t *>(b + off_npts), reinterpret_cast<int32_t *>(b + off_nfwd),
+                reinterpret_cast<Pair *>(b + off_excl), reinterpret_cast<Pair *>(b + off_btot), reinterpret_cast<Pair *>(b + off_total)};
+    }
+};
+
+// The scratch a job holds (include/fibers_hip.h): the caller's arena when it is free and on the job's device, else device memory of
+// the job's own.  The arena changes hands in stream order, so a pack kernel still reading it is never overtaken: release() -- also
+// when the lease ends -- records an event on `last`, the stream of the holder's latest launch, and acquire() makes the next holder's
+// stream wait for it (the host waits instead when that wait cannot be enqueued, and before the arena grows).  The job's own memory is
+// freed once `last` is done.
+struct ScratchLease {
+    fib_stream_ws *ws = nullptr;    // the arena held, or NULL: p is the job's own
+    void *p = nullptr;
+    hipStream_t last = nullptr;
+    ScratchLease() = default;
+    ScratchLease(const ScratchLease &) = delete;
+    ScratchLease &operator=(const ScratchLease &) = delete;
+    ~ScratchLease() { release(); }
+
+    int acquire(fib_stream_ws *arena, int device, size_t bytes, hipStream_t st) {
+        last = st;
+        auto alloc = [bytes](void **q) -> int {
+            const hipError_t e = hipMalloc(q, bytes);
+            if (e == hipSuccess) return FIB_OK;
+            *q = nullptr;
+            return fib::fail(FIB_ERR_NOMEM, "cannot allocate %zu bytes of streamline scratch: %s", bytes, hipGetErrorString(e));
+        };
+        if (arena) {
+            std::lock_guard<std::mutex> lk(arena->mu);
+            if (!arena->busy && arena->device == device) {
+                if (arena->bytes < bytes) {
+                    if (arena->pending) { (void)hipEventSynchronize(arena->done); arena->pending = false; }
+                    if (arena->p) (void)hipFree(arena->p);
+                    arena->bytes = 0;
+                    const int rc = alloc(&arena->p);
+                    if (rc != FIB_OK) return rc;
+                    arena->bytes = bytes;
+                }
+                if (arena->pending) {
+                    if (hipStreamWaitEvent(st, arena->done, 0) != hipSuccess) (void)hipEventSynchronize(arena->done);
+                    arena->pending = false;
+                }
+                arena->busy = true;
+                ws = arena; p = arena->p;
+                return FIB_OK;
+            }
+        }
+        return alloc(&p);
+    }
+    void release() {
+        if (ws) {
+            std::lock_guard<std::mutex> lk(ws->mu);
+            ws->pending = hipEventRecord(ws->done, last) == hipSuccess;
+            if (!ws->pending) (void)hipStreamSynchronize(last);
+            ws->busy = false;
+        } else if (p) {
+            (void)hipStreamSynchronize(last);
+            (void)hipFree(p);
+        }
+        ws = nullptr; p = nullptr;
+    }
+};
+}  // namespace
+
 struct fib_stream_job {
     int device = 0;
-    fib_stream_ws *ws = nullptr;    // arena the scratch was taken from (NULL: own allocation)
-    hipStream_t last_stream = nullptr;   // stream of the job's latest launch (trace or pack)
-    fib_stream_params prm{};
-    int64_t nseed = 0, nlines = 0;
-    int nsub = 1, stride = 0, nslots = 0;
-    float *scratch = nullptr;
-    // carved out of the same (cached) arena as the scratch: no hipMalloc/hipFree per call
-    struct View32 { int32_t *p = nullptr; } npts, nfwd;
-    struct ViewP { Pair *p = nullptr; } excl, block_tot, total;
+    int len_min = 0;
+    ScratchLayout lay;
+    ScratchLease scratch;           // (scratch.last: the stream of the job's latest launch -- trace or pack)
     int64_t kept_lines = 0, kept_pts = 0;
     bool lcm = false;               // LCM run: the method-difference flag rides in the sign bit of x until unpacked
 };
@@ -1260,17 +1342,7 @@ extern "C" void fib_stream_job_destroy(fib_stream_job *job) try {
     if (!job) return;
     fib::DeviceGuard guard;
     (void)hipSetDevice(job->device);
-    if (job->scratch) {
-        if (job->ws) {
-            std::lock_guard<std::mutex> lk(job->ws->mu);
-            job->ws->pending = hipEventRecord(job->ws->done, job->last_stream) == hipSuccess;
-            if (!job->ws->pending) (void)hipStreamSynchronize(job->last_stream);
-            job->ws->busy = false;
-        } else {
-            (void)hipFree(job->scratch);    // (hipFree waits for the device)
-        }
-    }
-    delete job;
+    delete job;                     // (gives the scratch back)
 } FIB_API_CATCH_VOID
 
 extern "C" int fibd_stream_field(int32_t nvec, int64_t nvox, const float *const *ovec, const float *const *f,
@@ -1297,117 +1369,102 @@ namespace {
 bool field_is_wide(const fib_stream_params *prm) {
     return (int64_t)prm->nx * prm->ny * prm->nz * prm->nvec >= ((int64_t)1 << 28) || fib::ab_env("FIBERS_STREAM_WIDE") != nullptr;
 }
+
+// the checks fibd_stream_trace and fibd_stream_run share (after their NULL checks); each entry point adds those of its own modes
+int check_args(const fib_stream_params *prm, const int64_t *seeds, int64_t nseed, const float *sublist, int32_t nsub) {
+    FIB_CHECK(nseed >= 0 && (nseed == 0 || seeds), FIB_ERR_INVALID, "invalid seed list");
+    FIB_CHECK(nsub >= 1 && sublist, FIB_ERR_INVALID, "sublist must hold at least one offset (use [0,0,0] for nsub=0, stream.jl:180)");
+    FIB_CHECK(prm->nx > 0 && prm->ny > 0 && prm->nz > 0 && prm->nvec >= 1 && prm->nvec <= 8, FIB_ERR_INVALID, "invalid volume / nvec");
+    FIB_CHECK(prm->len_max >= 0 && prm->len_max < (1 << 24), FIB_ERR_INVALID, "invalid len_max");
+    FIB_CHECK(prm->interp == 0 || prm->interp == 1, FIB_ERR_INVALID, "interp must be 0 (nearest voxel, the reference) or 1 (trilinear)");
+    FIB_CHECK((int64_t)prm->nx * prm->ny * prm->nz < ((int64_t)1 << 40), FIB_ERR_UNSUPPORTED, "volumes of 2^40 voxels or more are not supported");
+    return FIB_OK;
+}
+
+// TraceArgs of a trace of every line into the regions buf (the fields of the microscopy, LCM and fused forms are their callers')
+TraceArgs trace_args(const fib_stream_params *prm, const float *field4, const int64_t *seeds, const float *sublist, int32_t nsub,
+                     const ScratchLayout &lay, const ScratchLayout::Regions &buf) {
+    TraceArgs ta{};
+    ta.field = reinterpret_cast<const float4 *>(field4); ta.seeds = seeds; ta.sublist = sublist;
+    ta.scratch = buf.points; ta.npts = buf.npts; ta.nfwd = buf.nfwd;
+    ta.line0 = 0; ta.nlines = lay.nlines;
+    ta.nx = prm->nx; ta.ny = prm->ny; ta.nz = prm->nz; ta.nvec = prm->nvec; ta.nsub = nsub;
+    ta.len_max = prm->len_max; ta.stride = lay.stride; ta.nslots = lay.nslots;
+    ta.cosang = prm->cosang_thresh; ta.step = prm->step_size; ta.smooth = prm->smooth_coeff;
+    { const char *e = fib::ab_env("FIBERS_STREAM_SCRATCH_PLAIN"); ta.scratch_plain = e ? std::atoi(e) : 0; }
+    ta.norm_generic = fib::ab_env("FIBERS_STREAM_NORM_GENERIC") != nullptr;
+    { const char *e = fib::ab_env("FIBERS_STREAM_DBG"); ta.dbg = e ? std::atoi(e) : 0; }
+    return ta;
+}
+
+// PackArgs of a pack of every kept line of the regions buf into npts / seed_index / xyz (the .trk, LCM and capacity fields are the callers')
+PackArgs pack_args(const ScratchLayout &lay, const ScratchLayout::Regions &buf, int len_min, int32_t *npts, int64_t *seed_index, float *xyz) {
+    PackArgs pa{};
+    pa.scratch = buf.points; pa.npts = buf.npts; pa.nfwd = buf.nfwd;
+    pa.excl = buf.excl; pa.block_off = buf.block_tot;
+    pa.out_npts = npts; pa.out_seed = seed_index; pa.out_xyz = xyz;
+    pa.nlines = lay.nlines; pa.line0 = 0; pa.out_line0 = 0; pa.out_pt0 = 0;
+    pa.stride = lay.stride; pa.nslots = lay.nslots; pa.len_min = len_min;
+    pa.scratch_plain = fib::ab_env("FIBERS_STREAM_PACK_PLAIN") != nullptr;
+    return pa;
+}
+
 // the one-lane-per-line tracer for (LCM, TRI); the vector count is a compile-time constant for 1, 2 and 3 vectors per voxel, wide
 // fields take the run-time count (one instantiation per mode)
 template <bool LCM, bool TRI>
-void launch_trace(const TraceArgs &ta, int nvec, bool wide, unsigned grid, hipStream_t st) {
+void launch_trace(const TraceArgs &ta, int nvec, bool wide, hipStream_t st) {
+    const unsigned grid = (unsigned)fib::cdiv(ta.nlines, 256);
     if (wide)           hipLaunchKernelGGL((stream_trace_kernel<0, LCM, TRI, true>), dim3(grid), dim3(256), 0, st, ta);
     else if (nvec == 1) hipLaunchKernelGGL((stream_trace_kernel<1, LCM, TRI>), dim3(grid), dim3(256), 0, st, ta);
     else if (nvec == 2) hipLaunchKernelGGL((stream_trace_kernel<2, LCM, TRI>), dim3(grid), dim3(256), 0, st, ta);
     else if (nvec == 3) hipLaunchKernelGGL((stream_trace_kernel<3, LCM, TRI>), dim3(grid), dim3(256), 0, st, ta);
     else                hipLaunchKernelGGL((stream_trace_kernel<0, LCM, TRI>), dim3(grid), dim3(256), 0, st, ta);
 }
-struct LcmIn { const float *lcms = nullptr; float thresh = 0.0f; int sd0 = 0, sd1 = 1; unsigned long long seed = 0; };
-int stream_trace_impl(const fib_stream_params *prm, const float *field4, const LcmIn &lin, const int64_t *seeds, int64_t nseed,
-                      const float *sublist, int32_t nsub, void *stream,
-                      fib_stream_job **job_out, int64_t *nlines_out, int64_t *npoints_out);
+
+// the scan of the traced lines: offsets of the kept lines and the totals (counts_dev != NULL: {lines, points} there too)
+void scan_lines(const ScratchLayout &lay, const ScratchLayout::Regions &buf, int len_min, int64_t *counts_dev, hipStream_t st) {
+    fib::ProfScope prof("stream_scan", st);
+    hipLaunchKernelGGL(scan_block_kernel, dim3(lay.nblocks), dim3(SCAN_T), 0, st, buf.npts, lay.nlines, len_min, buf.excl, buf.block_tot);
+    hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(SCAN_T), 0, st, buf.block_tot, lay.nblocks, buf.total, (const Pair *)nullptr, counts_dev);
 }
 
-extern "C" int fibd_stream_trace(const fib_stream_params *prm, const float *field4, const int64_t *seeds, int64_t nseed,
-                                 const float *sublist, int32_t nsub, void *stream,
-                                 fib_stream_job **job_out, int64_t *nlines_out, int64_t *npoints_out) try {
-    return stream_trace_impl(prm, field4, LcmIn{}, seeds, nseed, sublist, nsub, stream, job_out, nlines_out, npoints_out);
-} FIB_API_CATCH
+// macro-scale angle-picked tracking (nearest voxel or the trilinear option), then the scan
+void trace_and_scan(const TraceArgs &ta, const fib_stream_params *prm, bool wide, const ScratchLayout &lay, const ScratchLayout::Regions &buf,
+                    int64_t *counts_dev, hipStream_t st) {
+    {
+        fib::ProfScope prof("stream_trace", st);
+        if (prm->interp) launch_trace<false, true>(ta, prm->nvec, wide, st);
+        else launch_trace<false, false>(ta, prm->nvec, wide, st);
+    }
+    scan_lines(lay, buf, prm->len_min, counts_dev, st);
+}
 
-extern "C" int fibd_stream_trace_lcm(const fib_stream_params *prm, const float *field4, const float *lcms, float lcm_thresh,
-                                     int32_t strdim0, int32_t strdim1, uint64_t rng_seed,
-                                     const int64_t *seeds, int64_t nseed, const float *sublist, int32_t nsub, void *stream,
-                                     fib_stream_job **job_out, int64_t *nlines_out, int64_t *npoints_out) try {
-    FIB_CHECK(lcms != nullptr, FIB_ERR_INVALID, "NULL lcms volume");
-    FIB_CHECK(strdim0 >= 0 && strdim0 < 3 && strdim1 >= 0 && strdim1 < 3 && strdim0 != strdim1, FIB_ERR_INVALID, "invalid in-plane dimensions");
-    FIB_CHECK(prm && prm->search_dist == 0, FIB_ERR_UNSUPPORTED, "LCM-guided tracking is a macro-scale mode (search_dist must be 0)");
-    LcmIn lin;
-    lin.lcms = lcms; lin.thresh = lcm_thresh; lin.sd0 = strdim0; lin.sd1 = strdim1; lin.seed = rng_seed;
-    return stream_trace_impl(prm, field4, lin, seeds, nseed, sublist, nsub, stream, job_out, nlines_out, npoints_out);
-} FIB_API_CATCH
-
-namespace {
+struct LcmIn { const float *lcms = nullptr; float thresh = 0.0f; int sd0 = 0, sd1 = 1; unsigned long long seed = 0; };
 int stream_trace_impl(const fib_stream_params *prm, const float *field4, const LcmIn &lin, const int64_t *seeds, int64_t nseed,
                       const float *sublist, int32_t nsub, void *stream,
                       fib_stream_job **job_out, int64_t *nlines_out, int64_t *npoints_out) {
     FIB_CHECK(prm && field4 && job_out && nlines_out && npoints_out, FIB_ERR_INVALID, "NULL argument");
     *job_out = nullptr;
-    FIB_CHECK(nseed >= 0 && (nseed == 0 || seeds), FIB_ERR_INVALID, "invalid seed list");
-    FIB_CHECK(nsub >= 1 && sublist, FIB_ERR_INVALID, "sublist must hold at least one offset (use [0,0,0] for nsub=0, stream.jl:180)");
-    FIB_CHECK(prm->nx > 0 && prm->ny > 0 && prm->nz > 0 && prm->nvec >= 1 && prm->nvec <= 8, FIB_ERR_INVALID, "invalid volume / nvec");
-    FIB_CHECK(prm->len_max >= 0 && prm->len_max < (1 << 24), FIB_ERR_INVALID, "invalid len_max");
+    int rc = check_args(prm, seeds, nseed, sublist, nsub);
+    if (rc != FIB_OK) return rc;
     FIB_CHECK(prm->search_dist <= 60, FIB_ERR_UNSUPPORTED, "search_dist up to 60 voxels is supported (got %d)", prm->search_dist);
-    FIB_CHECK(prm->interp == 0 || prm->interp == 1, FIB_ERR_INVALID, "interp must be 0 (nearest voxel, the reference) or 1 (trilinear)");
     FIB_CHECK(prm->search_flat_axis >= 0 && prm->search_flat_axis <= 3, FIB_ERR_INVALID, "search_flat_axis must be 0 (none) or 1..3 (x, y, z)");
     FIB_CHECK(prm->interp == 0 || (prm->search_dist == 0 && !lin.lcms), FIB_ERR_UNSUPPORTED,
               "trilinear interpolation is an option of macro-scale angle-picked tracking only");
-    FIB_CHECK((int64_t)prm->nx * prm->ny * prm->nz < ((int64_t)1 << 40), FIB_ERR_UNSUPPORTED, "volumes of 2^40 voxels or more are not supported");
     const bool wide = field_is_wide(prm);
     int device = 0;
     FIB_HIP(hipGetDevice(&device));
     hipStream_t st = (hipStream_t)stream;
-    fib_stream_job *job = new (std::nothrow) fib_stream_job();
+    std::unique_ptr<fib_stream_job> job(new (std::nothrow) fib_stream_job());
     FIB_CHECK(job != nullptr, FIB_ERR_NOMEM, "out of host memory");
-    job->device = device; job->prm = *prm; job->nseed = nseed; job->nsub = nsub;
-    job->nlines = nseed * nsub; job->stride = prm->len_max + 2;
-    job->nslots = (prm->len_max + 4 + 3) & ~3;          // trips of a line's loop: <= len_max + 1 points + two failed steps; whole groups of four (the tracer stores four slots together)
-    const int64_t nl = job->nlines;
+    job->device = device; job->len_min = prm->len_min;
+    job->lay = ScratchLayout(nseed * nsub, prm->len_max);
+    const int64_t nl = job->lay.nlines;
     *nlines_out = 0; *npoints_out = 0;
-    if (nl == 0) { *job_out = job; return FIB_OK; }
-    int rc = FIB_OK;
-    auto bail = [&](int code) { fib_stream_job_destroy(job); return code; };
-    const int nblocks = (int)fib::cdiv(nl, SCAN_B);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_scratch = up((size_t)fib::cdiv(nl, SCR_ROW) * SCR_ROW * job->nslots * 3 * sizeof(float));
-    const size_t b_i32 = up((size_t)nl * sizeof(int32_t)), b_excl = up((size_t)nl * sizeof(Pair));
-    const size_t b_btot = up((size_t)nblocks * sizeof(Pair)), b_tot = 256;
-    const size_t sbytes = b_scratch + 2 * b_i32 + b_excl + b_btot + b_tot;
-    job->last_stream = st;
-    if (fib_stream_ws *ws = reinterpret_cast<fib_stream_ws *>(prm->ws)) {   // the caller's arena, when it is free and on this device
-        std::lock_guard<std::mutex> lk(ws->mu);
-        if (!ws->busy && ws->device == device) {
-            if (ws->bytes < sbytes) {
-                if (ws->pending) { (void)hipEventSynchronize(ws->done); ws->pending = false; }
-                if (ws->p) (void)hipFree(ws->p);
-                ws->p = nullptr; ws->bytes = 0;
-                if (hipMalloc(&ws->p, sbytes) == hipSuccess) ws->bytes = sbytes;
-            }
-            if (ws->p) {
-                if (ws->pending) { (void)hipStreamWaitEvent(st, ws->done, 0); ws->pending = false; }
-                job->scratch = (float *)ws->p; job->ws = ws; ws->busy = true;
-            }
-        }
-    }
-    if (!job->scratch) {
-        hipError_t e = hipMalloc((void **)&job->scratch, sbytes);
-        if (e != hipSuccess) { job->scratch = nullptr; return bail(fib::fail(FIB_ERR_NOMEM, "cannot allocate %zu bytes of streamline scratch: %s", sbytes, hipGetErrorString(e))); }
-    }
-    {
-        char *base = reinterpret_cast<char *>(job->scratch) + b_scratch;
-        job->npts.p = reinterpret_cast<int32_t *>(base); base += b_i32;
-        job->nfwd.p = reinterpret_cast<int32_t *>(base); base += b_i32;
-        job->excl.p = reinterpret_cast<Pair *>(base); base += b_excl;
-        job->block_tot.p = reinterpret_cast<Pair *>(base); base += b_btot;
-        job->total.p = reinterpret_cast<Pair *>(base);
-    }
-    (void)rc;
-
-    TraceArgs ta{};
-    ta.field = reinterpret_cast<const float4 *>(field4); ta.seeds = seeds; ta.sublist = sublist;
-    ta.scratch = job->scratch; ta.npts = job->npts.p; ta.nfwd = job->nfwd.p;
-    ta.line0 = 0; ta.nlines = nl;
-    ta.nx = prm->nx; ta.ny = prm->ny; ta.nz = prm->nz; ta.nvec = prm->nvec; ta.nsub = nsub;
-    ta.len_max = prm->len_max; ta.stride = job->stride; ta.nslots = job->nslots;
-    ta.cosang = prm->cosang_thresh; ta.step = prm->step_size; ta.smooth = prm->smooth_coeff;
-    { const char *e = fib::ab_env("FIBERS_STREAM_SCRATCH_PLAIN"); ta.scratch_plain = e ? std::atoi(e) : 0; }
-    ta.norm_generic = fib::ab_env("FIBERS_STREAM_NORM_GENERIC") != nullptr;
-    { const char *e = fib::ab_env("FIBERS_STREAM_DBG"); ta.dbg = e ? std::atoi(e) : 0; }
-    const unsigned grid = (unsigned)fib::cdiv(nl, 256);
+    if (nl == 0) { *job_out = job.release(); return FIB_OK; }
+    if ((rc = job->scratch.acquire(prm->ws, device, job->lay.bytes, st)) != FIB_OK) return rc;
+    const ScratchLayout::Regions buf = job->lay.at(job->scratch.p);
+    TraceArgs ta = trace_args(prm, field4, seeds, sublist, nsub, job->lay, buf);
     fib::DevBuf<float4> d_search;
     fib::DevBuf<int32_t> d_cell;
     fib::DevBuf<float> d_lcm;
@@ -1444,13 +1501,13 @@ int stream_trace_impl(const fib_stream_params *prm, const float *field4, const L
         for (const float4 &t : tab) cstart[(size_t)cell_of(t) + 1]++;
         for (size_t i = 1; i < cstart.size(); i++) cstart[i] += cstart[i - 1];
         const size_t smem = tab.size() * sizeof(float4) + cstart.size() * sizeof(int32_t);
-        if (smem > 150 * 1024) return bail(fib::fail(FIB_ERR_UNSUPPORTED, "search_dist %d needs %zu bytes of LDS for the search table (max 150 KiB)", d, smem));
-        if ((rc = d_search.alloc(tab.size())) != FIB_OK) return bail(rc);
-        if ((rc = d_cell.alloc(cstart.size())) != FIB_OK) return bail(rc);
+        if (smem > 150 * 1024) return fib::fail(FIB_ERR_UNSUPPORTED, "search_dist %d needs %zu bytes of LDS for the search table (max 150 KiB)", d, smem);
+        if ((rc = d_search.alloc(tab.size())) != FIB_OK) return rc;
+        if ((rc = d_cell.alloc(cstart.size())) != FIB_OK) return rc;
         hipError_t ec = hipMemcpyAsync(d_search.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice, st);
         if (ec == hipSuccess) ec = hipMemcpyAsync(d_cell.p, cstart.data(), cstart.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
         if (ec == hipSuccess) ec = hipStreamSynchronize(st);     // (the tables are locals: they must outlive the copies)
-        if (ec != hipSuccess) return bail(fib::fail(FIB_ERR_HIP, "search table upload failed: %s", hipGetErrorString(ec)));
+        if (ec != hipSuccess) return fib::fail(FIB_ERR_HIP, "search table upload failed: %s", hipGetErrorString(ec));
         ta.search = d_search.p; ta.nsearch = (int)tab.size(); ta.search_dist = d; ta.search_cosang = prm->search_cosang;
         ta.sdx = d3[0]; ta.sdy = d3[1]; ta.sdz = d3[2];
         ta.cell_start = d_cell.p; ta.G = G;
@@ -1458,38 +1515,56 @@ int stream_trace_impl(const fib_stream_params *prm, const float *field4, const L
         (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
         const unsigned mg = (unsigned)std::min<int64_t>(ncu, fib::cdiv(nl, 16));
         ec = hipFuncSetAttribute(reinterpret_cast<const void *>(stream_trace_micro_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (ec != hipSuccess) return bail(fib::fail(FIB_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(ec)));
-        fib::ProfScope prof("stream_trace_micro", st);
-        hipLaunchKernelGGL(stream_trace_micro_kernel, dim3(mg), dim3(1024), smem, st, ta);
+        if (ec != hipSuccess) return fib::fail(FIB_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(ec));
+        {
+            fib::ProfScope prof("stream_trace_micro", st);
+            hipLaunchKernelGGL(stream_trace_micro_kernel, dim3(mg), dim3(1024), smem, st, ta);
+        }
+        scan_lines(job->lay, buf, prm->len_min, nullptr, st);
     } else if (lin.lcms) {
         const int64_t nvox = (int64_t)prm->nx * prm->ny * prm->nz;
-        if ((rc = d_lcm.alloc((size_t)nvox * 10)) != FIB_OK) return bail(rc);
+        if ((rc = d_lcm.alloc((size_t)nvox * 10)) != FIB_OK) return rc;
         hipLaunchKernelGGL(lcm_prepare_kernel, dim3((unsigned)fib::cdiv(nvox, 256)), dim3(256), 0, st, lin.lcms, lin.thresh, nvox, d_lcm.p);
         ta.lcm = d_lcm.p; ta.sd0 = lin.sd0; ta.sd1 = lin.sd1; ta.rng_seed = lin.seed;
         ta.lcm_plain = lin.thresh >= 0x1p-40f && !ta.norm_generic;
         job->lcm = true;
-        fib::ProfScope prof("stream_trace_lcm", st);
-        launch_trace<true, false>(ta, prm->nvec, wide, grid, st);
+        {
+            fib::ProfScope prof("stream_trace_lcm", st);
+            launch_trace<true, false>(ta, prm->nvec, wide, st);
+        }
+        scan_lines(job->lay, buf, prm->len_min, nullptr, st);
     } else {
-        fib::ProfScope prof("stream_trace", st);
-        if (prm->interp) launch_trace<false, true>(ta, prm->nvec, wide, grid, st);   // trilinear option
-        else launch_trace<false, false>(ta, prm->nvec, wide, grid, st);
-    }
-    { fib::ProfScope prof("stream_scan", st);
-    hipLaunchKernelGGL(scan_block_kernel, dim3(nblocks), dim3(SCAN_T), 0, st, job->npts.p, nl, prm->len_min, job->excl.p, job->block_tot.p);
-    hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(SCAN_T), 0, st, job->block_tot.p, nblocks, job->total.p);
+        trace_and_scan(ta, prm, wide, job->lay, buf, nullptr, st);
     }
     hipError_t e = hipGetLastError();
     Pair tot{0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(&tot, job->total.p, sizeof(Pair), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&tot, buf.total, sizeof(Pair), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return bail(fib::fail(FIB_ERR_HIP, "streamline trace failed: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fib::fail(FIB_ERR_HIP, "streamline trace failed: %s", hipGetErrorString(e));
     job->kept_lines = tot.lines; job->kept_pts = tot.pts;
     *nlines_out = tot.lines; *npoints_out = tot.pts;
-    *job_out = job;
+    *job_out = job.release();
     return FIB_OK;
 }
 }  // namespace
+
+extern "C" int fibd_stream_trace(const fib_stream_params *prm, const float *field4, const int64_t *seeds, int64_t nseed,
+                                 const float *sublist, int32_t nsub, void *stream,
+                                 fib_stream_job **job_out, int64_t *nlines_out, int64_t *npoints_out) try {
+    return stream_trace_impl(prm, field4, LcmIn{}, seeds, nseed, sublist, nsub, stream, job_out, nlines_out, npoints_out);
+} FIB_API_CATCH
+
+extern "C" int fibd_stream_trace_lcm(const fib_stream_params *prm, const float *field4, const float *lcms, float lcm_thresh,
+                                     int32_t strdim0, int32_t strdim1, uint64_t rng_seed,
+                                     const int64_t *seeds, int64_t nseed, const float *sublist, int32_t nsub, void *stream,
+                                     fib_stream_job **job_out, int64_t *nlines_out, int64_t *npoints_out) try {
+    FIB_CHECK(lcms != nullptr, FIB_ERR_INVALID, "NULL lcms volume");
+    FIB_CHECK(strdim0 >= 0 && strdim0 < 3 && strdim1 >= 0 && strdim1 < 3 && strdim0 != strdim1, FIB_ERR_INVALID, "invalid in-plane dimensions");
+    FIB_CHECK(prm && prm->search_dist == 0, FIB_ERR_UNSUPPORTED, "LCM-guided tracking is a macro-scale mode (search_dist must be 0)");
+    LcmIn lin;
+    lin.lcms = lcms; lin.thresh = lcm_thresh; lin.sd0 = strdim0; lin.sd1 = strdim1; lin.seed = rng_seed;
+    return stream_trace_impl(prm, field4, lin, seeds, nseed, sublist, nsub, stream, job_out, nlines_out, npoints_out);
+} FIB_API_CATCH
 
 // flags[i] = sign bit of x of point i, then the sign is cleared (LCM runs; see stream_trace_kernel)
 __global__ __launch_bounds__(256) void stream_unpack_flags_kernel(float *xyz, uint8_t *flags, int64_t npts) {
@@ -1500,28 +1575,34 @@ __global__ __launch_bounds__(256) void stream_unpack_flags_kernel(float *xyz, ui
     xyz[3 * i] = fabsf(x);
 }
 
-static int pack_plain(fib_stream_job *job, int32_t *npts, int64_t *seed_index, float *xyz, uint8_t *flags, bool *flags_done, void *stream);
-
 // whole-tile kernel while 16 (len_max + 2) points (+ the .trk headers and the alignment slack) fit in LDS
 template <bool XF = false>
-static int launch_pack_n(const PackArgs &pa_in, int64_t nlines, int stride, hipStream_t st, bool *flags_done = nullptr) {
+static int launch_pack_n(const PackArgs &pa_in, hipStream_t st, bool *flags_done = nullptr) {
     PackArgs pa = pa_in;
-    const size_t smem = ((size_t)PK_LINES * stride * 3 + PK_LINES + 8) * sizeof(float) + (pa.lcm ? (((size_t)PK_LINES * stride + 15) & ~(size_t)15) : 0);
+    const size_t smem = ((size_t)PK_LINES * pa.stride * 3 + PK_LINES + 8) * sizeof(float) + (pa.lcm ? (((size_t)PK_LINES * pa.stride + 15) & ~(size_t)15) : 0);
     if (flags_done) *flags_done = smem <= 120 * 1024;          // (the wave-per-tile kernel below leaves the flag bit in x: the caller strips it)
     if (smem > 120 * 1024) { pa.lcm = 0; pa.out_flags = nullptr; }
     if (smem <= 120 * 1024) {
         if (smem > 48 * 1024)
             FIB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(stream_pack_tile_kernel<PK_LINES, 16, XF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL((stream_pack_tile_kernel<PK_LINES, 16, XF>), dim3((unsigned)fib::cdiv(nlines, PK_LINES)), dim3(16 * PK_LINES), smem, st, pa);
+        hipLaunchKernelGGL((stream_pack_tile_kernel<PK_LINES, 16, XF>), dim3((unsigned)fib::cdiv(pa.nlines, PK_LINES)), dim3(16 * PK_LINES), smem, st, pa);
     } else
-        hipLaunchKernelGGL(stream_pack_kernel<XF>, dim3((unsigned)fib::cdiv(nlines, PK_LINES * PK_WAVES)), dim3(PK_WAVES * 64), 0, st, pa);
+        hipLaunchKernelGGL(stream_pack_kernel<XF>, dim3((unsigned)fib::cdiv(pa.nlines, PK_LINES * PK_WAVES)), dim3(PK_WAVES * 64), 0, st, pa);
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 }
-template <bool XF = false>
-static int launch_pack(fib_stream_job *job, const PackArgs &pa, hipStream_t st, bool *flags_done = nullptr) {
-    job->last_stream = st;
-    return launch_pack_n<XF>(pa, job->nlines, job->stride, st, flags_done);
+
+static int pack_plain(fib_stream_job *job, int32_t *npts, int64_t *seed_index, float *xyz, uint8_t *flags, bool *flags_done, void *stream) {
+    FIB_CHECK(job != nullptr, FIB_ERR_INVALID, "job is NULL");
+    if (job->kept_lines == 0) return FIB_OK;
+    FIB_CHECK(npts && seed_index && xyz, FIB_ERR_INVALID, "NULL output buffer");
+    fib::DeviceGuard guard;
+    FIB_HIP(hipSetDevice(job->device));
+    PackArgs pa = pack_args(job->lay, job->lay.at(job->scratch.p), job->len_min, npts, seed_index, xyz);
+    pa.lcm = job->lcm ? 1 : 0; pa.out_flags = job->lcm ? flags : nullptr;
+    fib::ProfScope prof("stream_pack", (hipStream_t)stream);
+    job->scratch.last = (hipStream_t)stream;
+    return launch_pack_n(pa, (hipStream_t)stream, flags_done);   // (LCM jobs whose lines do not fit the tile kernel: x still carries the flag bit; the caller strips it)
 }
 
 extern "C" int fibd_stream_pack_flags(fib_stream_job *job, int32_t *npts, int64_t *seed_index, float *xyz, uint8_t *flags, void *stream) try {
@@ -1541,26 +1622,6 @@ extern "C" int fibd_stream_pack(fib_stream_job *job, int32_t *npts, int64_t *see
     return fibd_stream_pack_flags(job, npts, seed_index, xyz, nullptr, stream);   // (strips the flag bit of LCM runs)
 } FIB_API_CATCH
 
-static int pack_plain(fib_stream_job *job, int32_t *npts, int64_t *seed_index, float *xyz, uint8_t *flags, bool *flags_done, void *stream) {
-    FIB_CHECK(job != nullptr, FIB_ERR_INVALID, "job is NULL");
-    if (job->kept_lines == 0) return FIB_OK;
-    FIB_CHECK(npts && seed_index && xyz, FIB_ERR_INVALID, "NULL output buffer");
-    fib::DeviceGuard guard;
-    FIB_HIP(hipSetDevice(job->device));
-    PackArgs pa{};
-    pa.scratch = job->scratch; pa.npts = job->npts.p; pa.nfwd = job->nfwd.p;
-    pa.excl = job->excl.p; pa.block_off = job->block_tot.p;
-    pa.out_npts = npts; pa.out_seed = seed_index; pa.out_xyz = xyz;
-    pa.nlines = job->nlines; pa.line0 = 0; pa.out_line0 = 0; pa.out_pt0 = 0;
-    pa.stride = job->stride; pa.nslots = job->nslots; pa.len_min = job->prm.len_min;
-    pa.scratch_plain = fib::ab_env("FIBERS_STREAM_PACK_PLAIN") != nullptr;
-    pa.lcm = job->lcm ? 1 : 0; pa.out_flags = job->lcm ? flags : nullptr;
-    fib::ProfScope prof("stream_pack", (hipStream_t)stream);
-    { const int rcl = launch_pack(job, pa, (hipStream_t)stream, flags_done); if (rcl != FIB_OK) return rcl; }
-    FIB_HIP(hipGetLastError());
-    return FIB_OK;                                      // (LCM jobs whose lines do not fit the tile kernel: x still carries the flag bit; the caller strips it)
-}
-
 // fibd_stream_pack_trk and fibd_stream_pack_trk_xfm (vox2vox != NULL: the XF variant of the pack kernels)
 static int pack_trk(fib_stream_job *job, const float *vox2vox, const float voxel_size[3], void *body, void *stream) {
     FIB_CHECK(job != nullptr && voxel_size != nullptr, FIB_ERR_INVALID, "NULL argument");
@@ -1569,19 +1630,12 @@ static int pack_trk(fib_stream_job *job, const float *vox2vox, const float voxel
     FIB_CHECK(body != nullptr, FIB_ERR_INVALID, "NULL output buffer");
     fib::DeviceGuard guard;
     FIB_HIP(hipSetDevice(job->device));
-    PackArgs pa{};
-    pa.scratch = job->scratch; pa.npts = job->npts.p; pa.nfwd = job->nfwd.p;
-    pa.excl = job->excl.p; pa.block_off = job->block_tot.p;
-    pa.out_npts = nullptr; pa.out_seed = nullptr; pa.out_xyz = reinterpret_cast<float *>(body);
-    pa.nlines = job->nlines; pa.line0 = 0; pa.out_line0 = 0; pa.out_pt0 = 0;
-    pa.stride = job->stride; pa.nslots = job->nslots; pa.len_min = job->prm.len_min;
-    pa.scratch_plain = fib::ab_env("FIBERS_STREAM_PACK_PLAIN") != nullptr;
+    PackArgs pa = pack_args(job->lay, job->lay.at(job->scratch.p), job->len_min, nullptr, nullptr, reinterpret_cast<float *>(body));
     pa.trk = 1; pa.vs[0] = voxel_size[0]; pa.vs[1] = voxel_size[1]; pa.vs[2] = voxel_size[2];
     if (vox2vox) memcpy(pa.xf.m, vox2vox, sizeof pa.xf.m);
     fib::ProfScope prof(vox2vox ? "stream_pack_trk_xfm" : "stream_pack_trk", (hipStream_t)stream);
-    { const int rcl = vox2vox ? launch_pack<true>(job, pa, (hipStream_t)stream) : launch_pack(job, pa, (hipStream_t)stream); if (rcl != FIB_OK) return rcl; }
-    FIB_HIP(hipGetLastError());
-    return FIB_OK;
+    job->scratch.last = (hipStream_t)stream;
+    return vox2vox ? launch_pack_n<true>(pa, (hipStream_t)stream) : launch_pack_n(pa, (hipStream_t)stream);
 }
 
 extern "C" int fibd_stream_pack_trk(fib_stream_job *job, const float voxel_size[3], void *body, void *stream) try {
@@ -1592,6 +1646,17 @@ extern "C" int fibd_stream_pack_trk_xfm(fib_stream_job *job, const float vox2vox
     FIB_CHECK(vox2vox != nullptr, FIB_ERR_INVALID, "NULL argument");
     return pack_trk(job, vox2vox, voxel_size, body, stream);
 } FIB_API_CATCH
+
+// the fused trace + look-back + pack kernel for NVEC vectors per voxel (fibd_stream_run)
+template <int NVEC>
+static int launch_fused(const TraceArgs &ta, unsigned grid, size_t smem, hipStream_t st) {
+    if (smem > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(stream_trace_kernel<NVEC, false, false, false, true>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        return fib::fail(FIB_ERR_HIP, "hipFuncSetAttribute failed");
+    fib::ProfScope prof("stream_trace", st);
+    hipLaunchKernelGGL((stream_trace_kernel<NVEC, false, false, false, true>), dim3(grid), dim3(FUSED_BLOCK), smem, st, ta);
+    return FIB_OK;
+}
 
 // stream (stream.jl:730-790) in ONE call, straight into the caller's buffers (no second call, no allocation by the library):
 // trace, scan and pack one after the other on the caller's stream.  ([r5] the batched form -- a batch packed on a second stream
@@ -1605,13 +1670,9 @@ static int stream_run_impl(const fib_stream_params *prm, const float *field4, co
     FIB_CHECK(prm && field4 && (counts_dev || (nlines_out && npoints_out)), FIB_ERR_INVALID, "NULL argument");
     if (nlines_out) *nlines_out = 0;
     if (npoints_out) *npoints_out = 0;
-    FIB_CHECK(nseed >= 0 && (nseed == 0 || seeds), FIB_ERR_INVALID, "invalid seed list");
-    FIB_CHECK(nsub >= 1 && sublist, FIB_ERR_INVALID, "sublist must hold at least one offset (use [0,0,0] for nsub=0, stream.jl:180)");
-    FIB_CHECK(prm->nx > 0 && prm->ny > 0 && prm->nz > 0 && prm->nvec >= 1 && prm->nvec <= 8, FIB_ERR_INVALID, "invalid volume / nvec");
-    FIB_CHECK(prm->len_max >= 0 && prm->len_max < (1 << 24), FIB_ERR_INVALID, "invalid len_max");
+    int rc = check_args(prm, seeds, nseed, sublist, nsub);
+    if (rc != FIB_OK) return rc;
     FIB_CHECK(prm->search_dist == 0, FIB_ERR_UNSUPPORTED, "fibd_stream_run covers macro-scale tracking (search_dist 0); use fibd_stream_trace for the microscopy regime");
-    FIB_CHECK(prm->interp == 0 || prm->interp == 1, FIB_ERR_INVALID, "interp must be 0 (nearest voxel, the reference) or 1 (trilinear)");
-    FIB_CHECK((int64_t)prm->nx * prm->ny * prm->nz < ((int64_t)1 << 40), FIB_ERR_UNSUPPORTED, "volumes of 2^40 voxels or more are not supported");
     FIB_CHECK(lines_cap >= 0 && points_cap >= 0 && (lines_cap == 0 || (npts && seed_index)) && (points_cap == 0 || xyz), FIB_ERR_INVALID, "invalid output buffers");
     const int64_t nl = nseed * nsub;
     hipStream_t st = (hipStream_t)stream;
@@ -1622,122 +1683,50 @@ static int stream_run_impl(const fib_stream_params *prm, const float *field4, co
     const bool wide = field_is_wide(prm);
     int device = 0;
     FIB_HIP(hipGetDevice(&device));
-    const int stride = prm->len_max + 2, nslots = (prm->len_max + 4 + 3) & ~3;   // (whole groups of four slots: the tracer stores them together)
-    const int nblk = (int)fib::cdiv(nl, SCAN_B);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_scr = up((size_t)fib::cdiv(nl, SCR_ROW) * SCR_ROW * nslots * 3 * sizeof(float));
-    const size_t b_i32 = up((size_t)nl * sizeof(int32_t)), b_excl = up((size_t)nl * sizeof(Pair)), b_bt = up((size_t)nblk * sizeof(Pair));
-    const size_t sbytes = b_scr + 2 * b_i32 + b_excl + b_bt + 256;
-    // the caller's workspace when it is free, else one of our own for the call
-    fib_stream_ws *ws = reinterpret_cast<fib_stream_ws *>(prm->ws), *own = nullptr;
-    bool have = false;
-    if (ws) {
-        std::lock_guard<std::mutex> lk(ws->mu);
-        if (!ws->busy && ws->device == device) { ws->busy = true; have = true; }
-    }
-    if (!have) {
-        int rcw = fibd_stream_ws_create(device, &own);
-        if (rcw != FIB_OK) return rcw;
-        ws = own; ws->busy = true;
-    }
-    auto release = [&](int code) {
-        if (own) { (void)hipStreamSynchronize(st); own->busy = false; fibd_stream_ws_destroy(own); }
-        else {
-            std::lock_guard<std::mutex> lk(ws->mu);
-            ws->pending = hipEventRecord(ws->done, st) == hipSuccess;
-            if (!ws->pending) (void)hipStreamSynchronize(st);
-            ws->busy = false;
-        }
-        return code;
-    };
-    if (ws->bytes < sbytes) {
-        if (ws->pending) { (void)hipEventSynchronize(ws->done); ws->pending = false; }
-        if (ws->p) (void)hipFree(ws->p);
-        ws->p = nullptr; ws->bytes = 0;
-        if (hipMalloc(&ws->p, sbytes) != hipSuccess) { ws->p = nullptr; return release(fib::fail(FIB_ERR_NOMEM, "cannot allocate %zu bytes of streamline scratch", sbytes)); }
-        ws->bytes = sbytes;
-    }
-    if (ws->pending) {
-        if (hipStreamWaitEvent(st, ws->done, 0) != hipSuccess) (void)hipEventSynchronize(ws->done);
-        ws->pending = false;
-    }
-    char *pb = reinterpret_cast<char *>(ws->p);
-    float *scr = reinterpret_cast<float *>(pb);
-    int32_t *bn = reinterpret_cast<int32_t *>(pb + b_scr), *bf = reinterpret_cast<int32_t *>(pb + b_scr + b_i32);
-    Pair *bex = reinterpret_cast<Pair *>(pb + b_scr + 2 * b_i32), *bbt = reinterpret_cast<Pair *>(pb + b_scr + 2 * b_i32 + b_excl);
-    Pair *total = reinterpret_cast<Pair *>(pb + b_scr + 2 * b_i32 + b_excl + b_bt);
-    TraceArgs ta{};
-    ta.field = reinterpret_cast<const float4 *>(field4); ta.seeds = seeds; ta.sublist = sublist;
-    ta.scratch = scr; ta.npts = bn; ta.nfwd = bf; ta.line0 = 0; ta.nlines = nl;
-    ta.nx = prm->nx; ta.ny = prm->ny; ta.nz = prm->nz; ta.nvec = prm->nvec; ta.nsub = nsub;
-    ta.len_max = prm->len_max; ta.stride = stride; ta.nslots = nslots;
-    ta.cosang = prm->cosang_thresh; ta.step = prm->step_size; ta.smooth = prm->smooth_coeff;
-    { const char *e = fib::ab_env("FIBERS_STREAM_SCRATCH_PLAIN"); ta.scratch_plain = e ? std::atoi(e) : 0; }
-    ta.norm_generic = fib::ab_env("FIBERS_STREAM_NORM_GENERIC") != nullptr;
-    { const char *e = fib::ab_env("FIBERS_STREAM_DBG"); ta.dbg = e ? std::atoi(e) : 0; }
-    const unsigned grid = (unsigned)fib::cdiv(nl, 256);
+    const ScratchLayout lay(nl, prm->len_max);
+    ScratchLease scratch;                                          // (given back when the call returns)
+    if ((rc = scratch.acquire(prm->ws, device, lay.bytes, st)) != FIB_OK) return rc;
+    const ScratchLayout::Regions buf = lay.at(scratch.p);
+    TraceArgs ta = trace_args(prm, field4, seeds, sublist, nsub, lay, buf);
     // [r5] FUSED (fused_pack_block): trace + look-back + pack in ONE launch, for nearest-voxel tracking with 1, 2 or 3 vectors per voxel on fields
     // below 2^28 vectors whose lines fit a 16-line LDS tile (len_max <= ~200) -- from 2^21 lines on: the fused kernel wins by overlapping
     // workgroups that pack with workgroups that still trace, which needs several rounds of workgroups per CU (measured, tools/stream_fused_ab.py:
     // 9.96 M lines x 3 vectors 9.7-10.6 ms against 11.5-11.8; 1 M lines 1.05-1.17 ms against 1.09-1.13: two rounds, no steady state).
     // Everything else takes the three launches below.  (Diagnostic build: FIBERS_STREAM_UNFUSED=1 / FIBERS_STREAM_FUSED=1 force either.)
-    const size_t fsmem = std::max(((size_t)FUSED_TILE * stride * 3 + FUSED_TILE + 8) * sizeof(float), (size_t)(FUSED_BLOCK / 16) * 4 * SCR_SLOT_FLOATS * sizeof(float));   // the pack's tile buffer; the trace loop parks four trips of points there
+    const size_t fsmem = std::max(((size_t)FUSED_TILE * lay.stride * 3 + FUSED_TILE + 8) * sizeof(float), (size_t)(FUSED_BLOCK / 16) * 4 * SCR_SLOT_FLOATS * sizeof(float));   // the pack's tile buffer; the trace loop parks four trips of points there
     const bool fused_ok = !wide && !prm->interp && prm->nvec >= 1 && prm->nvec <= 3 && fsmem <= 40 * 1024 &&
-                          nl < ((int64_t)1 << 26) && nl * (int64_t)(prm->len_max + 2) < ((int64_t)1 << 36) && b_excl >= ((size_t)fib::cdiv(nl, FUSED_BLOCK) + 1) * sizeof(unsigned long long);
+                          nl < ((int64_t)1 << 26) && nl * (int64_t)(prm->len_max + 2) < ((int64_t)1 << 36) &&
+                          lay.off_btot - lay.off_excl >= ((size_t)fib::cdiv(nl, FUSED_BLOCK) + 1) * sizeof(unsigned long long);   // (the look-back state lives in excl)
     const bool fused = fused_ok && fib::ab_env("FIBERS_STREAM_UNFUSED") == nullptr && (nl >= ((int64_t)1 << 21) || fib::ab_env("FIBERS_STREAM_FUSED") != nullptr);
     if (fused) {
         const unsigned fgrid = (unsigned)fib::cdiv(nl, FUSED_BLOCK);
-        ta.fstate = reinterpret_cast<unsigned long long *>(bex);          // (the scan's array is free: no scan)
-        ta.out_npts = npts; ta.out_seed = seed_index; ta.out_xyz = xyz; ta.ftotal = total; ta.fcounts = counts_dev;
+        ta.fstate = reinterpret_cast<unsigned long long *>(buf.excl);   // (the scan's array is free: no scan)
+        ta.out_npts = npts; ta.out_seed = seed_index; ta.out_xyz = xyz; ta.ftotal = buf.total; ta.fcounts = counts_dev;
         ta.lines_cap = lines_cap; ta.points_cap = points_cap; ta.len_min = prm->len_min;
         if (hipMemsetAsync(ta.fstate, 0, ((size_t)fgrid + 1) * sizeof(unsigned long long), st) != hipSuccess)      // (+ the ticket counter behind the granules)
-            return release(fib::fail(FIB_ERR_HIP, "hipMemsetAsync failed"));
+            return fib::fail(FIB_ERR_HIP, "hipMemsetAsync failed");
         // [r6] one code path per vector count 1..3 (DTI e1 | e1 + e2 or two peaks | three peaks)
-        const void *fk = prm->nvec == 1 ? reinterpret_cast<const void *>(stream_trace_kernel<1, false, false, false, true>)
-                       : prm->nvec == 2 ? reinterpret_cast<const void *>(stream_trace_kernel<2, false, false, false, true>)
-                                        : reinterpret_cast<const void *>(stream_trace_kernel<3, false, false, false, true>);
-        if (fsmem > 48 * 1024 && hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fsmem) != hipSuccess)
-            return release(fib::fail(FIB_ERR_HIP, "hipFuncSetAttribute failed"));
-        fib::ProfScope prof("stream_trace", st);
-        if (prm->nvec == 1)      hipLaunchKernelGGL((stream_trace_kernel<1, false, false, false, true>), dim3(fgrid), dim3(FUSED_BLOCK), fsmem, st, ta);
-        else if (prm->nvec == 2) hipLaunchKernelGGL((stream_trace_kernel<2, false, false, false, true>), dim3(fgrid), dim3(FUSED_BLOCK), fsmem, st, ta);
-        else                     hipLaunchKernelGGL((stream_trace_kernel<3, false, false, false, true>), dim3(fgrid), dim3(FUSED_BLOCK), fsmem, st, ta);
+        rc = prm->nvec == 1 ? launch_fused<1>(ta, fgrid, fsmem, st) : prm->nvec == 2 ? launch_fused<2>(ta, fgrid, fsmem, st) : launch_fused<3>(ta, fgrid, fsmem, st);
+        if (rc != FIB_OK) return rc;
     } else {
-    {
-        fib::ProfScope prof("stream_trace", st);
-        if (prm->interp) launch_trace<false, true>(ta, prm->nvec, wide, grid, st);
-        else launch_trace<false, false>(ta, prm->nvec, wide, grid, st);
-    }
-    {
-        fib::ProfScope prof("stream_scan", st);
-        hipLaunchKernelGGL(scan_block_kernel, dim3(nblk), dim3(SCAN_T), 0, st, bn, nl, prm->len_min, bex, bbt);
-        hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(SCAN_T), 0, st, bbt, nblk, total, (const Pair *)nullptr, counts_dev);
-    }
-    if (hipGetLastError() != hipSuccess) return release(fib::fail(FIB_ERR_HIP, "streamline trace launch failed"));
-    PackArgs pa{};
-    pa.scratch = scr; pa.npts = bn; pa.nfwd = bf; pa.excl = bex; pa.block_off = bbt;
-    pa.out_npts = npts; pa.out_seed = seed_index; pa.out_xyz = xyz;
-    pa.nlines = nl; pa.line0 = 0; pa.out_line0 = 0; pa.out_pt0 = 0;
-    pa.stride = stride; pa.nslots = nslots; pa.len_min = prm->len_min;
-    pa.scratch_plain = fib::ab_env("FIBERS_STREAM_PACK_PLAIN") != nullptr;
-    pa.lines_cap = lines_cap; pa.points_cap = points_cap; pa.capped = 1;   // a line whose place lies beyond the buffers is dropped, the totals say what was needed
-    {
+        trace_and_scan(ta, prm, wide, lay, buf, counts_dev, st);
+        if (hipGetLastError() != hipSuccess) return fib::fail(FIB_ERR_HIP, "streamline trace launch failed");
+        PackArgs pa = pack_args(lay, buf, prm->len_min, npts, seed_index, xyz);
+        pa.lines_cap = lines_cap; pa.points_cap = points_cap; pa.capped = 1;   // a line whose place lies beyond the buffers is dropped, the totals say what was needed
         fib::ProfScope prof("stream_pack", st);
-        const int rcl = launch_pack_n(pa, nl, stride, st);
-        if (rcl != FIB_OK) return release(rcl);
+        if ((rc = launch_pack_n(pa, st)) != FIB_OK) return rc;
     }
-    }   // (!fused)
-    if (hipGetLastError() != hipSuccess) return release(fib::fail(FIB_ERR_HIP, "streamline launch failed"));
-    if (counts_dev) return release(FIB_OK);                       // ({lines, points} were written by the scan / the last workgroup: no host round trip)
+    if (hipGetLastError() != hipSuccess) return fib::fail(FIB_ERR_HIP, "streamline launch failed");
+    if (counts_dev) return FIB_OK;                                 // ({lines, points} were written by the scan / the last workgroup: no host round trip)
     Pair tot{0, 0};
-    hipError_t e = hipMemcpyAsync(&tot, total, sizeof(Pair), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(&tot, buf.total, sizeof(Pair), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return release(fib::fail(FIB_ERR_HIP, "streamline run failed: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fib::fail(FIB_ERR_HIP, "streamline run failed: %s", hipGetErrorString(e));
     *nlines_out = tot.lines; *npoints_out = tot.pts;
     if (tot.lines > lines_cap || tot.pts > points_cap)
-        return release(fib::fail(FIB_ERR_CAPACITY, "output buffers too small: %lld lines / %lld points needed, %lld / %lld given",
-                                 (long long)tot.lines, (long long)tot.pts, (long long)lines_cap, (long long)points_cap));
-    return release(FIB_OK);
+        return fib::fail(FIB_ERR_CAPACITY, "output buffers too small: %lld lines / %lld points needed, %lld / %lld given",
+                         (long long)tot.lines, (long long)tot.pts, (long long)lines_cap, (long long)points_cap);
+    return FIB_OK;
 }
 
 extern "C" int fibd_stream_run(const fib_stream_params *prm, const float *field4, const int64_t *seeds, int64_t nseed,
@@ -1758,13 +1747,13 @@ extern "C" int fibd_stream_run_enqueue(const fib_stream_params *prm, const float
 
 extern "C" int fibd_stream_all_npts(fib_stream_job *job, int32_t *all_npts, void *stream) try {
     FIB_CHECK(job != nullptr, FIB_ERR_INVALID, "job is NULL");
-    if (job->nlines == 0) return FIB_OK;
+    if (job->lay.nlines == 0) return FIB_OK;
     FIB_CHECK(all_npts != nullptr, FIB_ERR_INVALID, "NULL output buffer");
     fib::DeviceGuard guard;
     FIB_HIP(hipSetDevice(job->device));
-    job->last_stream = (hipStream_t)stream;
-    hipLaunchKernelGGL(copy_i32_kernel, dim3((unsigned)fib::cdiv(job->nlines, 256)), dim3(256), 0, (hipStream_t)stream,
-                       job->npts.p, all_npts, job->nlines);
+    job->scratch.last = (hipStream_t)stream;
+    hipLaunchKernelGGL(copy_i32_kernel, dim3((unsigned)fib::cdiv(job->lay.nlines, 256)), dim3(256), 0, (hipStream_t)stream,
+                       job->lay.at(job->scratch.p).npts, all_npts, job->lay.nlines);
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 } FIB_API_CATCH

@@ -294,6 +294,18 @@ def stream_field_device(ovec: List, f: Optional[List] = None, f_thresh: float = 
     return field, mout
 
 
+def _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                   search_dist=0, search_ang=10):
+    """the preamble of the device-resident tracer calls: checks field / seeds / sublist, resolves `workspace` ("default": the host
+    mirror's arena for the field's device) and returns the fib_stream_params"""
+    import torch
+    _chk_dev(field, torch.float32, "field")
+    _chk_dev(seeds, torch.int64, "seeds")
+    _chk_dev(sublist, torch.float32, "sublist")
+    ws = default_workspace(field.device.index or 0) if isinstance(workspace, str) else workspace
+    return _params(shape, field.shape[1], len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist, search_ang, ws, interp)
+
+
 def stream_device(field, shape, seeds, sublist, len_min=3, len_max=None, ang_thresh=45, step_size=0.5,
                   smooth_coeff=0.2, stream=None, want_all_npts=False, search_dist=0, search_ang=10,
                   lcms=None, lcm_thresh=0.099, strdims=(0, 1), rng_seed=0, xyz_out=None, workspace="default", interp="nearest"):
@@ -308,12 +320,8 @@ def stream_device(field, shape, seeds, sublist, len_min=3, len_max=None, ang_thr
     host mirror's arena for the field's device).  interp="trilinear": the non-reference option of fib_stream_params.interp.
     Returns dict(npts int32 [nlines], seed_index int64 [nlines], xyz float32 [npoints, 3])."""
     import torch
-    _chk_dev(field, torch.float32, "field")
-    _chk_dev(seeds, torch.int64, "seeds")
-    _chk_dev(sublist, torch.float32, "sublist")
-    nvec = field.shape[1]
-    ws = default_workspace(field.device.index or 0) if isinstance(workspace, str) else workspace
-    prm = _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist, search_ang, ws, interp)
+    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                         search_dist, search_ang)
     job = C.c_void_p()
     nl, npnt = C.c_int64(0), C.c_int64(0)
     L = _lib.lib()
@@ -368,17 +376,11 @@ class StreamBuffers:
 def stream_device_run(field, shape, seeds, sublist, buffers: StreamBuffers = None, len_min=3, len_max=None, ang_thresh=45, step_size=0.5,
                       smooth_coeff=0.2, stream=None, workspace="default", interp="nearest"):
     """stream_device in ONE library call (fibd_stream_run): trace, scan and pack without a host round trip in between -- from 2^21
-    lines on (nearest-voxel tracking, 1 or 3 vectors per voxel) as ONE kernel in which the workgroup that traced 512 lines packs them
+    lines on (nearest-voxel tracking, 1, 2 or 3 vectors per voxel) as ONE kernel in which the workgroup that traced 512 lines packs them
     behind a decoupled look-back; results go straight into `buffers` (grown and the call repeated when they are too small: a first
     call sizes them).  Same lines, order and layout as stream_device; macro-scale angle picking only.
     Returns dict(npts, seed_index, xyz) -- views of the buffers, valid until the next call with them."""
-    import torch
-    _chk_dev(field, torch.float32, "field")
-    _chk_dev(seeds, torch.int64, "seeds")
-    _chk_dev(sublist, torch.float32, "sublist")
-    nvec = field.shape[1]
-    ws = default_workspace(field.device.index or 0) if isinstance(workspace, str) else workspace
-    prm = _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, 0, 10, ws, interp)
+    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp)
     nl_max = int(seeds.numel()) * int(sublist.shape[0])
     if buffers is None:
         buffers = StreamBuffers(field.device)
@@ -406,17 +408,12 @@ def stream_device_run_enqueue(field, shape, seeds, sublist, buffers: StreamBuffe
     None) receives {lines, points} from the stream -- read it after synchronising; values above the buffers' capacities mean that
     lines were dropped for lack of room.  Returns (buffers, counts)."""
     import torch
-    _chk_dev(field, torch.float32, "field")
-    _chk_dev(seeds, torch.int64, "seeds")
-    _chk_dev(sublist, torch.float32, "sublist")
+    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp)
     if buffers is None or buffers.npts is None or buffers.npts.numel() == 0:
         raise ValueError("stream_device_run_enqueue needs sized buffers (call stream_device_run once)")
     if counts is None:
         counts = torch.zeros(2, dtype=torch.int64, device=field.device)
     _chk_dev(counts, torch.int64, "counts")
-    nvec = field.shape[1]
-    ws = default_workspace(field.device.index or 0) if isinstance(workspace, str) else workspace
-    prm = _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, 0, 10, ws, interp)
     _lib.check(_lib.lib().fibd_stream_run_enqueue(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sublist.data_ptr(),
                                                   sublist.shape[0], buffers.npts.data_ptr(), buffers.seed_index.data_ptr(), buffers.npts.numel(),
                                                   buffers.xyz.data_ptr(), buffers.xyz.shape[0], counts.data_ptr(), _stream_ptr(stream)))

@@ -306,7 +306,7 @@ int fibd_stream_pack(fib_stream_job *job, int32_t *npts, int64_t *seed_index, fl
 
 /* trace + pack in ONE call into caller-provided device buffers (npts [lines_cap] int32, seed_index [lines_cap] int64, xyz
  * [3*points_cap] float): the same lines, order and layout as fibd_stream_trace + fibd_stream_pack without the second call and
- * without any allocation on the caller's side of the boundary between them.  From 2^21 lines on (nearest-voxel tracking, 1 or 3
+ * without any allocation on the caller's side of the boundary between them.  From 2^21 lines on (nearest-voxel tracking, 1, 2 or 3
  * vectors per voxel, lines that fit a 16-line LDS tile) it is ONE kernel: the workgroup that traced 512 lines packs them behind a
  * decoupled look-back over the workgroups' totals.  *nlines / *npoints receive the totals; when they exceed the capacities the call
  * returns FIB_ERR_CAPACITY (lines that did not fit are missing from the buffers; call again with larger ones).  Macro-scale angle

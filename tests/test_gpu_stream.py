@@ -520,6 +520,102 @@ def test_stream_run_enqueue_leaves_the_counts_on_the_device(fj):
     assert counts.tolist() == [0, 0]
 
 
+def test_stream_scratch_lease_paths_return_the_same_lines(fj):
+    """the tracer's scratch on every path of fib_stream_ws (include/fibers_hip.h): no workspace; the default arena held by a traced,
+    unpacked job, so that stream_device / stream_device_run / stream_device_run_enqueue take scratch of their own meanwhile; arenas
+    that must grow and then serve a smaller call; a call on a side stream right after a job on another stream released the arena (the
+    stream-ordered hand-over); an arena on another device -- every result bit-identical to stream_device on the free default arena"""
+    import ctypes as C
+    import sys
+    import torch
+    from fibers_jl_amd import _lib
+    n = 20
+    dev = torch.device("cuda", 0)
+    f = _fields(n, 4)
+    ov = [torch.from_numpy(np.ascontiguousarray(f[k].reshape(-1, 3, order="F").T)).to(dev) for k in ("wavy", "circ")]
+    mask = torch.from_numpy((np.random.default_rng(3).random(n ** 3) < 0.9).astype(np.uint8)).to(dev)
+    field, mout = fj.stream_field_device(ov, mask=mask)
+    seeds = torch.nonzero(mout).flatten()
+    sub = torch.from_numpy(fj.make_sublist(2, np.random.default_rng(8))).to(dev)
+    shape = (n, n, n)
+    kw = dict(len_min=2, len_max=30, smooth_coeff=0.3)
+    big = dict(kw, len_max=90)                                                          # 3 x the point slots per line: the arena grows
+    ref = fj.stream_device(field, shape, seeds, sub, **kw)
+    ref_big = fj.stream_device(field, shape, seeds, sub, **big)
+    assert ref["npts"].numel() > 1000 and ref_big["xyz"].shape[0] > ref["xyz"].shape[0]
+
+    def same(got, want, what):
+        for k in ("npts", "seed_index", "xyz"):
+            assert torch.equal(got[k], want[k]), (what, k)
+
+    def trace(ws, stream=None, **kw_):
+        return fj.stream_device(field, shape, seeds, sub, stream=stream, workspace=ws, **(kw_ or kw))
+
+    def run(ws, stream=None, **kw_):
+        return fj.stream_device_run(field, shape, seeds, sub, buffers=fj.StreamBuffers(dev), stream=stream, workspace=ws, **(kw_ or kw))
+
+    def enqueue(ws):                                                                    # -> a function that reads the results once synchronised
+        bufs = fj.StreamBuffers(dev, ref["npts"].numel(), ref["xyz"].shape[0])
+        _, counts = fj.stream_device_run_enqueue(field, shape, seeds, sub, bufs, workspace=ws, **kw)
+
+        def result():
+            nl, npnt = counts.tolist()
+            return dict(npts=bufs.npts[:nl], seed_index=bufs.seed_index[:nl], xyz=bufs.xyz[:npnt])
+        return result
+
+    same(trace(None), ref, "stream_device, no workspace")
+    same(run(None), ref, "stream_device_run, no workspace")
+
+    # a traced job holds the default arena, unpacked: the calls meanwhile take scratch of their own
+    smod = sys.modules[fj.stream_device_run.__module__]                                # (fj.stream is the function, not the module)
+    prm = smod._params(shape, 2, 2, 30, 45, 0.5, 0.3, 0, 10, smod.default_workspace(0))
+    L = _lib.lib()
+    job, nl, npnt = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+    _lib.check(L.fibd_stream_trace(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sub.data_ptr(), sub.shape[0], None,
+                                   C.byref(job), C.byref(nl), C.byref(npnt)))
+    try:
+        assert (nl.value, npnt.value) == (ref["npts"].numel(), ref["xyz"].shape[0])
+        same(trace("default"), ref, "stream_device, arena held")
+        same(run("default"), ref, "stream_device_run, arena held")
+        result = enqueue("default")
+        torch.cuda.synchronize()
+        same(result(), ref, "stream_device_run_enqueue, arena held")
+        held = {k: torch.empty_like(ref[k]) for k in ("npts", "seed_index", "xyz")}
+        _lib.check(L.fibd_stream_pack(job, held["npts"].data_ptr(), held["seed_index"].data_ptr(), held["xyz"].data_ptr(), None))
+        torch.cuda.synchronize()
+        same(held, ref, "the held job")
+    finally:
+        L.fib_stream_job_destroy(job)
+
+    # new arenas that grow (through a trace, then through a run) and then serve the smaller call again
+    ws = fj.StreamWorkspace(0)
+    same(run(ws), ref, "stream_device_run, new arena")
+    same(trace(ws, **big), ref_big, "stream_device, arena grown")
+    same(run(ws), ref, "stream_device_run, after the growth")
+    ws = fj.StreamWorkspace(0)
+    same(trace(ws), ref, "stream_device, new arena")
+    same(run(ws, **big), ref_big, "stream_device_run, arena grown")
+    same(trace(ws), ref, "stream_device, after the growth")
+
+    # the hand-over: a job on the current stream releases the arena with its work still queued, a call on a side stream takes it next
+    side = torch.cuda.Stream(dev)
+    result = enqueue(ws)
+    got = run(ws, stream=side)
+    torch.cuda.synchronize()
+    same(got, ref, "stream_device_run on a side stream, after a release")
+    same(result(), ref, "stream_device_run_enqueue before the hand-over")
+    result = enqueue(ws)
+    got = trace(ws, stream=side)
+    torch.cuda.synchronize()
+    same(got, ref, "stream_device on a side stream, after a release")
+    same(result(), ref, "stream_device_run_enqueue before the hand-over")
+
+    if torch.cuda.device_count() > 1:                                                   # an arena on another device: scratch of the call's own
+        other = fj.StreamWorkspace(1)
+        same(trace(other), ref, "stream_device, arena on another device")
+        same(run(other), ref, "stream_device_run, arena on another device")
+
+
 def test_stream_wide_field_past_the_32_bit_gather_limit(fj, orc):
     """An orientation field of 2^28 vectors or more (4 GiB of float4: the microscopy regime's whole-slide sections, stream.jl:83,147-172) takes
     the tracer's WIDE form -- 64-bit voxel indices and gather offsets, chosen at launch.  4096 x 4096 x 17 voxels, one vector each = 4.56 GB;
