@@ -252,14 +252,23 @@ __device__ __forceinline__ int lcm_match_edge(int dx, int dy, int dz, int sd0, i
 // The points go into the slot-major scratch and the per-line counts beside them; the scan + pack kernels below give every kept
 // line its place.  ([r5] the two-pass form -- count, scan, trace again straight into the output -- was as slow as the copy it
 // saved (a trace without stores takes 0.50 of the 0.53 ms) and has been removed: profiles/r04/negative_results.txt.)
-// TRI (params.interp = 1, not in the reference): the direction followed is the trilinear blend of the eight voxels around the
-// tentative position instead of the nearest voxel's vector -- see the TRI block below for the exact definition.
+// TRI (params.interp = 1, 2, 3, not in the reference): the direction followed is the trilinear blend of the eight voxels around the
+// tentative position instead of the nearest voxel's vector -- see `blend` below for the exact definition.  TRI is also the
+// integrator that finds the tentative position: 1 = forward Euler, 2 = midpoint (RK2, one more blend per step), 3 = classical RK4
+// (three more) -- include/fibers_hip.h, fib_stream_params.interp.
 // WIDE: 64-bit voxel indices and gather offsets, for orientation fields of 2^28 vectors (4 GiB) or more -- the microscopy
 // regime's whole-slide sections (stream.jl:83,147-172); chosen at launch, bit-identical to the 32-bit form on small fields.
 struct FuseLds;   // (defined with the pack kernels below)
 template <int NVEC> __device__ void fused_pack_block(const TraceArgs &a, int64_t b, int64_t li, bool live, int npts, int nf, int gap);
 
-template <int NVEC, bool LCM = false, bool TRI = false, bool WIDE = false, bool FUSED = false>   // NVEC > 0: compile-time vector count; 0: runtime
+// [rk] The stages of RK2 / RK4 probe the SAME register cell cache as the final evaluation (NVEC == 1): the positions a line visits --
+// pos + h/2, pos + h/2, pos + h, nxt, then the next step's -- advance along the line, so the stages reload the cell where the Euler
+// form would and otherwise hit it.  0: the stages gather their eight corners directly (the alternative that was measured:
+// profiles/stream_rk/README.md).
+#ifndef FIB_RK_STAGE_CACHE
+#define FIB_RK_STAGE_CACHE 1
+#endif
+template <int NVEC, bool LCM = false, int TRI = 0, bool WIDE = false, bool FUSED = false>   // NVEC > 0: compile-time vector count; 0: runtime
 __global__ __launch_bounds__(FUSED ? FUSED_BLOCK : 256) void stream_trace_kernel(const TraceArgs a) {
     // FUSED: the workgroup's place in the line order is a TICKET, not blockIdx: whatever order workgroups are dispatched in, everything a
     // workgroup later waits for in the look-back (tickets below its own) was drawn by a workgroup that is already running
@@ -322,11 +331,111 @@ __global__ __launch_bounds__(FUSED ? FUSED_BLOCK : 256) void stream_trace_kernel
         vx = s.x * 1.0f; vy = s.y * 1.0f; vz = s.z * 1.0f;
     }
     // One trip of the loop = one step of whichever pass the lane is in.  true: the pass ended at this trip (stream.jl:657, :670, :674).
+    // D(q, r): the trilinear option's direction at position q against the reference direction r,
+    //   w = normalise( sum over the 8 corners c of floor(q) + {0,1}^3 inside the volume of  t_c * s_c * u_c ),
+    // t_c = (ax * ay) * az with a = frac or 1 - frac per axis, u_c = the corner's vector picked by the angle rule against r (corners
+    // without a vector contribute nothing), s_c = sign of its cosine; products and sums in Float32 in corner order x fastest, the norm
+    // as LinearAlgebra.norm does it (normalise3).  false: no direction (a zero or non-finite blend; a q that is not finite has no corner
+    // inside the volume).  The 8 x nvec float4 loads of a blend hit L2 / the vector cache (the stencil moves by half a voxel per step); an
+    // LDS copy per lane (128 B x nvec x 256 lanes) was not worth its LDS traffic.  [r5] CACHED (one vector per voxel): the cell's eight
+    // vectors are kept in REGISTERS between the blends that stay in it (trace 2.39 -> 1.82 ms).
+    auto blend = [&](auto cached, float qx, float qy, float qz, float rx, float ry, float rz, float &wx, float &wy, float &wz) -> bool {
+        const float gx0 = floorf(qx), gy0 = floorf(qy), gz0 = floorf(qz);
+        const float tx = qx - gx0, ty = qy - gy0, tz = qz - gz0;
+        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+        // per-axis validity of the low / high corner and the linear index of the low corner: no per-corner bounds test
+        const bool xl = gx0 >= 1.0f && gx0 <= fnx, xh = gx0 + 1.0f >= 1.0f && gx0 + 1.0f <= fnx;
+        const bool yl = gy0 >= 1.0f && gy0 <= fny, yh = gy0 + 1.0f >= 1.0f && gy0 + 1.0f <= fny;
+        const bool zl = gz0 >= 1.0f && gz0 <= fnz, zh = gz0 + 1.0f >= 1.0f && gz0 + 1.0f <= fnz;
+        const int64_t cbase = ((int64_t)gx0 - 1) + (int64_t)a.nx * (((int64_t)gy0 - 1) + (int64_t)a.ny * ((int64_t)gz0 - 1));
+        const float ax0 = 1.0f - tx, ay0 = 1.0f - ty, az0 = 1.0f - tz;
+        if constexpr (NVEC == 1 && decltype(cached)::value) {
+            // [r5] one vector per voxel: the eight corner vectors stay in registers while the position stays in the cell (a step is
+            // half a voxel: ~40 % of the steps do) -- the lanes that changed cell reload, corners outside the volume count as
+            // "no vector".  Same data, same arithmetic.
+            if (gx0 != tri_gx || gy0 != tri_gy || gz0 != tri_gz) {
+#pragma unroll
+                for (int c = 0; c < 8; c++) {
+                    const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
+                    float4 w = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if ((cx ? xh : xl) && (cy ? yh : yl) && (cz ? zh : zl)) {
+                        if constexpr (WIDE) w = *reinterpret_cast<const float4 *>(fbase + (uint64_t)(cbase + cx + (int64_t)a.nx * (cy + a.ny * cz)) * (uint64_t)16);
+                        else w = *reinterpret_cast<const float4 *>(fbase + (size_t)((uint32_t)((int)cbase + cx + a.nx * (cy + a.ny * cz)) * 16u));
+                    }
+                    tri_x[c] = w.x; tri_y[c] = w.y; tri_z[c] = w.z;
+                }
+                tri_gx = gx0; tri_gy = gy0; tri_gz = gz0;
+            }
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
+                const float ux = tri_x[c], uy = tri_y[c], uz = tri_z[c];
+                if (is_zero3(ux, uy, uz)) continue;           // (no vector there, or a corner outside the volume)
+                const float tc = ((cx ? tx : ax0) * (cy ? ty : ay0)) * (cz ? tz : az0);
+                const float uc = dot3(rx, ry, rz, ux, uy, uz);
+                if (!(fabsf(uc) < INFINITY)) continue;
+                const float sg = uc > 0.0f ? tc : -tc;
+                sx = sx + sg * ux; sy = sy + sg * uy; sz = sz + sg * uz;
+            }
+        } else
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
+            if (!((cx ? xh : xl) && (cy ? yh : yl) && (cz ? zh : zl))) continue;
+            const float tc = ((cx ? tx : ax0) * (cy ? ty : ay0)) * (cz ? tz : az0);
+            const float4 *cc;
+            if constexpr (WIDE) cc = reinterpret_cast<const float4 *>(fbase + (uint64_t)(cbase + cx + (int64_t)a.nx * (cy + a.ny * cz)) * (uint64_t)(nvec * 16));
+            else {
+                const uint32_t cv = (uint32_t)((int)cbase + cx + a.nx * (cy + a.ny * cz));
+                cc = reinterpret_cast<const float4 *>(fbase + (size_t)(cv * (uint32_t)(nvec * 16)));
+            }
+            float ux = 0.0f, uy = 0.0f, uz = 0.0f, uc = 0.0f, ua = 0.0f;
+#pragma unroll
+            for (int k = 0; k < nvec; k++) {
+                const float4 w = cc[k];
+                float cs, ca;
+                if (is_zero3(w.x, w.y, w.z)) { cs = -INFINITY; ca = -INFINITY; }
+                else { cs = dot3(rx, ry, rz, w.x, w.y, w.z); ca = fabsf(cs); }
+                if (k == 0 || __float_as_int(ca) > __float_as_int(ua)) { ua = ca; uc = cs; ux = w.x; uy = w.y; uz = w.z; }
+            }
+            if (!(fabsf(uc) < INFINITY)) continue;
+            const float sg = uc > 0.0f ? tc : -tc;
+            sx = sx + sg * ux; sy = sy + sg * uy; sz = sz + sg * uz;
+        }
+        const float m = fmaxf(fabsf(sx), fmaxf(fabsf(sy), fabsf(sz)));
+        if (m == 0.0f || !(m < INFINITY)) return false;
+        wx = sx; wy = sy; wz = sz;
+        normalise3(wx, wy, wz, a.norm_generic != 0);
+        return true;
+    };
+    constexpr std::integral_constant<bool, NVEC == 1> cell_cached{};                                   // the evaluation at the tentative position
+    constexpr std::integral_constant<bool, NVEC == 1 && FIB_RK_STAGE_CACHE != 0> stage_cached{};      // the stages of RK2 / RK4
+    const float h_half = a.step * 0.5f, h_sixth = a.step / 6.0f;  // (TRI >= 2; one IEEE division)
     bool emitted = false;
     auto step = [&]() -> bool {
         emitted = false;
         {
-            const float nxp = px + vx * a.step, nyp = py + vy * a.step, nzp = pz + vz * a.step;   // stream.jl:512
+            // the tentative position: stream.jl:512 (forward Euler), or -- TRI = 2, 3 -- the midpoint rule / classical Runge-Kutta on the
+            // blended field (include/fibers_hip.h).  k1 is the carried direction; every product and sum is rounded on its own, in the
+            // header's order; a stage without a direction ends the pass like an invalid position does (stream.jl:657): nothing is emitted.
+            float nxp, nyp, nzp;
+            if constexpr (TRI >= 2) {
+                float k2x, k2y, k2z;
+                if (!blend(stage_cached, px + vx * h_half, py + vy * h_half, pz + vz * h_half, vx, vy, vz, k2x, k2y, k2z)) return true;
+                if constexpr (TRI == 2) {
+                    nxp = px + k2x * a.step; nyp = py + k2y * a.step; nzp = pz + k2z * a.step;
+                } else {
+                    float k3x, k3y, k3z, k4x, k4y, k4z;
+                    if (!blend(stage_cached, px + k2x * h_half, py + k2y * h_half, pz + k2z * h_half, k2x, k2y, k2z, k3x, k3y, k3z)) return true;
+                    if (!blend(stage_cached, px + k3x * a.step, py + k3y * a.step, pz + k3z * a.step, k3x, k3y, k3z, k4x, k4y, k4z)) return true;
+                    const float smx = ((vx + 2.0f * k2x) + 2.0f * k3x) + k4x;
+                    const float smy = ((vy + 2.0f * k2y) + 2.0f * k3y) + k4y;
+                    const float smz = ((vz + 2.0f * k2z) + 2.0f * k3z) + k4z;
+                    nxp = px + smx * h_sixth; nyp = py + smy * h_sixth; nzp = pz + smz * h_sixth;
+                }
+            } else {
+                nxp = px + vx * a.step; nyp = py + vy * a.step; nzp = pz + vz * a.step;              // stream.jl:512
+            }
             const float rx = rintf(nxp), ry = rintf(nyp), rz = rintf(nzp);                        // stream.jl:514
             // x in axes(mask, 1) ... (:517) on the 0-based integers: one unsigned compare per axis (NaN -> 0 - 1, +-huge -> saturated: outside)
             const unsigned ux = (unsigned)cvt_i32_sat(rx) - 1u, uy = (unsigned)cvt_i32_sat(ry) - 1u, uz = (unsigned)cvt_i32_sat(rz) - 1u;   // (unsigned: no overflow to reason about)
@@ -370,82 +479,11 @@ __global__ __launch_bounds__(FUSED ? FUSED_BLOCK : 256) void stream_trace_kernel
             float wx, wy, wz;
             if (bestc > 0.0f) { wx = bx; wy = by; wz = bz; } else { wx = -bx; wy = -by; wz = -bz; }   // :365-369
             ivec = best;                                          // stream.jl:371
-            if (TRI) {
+            if constexpr (TRI != 0) {
                 // Trilinear option.  Everything above still decides whether the line goes on (bounds, the nearest voxel's pick must
-                // exist) and which vector index the backward pass starts from; the direction becomes
-                //   w = normalise( sum over the 8 corners c of floor(p') + {0,1}^3 inside the volume of  t_c * s_c * u_c ),
-                // t_c = (ax * ay) * az with a = frac or 1 - frac per axis, u_c = the corner's vector picked by the same angle rule
-                // against the current direction (corners without a vector contribute nothing), s_c = sign of its cosine; products
-                // and sums in Float32 in corner order x fastest, the norm as LinearAlgebra.norm does it (below).  A zero or
-                // non-finite blend ends the line.  The 8 x nvec float4 loads of a step hit L2 / the vector cache (the stencil moves
-                // by half a voxel per step); an LDS copy per lane (128 B x nvec x 256 lanes) was not worth its LDS traffic.  [r5] With one
-                // vector per voxel the cell's eight vectors are kept in REGISTERS between the steps that stay in it (trace 2.39 -> 1.82 ms).
-                const float gx0 = floorf(nxp), gy0 = floorf(nyp), gz0 = floorf(nzp);
-                const float tx = nxp - gx0, ty = nyp - gy0, tz = nzp - gz0;
-                float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-                // per-axis validity of the low / high corner and the linear index of the low corner: no per-corner bounds test
-                const bool xl = gx0 >= 1.0f && gx0 <= fnx, xh = gx0 + 1.0f >= 1.0f && gx0 + 1.0f <= fnx;
-                const bool yl = gy0 >= 1.0f && gy0 <= fny, yh = gy0 + 1.0f >= 1.0f && gy0 + 1.0f <= fny;
-                const bool zl = gz0 >= 1.0f && gz0 <= fnz, zh = gz0 + 1.0f >= 1.0f && gz0 + 1.0f <= fnz;
-                const int64_t cbase = ((int64_t)gx0 - 1) + (int64_t)a.nx * (((int64_t)gy0 - 1) + (int64_t)a.ny * ((int64_t)gz0 - 1));
-                const float ax0 = 1.0f - tx, ay0 = 1.0f - ty, az0 = 1.0f - tz;
-                if constexpr (NVEC == 1) {
-                    // [r5] one vector per voxel: the eight corner vectors stay in registers while the position stays in the cell (a step is
-                    // half a voxel: ~40 % of the steps do) -- the lanes that changed cell reload, corners outside the volume count as
-                    // "no vector".  Same data, same arithmetic.
-                    if (gx0 != tri_gx || gy0 != tri_gy || gz0 != tri_gz) {
-#pragma unroll
-                        for (int c = 0; c < 8; c++) {
-                            const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
-                            float4 w = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                            if ((cx ? xh : xl) && (cy ? yh : yl) && (cz ? zh : zl)) {
-                                if constexpr (WIDE) w = *reinterpret_cast<const float4 *>(fbase + (uint64_t)(cbase + cx + (int64_t)a.nx * (cy + a.ny * cz)) * (uint64_t)16);
-                                else w = *reinterpret_cast<const float4 *>(fbase + (size_t)((uint32_t)((int)cbase + cx + a.nx * (cy + a.ny * cz)) * 16u));
-                            }
-                            tri_x[c] = w.x; tri_y[c] = w.y; tri_z[c] = w.z;
-                        }
-                        tri_gx = gx0; tri_gy = gy0; tri_gz = gz0;
-                    }
-#pragma unroll
-                    for (int c = 0; c < 8; c++) {
-                        const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
-                        const float ux = tri_x[c], uy = tri_y[c], uz = tri_z[c];
-                        if (is_zero3(ux, uy, uz)) continue;           // (no vector there, or a corner outside the volume)
-                        const float tc = ((cx ? tx : ax0) * (cy ? ty : ay0)) * (cz ? tz : az0);
-                        const float uc = dot3(vx, vy, vz, ux, uy, uz);
-                        if (!(fabsf(uc) < INFINITY)) continue;
-                        const float sg = uc > 0.0f ? tc : -tc;
-                        sx = sx + sg * ux; sy = sy + sg * uy; sz = sz + sg * uz;
-                    }
-                } else
-#pragma unroll
-                for (int c = 0; c < 8; c++) {
-                    const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
-                    if (!((cx ? xh : xl) && (cy ? yh : yl) && (cz ? zh : zl))) continue;
-                    const float tc = ((cx ? tx : ax0) * (cy ? ty : ay0)) * (cz ? tz : az0);
-                    const float4 *cc;
-                    if constexpr (WIDE) cc = reinterpret_cast<const float4 *>(fbase + (uint64_t)(cbase + cx + (int64_t)a.nx * (cy + a.ny * cz)) * (uint64_t)(nvec * 16));
-                    else {
-                        const uint32_t cv = (uint32_t)((int)cbase + cx + a.nx * (cy + a.ny * cz));
-                        cc = reinterpret_cast<const float4 *>(fbase + (size_t)(cv * (uint32_t)(nvec * 16)));
-                    }
-                    float ux = 0.0f, uy = 0.0f, uz = 0.0f, uc = 0.0f, ua = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < nvec; k++) {
-                        const float4 w = cc[k];
-                        float cs, ca;
-                        if (is_zero3(w.x, w.y, w.z)) { cs = -INFINITY; ca = -INFINITY; }
-                        else { cs = dot3(vx, vy, vz, w.x, w.y, w.z); ca = fabsf(cs); }
-                        if (k == 0 || __float_as_int(ca) > __float_as_int(ua)) { ua = ca; uc = cs; ux = w.x; uy = w.y; uz = w.z; }
-                    }
-                    if (!(fabsf(uc) < INFINITY)) continue;
-                    const float sg = uc > 0.0f ? tc : -tc;
-                    sx = sx + sg * ux; sy = sy + sg * uy; sz = sz + sg * uz;
-                }
-                const float m = fmaxf(fabsf(sx), fmaxf(fabsf(sy), fabsf(sz)));
-                if (m == 0.0f || !(m < INFINITY)) return true;
-                wx = sx; wy = sy; wz = sz;
-                normalise3(wx, wy, wz, a.norm_generic != 0);
+                // exist) and which vector index the backward pass starts from; the direction becomes the blend at the tentative
+                // position against the current direction (`blend` above).  A zero or non-finite blend ends the line.
+                if (!blend(cell_cached, nxp, nyp, nzp, vx, vy, vz, wx, wy, wz)) return true;
             }
             bool isdiff = false;
             if (LCM) {
@@ -1376,7 +1414,8 @@ int check_args(const fib_stream_params *prm, const int64_t *seeds, int64_t nseed
     FIB_CHECK(nsub >= 1 && sublist, FIB_ERR_INVALID, "sublist must hold at least one offset (use [0,0,0] for nsub=0, stream.jl:180)");
     FIB_CHECK(prm->nx > 0 && prm->ny > 0 && prm->nz > 0 && prm->nvec >= 1 && prm->nvec <= 8, FIB_ERR_INVALID, "invalid volume / nvec");
     FIB_CHECK(prm->len_max >= 0 && prm->len_max < (1 << 24), FIB_ERR_INVALID, "invalid len_max");
-    FIB_CHECK(prm->interp == 0 || prm->interp == 1, FIB_ERR_INVALID, "interp must be 0 (nearest voxel, the reference) or 1 (trilinear)");
+    FIB_CHECK(prm->interp >= FIB_STREAM_NEAREST && prm->interp <= FIB_STREAM_TRILINEAR_RK4, FIB_ERR_INVALID,
+              "interp must be 0 (nearest voxel, the reference), 1 (trilinear), 2 (trilinear, RK2) or 3 (trilinear, RK4)");
     FIB_CHECK((int64_t)prm->nx * prm->ny * prm->nz < ((int64_t)1 << 40), FIB_ERR_UNSUPPORTED, "volumes of 2^40 voxels or more are not supported");
     return FIB_OK;
 }
@@ -1411,7 +1450,7 @@ PackArgs pack_args(const ScratchLayout &lay, const ScratchLayout::Regions &buf, 
 
 // the one-lane-per-line tracer for (LCM, TRI); the vector count is a compile-time constant for 1, 2 and 3 vectors per voxel, wide
 // fields take the run-time count (one instantiation per mode)
-template <bool LCM, bool TRI>
+template <bool LCM, int TRI>
 void launch_trace(const TraceArgs &ta, int nvec, bool wide, hipStream_t st) {
     const unsigned grid = (unsigned)fib::cdiv(ta.nlines, 256);
     if (wide)           hipLaunchKernelGGL((stream_trace_kernel<0, LCM, TRI, true>), dim3(grid), dim3(256), 0, st, ta);
@@ -1433,8 +1472,12 @@ void trace_and_scan(const TraceArgs &ta, const fib_stream_params *prm, bool wide
                     int64_t *counts_dev, hipStream_t st) {
     {
         fib::ProfScope prof("stream_trace", st);
-        if (prm->interp) launch_trace<false, true>(ta, prm->nvec, wide, st);
-        else launch_trace<false, false>(ta, prm->nvec, wide, st);
+        switch (prm->interp) {                                    // (check_args: 0 .. 3)
+        case FIB_STREAM_NEAREST:       launch_trace<false, 0>(ta, prm->nvec, wide, st); break;
+        case FIB_STREAM_TRILINEAR:     launch_trace<false, 1>(ta, prm->nvec, wide, st); break;
+        case FIB_STREAM_TRILINEAR_RK2: launch_trace<false, 2>(ta, prm->nvec, wide, st); break;
+        default:                       launch_trace<false, 3>(ta, prm->nvec, wide, st); break;
+        }
     }
     scan_lines(lay, buf, prm->len_min, counts_dev, st);
 }
@@ -1530,7 +1573,7 @@ int stream_trace_impl(const fib_stream_params *prm, const float *field4, const L
         job->lcm = true;
         {
             fib::ProfScope prof("stream_trace_lcm", st);
-            launch_trace<true, false>(ta, prm->nvec, wide, st);
+            launch_trace<true, 0>(ta, prm->nvec, wide, st);
         }
         scan_lines(job->lay, buf, prm->len_min, nullptr, st);
     } else {
@@ -1650,11 +1693,11 @@ extern "C" int fibd_stream_pack_trk_xfm(fib_stream_job *job, const float vox2vox
 // the fused trace + look-back + pack kernel for NVEC vectors per voxel (fibd_stream_run)
 template <int NVEC>
 static int launch_fused(const TraceArgs &ta, unsigned grid, size_t smem, hipStream_t st) {
-    if (smem > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(stream_trace_kernel<NVEC, false, false, false, true>),
+    if (smem > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(stream_trace_kernel<NVEC, false, 0, false, true>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
         return fib::fail(FIB_ERR_HIP, "hipFuncSetAttribute failed");
     fib::ProfScope prof("stream_trace", st);
-    hipLaunchKernelGGL((stream_trace_kernel<NVEC, false, false, false, true>), dim3(grid), dim3(FUSED_BLOCK), smem, st, ta);
+    hipLaunchKernelGGL((stream_trace_kernel<NVEC, false, 0, false, true>), dim3(grid), dim3(FUSED_BLOCK), smem, st, ta);
     return FIB_OK;
 }
 

@@ -112,17 +112,34 @@ def default_workspace(device: int) -> StreamWorkspace:
     return ws
 
 
-def _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist=0, search_ang=10, ws=None, interp="nearest",
-            search_flat_axis=0):
-    """search_dist > 0 selects the microscopy regime (stream.jl:83, 547-619); interp: "nearest" (the reference) or "trilinear"
-    (fib_stream_params.interp in include/fibers_hip.h); search_flat_axis 1..3: that axis is searched over one voxel only
-    (the through-plane axis of 2-D angle inputs, stream.jl:153-155)"""
+INTERP_NEAREST, INTERP_TRILINEAR, INTERP_TRILINEAR_RK2, INTERP_TRILINEAR_RK4 = 0, 1, 2, 3    # FIB_STREAM_* (include/fibers_hip.h)
+_INTEGRATORS = {"euler": INTERP_TRILINEAR, "rk2": INTERP_TRILINEAR_RK2, "rk4": INTERP_TRILINEAR_RK4}
+
+
+def _interp_code(interp, integrator):
+    """(interp, integrator) -> fib_stream_params.interp.  The integrators other than forward Euler sample the field between the
+    voxels, so they exist for the trilinear field only: a piecewise-constant field has nothing for the stages to sample."""
     if interp not in ("nearest", "trilinear"):
         raise ValueError("interp must be 'nearest' or 'trilinear'")
+    if integrator not in _INTEGRATORS:
+        raise ValueError("integrator must be 'euler', 'rk2' or 'rk4'")
+    if interp == "nearest":
+        if integrator != "euler":
+            raise ValueError("integrator=%r needs interp='trilinear' (the reference's nearest-voxel field is stepped by forward Euler)" % integrator)
+        return INTERP_NEAREST
+    return _INTEGRATORS[integrator]
+
+
+def _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist=0, search_ang=10, ws=None, interp="nearest",
+            search_flat_axis=0, integrator="euler"):
+    """search_dist > 0 selects the microscopy regime (stream.jl:83, 547-619); interp: "nearest" (the reference) or "trilinear",
+    integrator: "euler", or "rk2" / "rk4" on the trilinear field (fib_stream_params.interp in include/fibers_hip.h);
+    search_flat_axis 1..3: that axis is searched over one voxel only (the through-plane axis of 2-D angle inputs, stream.jl:153-155)"""
+    code = _interp_code(interp, integrator)
     nx, ny, nz = shape
     return _lib.StreamParams(nx, ny, nz, nvec, int(len_min), int(len_max if len_max is not None else max(shape)),
                              float(cosd32(ang_thresh)), float(np.float32(step_size)), float(np.float32(smooth_coeff)),
-                             int(search_dist), float(cosd32(search_ang)), ws._h if ws is not None else None, 1 if interp == "trilinear" else 0,
+                             int(search_dist), float(cosd32(search_ang)), ws._h if ws is not None else None, code,
                              int(search_flat_axis))
 
 
@@ -131,7 +148,7 @@ def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, f
            len_min: int = 3, len_max: Optional[int] = None, ang_thresh: Optional[float] = 45,
            step_size: Optional[float] = 0.5, smooth_coeff: Optional[float] = 0.2, lcms=None, lcm_thresh: float = 0.099,
            search_dist: int = 15, search_ang: float = 10, sublist=None, rng=None, rng_seed: int = 0,
-           device: int = 0, interp: str = "nearest") -> Tract:
+           device: int = 0, interp: str = "nearest", integrator: str = "euler") -> Tract:
     """Streamline tractography (stream.jl:730).  Returns a `Tract` whose lines are in the reference's order
     (seed voxels in column-major `findall` order, sub-voxel offsets innermost), points in 1-based voxel
     coordinates, each line ordered [forward reversed, backward] as stream.jl:652 builds it.
@@ -188,7 +205,7 @@ def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, f
         sptr = sarr.ctypes.data
     sub = make_sublist(nsub, rng) if sublist is None else np.ascontiguousarray(sublist, np.float32).reshape(-1, 3)
     prm = _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff,
-                  int(search_dist) if domicro else 0, search_ang, interp=interp,
+                  int(search_dist) if domicro else 0, search_ang, interp=interp, integrator=integrator,
                   search_flat_axis=flat_axis if domicro else 0)                 # micro_search_dist[thrudim] = 0 (stream.jl:153-155)
     ov = (C.c_void_p * nvec)(*[v.ctypes.data for v in vols])
     fv = None if fvols is None else (C.c_void_p * nvec)(*[v.ctypes.data for v in fvols])
@@ -295,7 +312,7 @@ def stream_field_device(ovec: List, f: Optional[List] = None, f_thresh: float = 
 
 
 def _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
-                   search_dist=0, search_ang=10):
+                   search_dist=0, search_ang=10, integrator="euler"):
     """the preamble of the device-resident tracer calls: checks field / seeds / sublist, resolves `workspace` ("default": the host
     mirror's arena for the field's device) and returns the fib_stream_params"""
     import torch
@@ -303,12 +320,13 @@ def _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, an
     _chk_dev(seeds, torch.int64, "seeds")
     _chk_dev(sublist, torch.float32, "sublist")
     ws = default_workspace(field.device.index or 0) if isinstance(workspace, str) else workspace
-    return _params(shape, field.shape[1], len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist, search_ang, ws, interp)
+    return _params(shape, field.shape[1], len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist, search_ang, ws, interp,
+                   integrator=integrator)
 
 
 def stream_device(field, shape, seeds, sublist, len_min=3, len_max=None, ang_thresh=45, step_size=0.5,
                   smooth_coeff=0.2, stream=None, want_all_npts=False, search_dist=0, search_ang=10,
-                  lcms=None, lcm_thresh=0.099, strdims=(0, 1), rng_seed=0, xyz_out=None, workspace="default", interp="nearest"):
+                  lcms=None, lcm_thresh=0.099, strdims=(0, 1), rng_seed=0, xyz_out=None, workspace="default", interp="nearest", integrator="euler"):
     """Trace + pack on the GPU.  field: [nvox, nvec, 4] from stream_field_device; seeds: int64 CUDA tensor of
     0-based column-major voxel indices (findall order); sublist: float32 CUDA [nsub, 3].
     search_dist > 0: microscopy regime (stream.jl:547-619; reference defaults there: search_dist 15, search_ang 10,
@@ -321,7 +339,7 @@ def stream_device(field, shape, seeds, sublist, len_min=3, len_max=None, ang_thr
     Returns dict(npts int32 [nlines], seed_index int64 [nlines], xyz float32 [npoints, 3])."""
     import torch
     prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
-                         search_dist, search_ang)
+                         search_dist, search_ang, integrator=integrator)
     job = C.c_void_p()
     nl, npnt = C.c_int64(0), C.c_int64(0)
     L = _lib.lib()
@@ -374,13 +392,14 @@ class StreamBuffers:
 
 
 def stream_device_run(field, shape, seeds, sublist, buffers: StreamBuffers = None, len_min=3, len_max=None, ang_thresh=45, step_size=0.5,
-                      smooth_coeff=0.2, stream=None, workspace="default", interp="nearest"):
+                      smooth_coeff=0.2, stream=None, workspace="default", interp="nearest", integrator="euler"):
     """stream_device in ONE library call (fibd_stream_run): trace, scan and pack without a host round trip in between -- from 2^21
     lines on (nearest-voxel tracking, 1, 2 or 3 vectors per voxel) as ONE kernel in which the workgroup that traced 512 lines packs them
     behind a decoupled look-back; results go straight into `buffers` (grown and the call repeated when they are too small: a first
     call sizes them).  Same lines, order and layout as stream_device; macro-scale angle picking only.
     Returns dict(npts, seed_index, xyz) -- views of the buffers, valid until the next call with them."""
-    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp)
+    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                         integrator=integrator)
     nl_max = int(seeds.numel()) * int(sublist.shape[0])
     if buffers is None:
         buffers = StreamBuffers(field.device)
@@ -402,13 +421,14 @@ def stream_device_run(field, shape, seeds, sublist, buffers: StreamBuffers = Non
 
 
 def stream_device_run_enqueue(field, shape, seeds, sublist, buffers: StreamBuffers, counts=None, len_min=3, len_max=None, ang_thresh=45,
-                              step_size=0.5, smooth_coeff=0.2, stream=None, workspace="default", interp="nearest"):
+                              step_size=0.5, smooth_coeff=0.2, stream=None, workspace="default", interp="nearest", integrator="euler"):
     """stream_device_run without the host round trip at its end (fibd_stream_run_enqueue): returns as soon as the work is enqueued.
     `buffers` must already be large enough (a stream_device_run call sizes them); `counts` (int64 CUDA tensor of 2 elements, made if
     None) receives {lines, points} from the stream -- read it after synchronising; values above the buffers' capacities mean that
     lines were dropped for lack of room.  Returns (buffers, counts)."""
     import torch
-    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp)
+    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                         integrator=integrator)
     if buffers is None or buffers.npts is None or buffers.npts.numel() == 0:
         raise ValueError("stream_device_run_enqueue needs sized buffers (call stream_device_run once)")
     if counts is None:

@@ -192,7 +192,8 @@ def stream_to_trk(outfile, field, shape, seeds, sublist, ref: MRI, stream=None, 
     from .dti import _stream_ptr, _sync
     nvec = field.shape[1]
     prm = _params(shape, nvec, kw.get("len_min", 3), kw.get("len_max"), kw.get("ang_thresh", 45),
-                  kw.get("step_size", 0.5), kw.get("smooth_coeff", 0.2), ws=default_workspace(field.device.index or 0))
+                  kw.get("step_size", 0.5), kw.get("smooth_coeff", 0.2), ws=default_workspace(field.device.index or 0),
+                  interp=kw.get("interp", "nearest"), integrator=kw.get("integrator", "euler"))
     job = C.c_void_p()
     nl, npnt = C.c_int64(0), C.c_int64(0)
     L = _lib.lib()

@@ -264,7 +264,27 @@ typedef struct {
      * blend of the 8 voxels around the tentative position: w = normalise(sum_c t_c s_c u_c), t_c the trilinear weight of corner c
      * (corners outside the volume dropped), u_c the corner's vector picked by the angle rule of stream.jl:340-374 against the
      * current direction (corners without a vector dropped), s_c the sign of its cosine; a zero blend ends the line.  Bounds,
-     * mask and the nearest voxel's pick still decide termination exactly as in the reference; macro scale, angle picking only. */
+     * mask and the nearest voxel's pick still decide termination exactly as in the reference; macro scale, angle picking only.
+     *
+     * 2, 3: the same trilinear field with a midpoint (RK2) / classical Runge-Kutta (RK4) integrator instead of forward Euler (NOT in
+     * the reference either; the FIB_STREAM_* constants below).  Let D(p, r) be the blend above: the direction at position p, corners
+     * picked and sign-aligned against the reference direction r, normalised; NONE when the blend is zero or not finite or p is not
+     * finite.  A step of the trilinear tracker at state (pos, vec) is
+     *     nxt = pos + vec * step ; bounds / mask / nearest-voxel pick at nxt (ends the pass, sets the carried vector index) ;
+     *     vnext = D(nxt, vec) (NONE ends the pass) ; emit pos ; bend test dot(vec, vnext) ; len_max ; smoothing ; advance
+     * and the integrator changes ONLY how nxt is obtained from (pos, vec) -- vnext and the bend test stay taken against vec.
+     * With h = step, half = step * 0.5f, sixth = step / 6.0f (one IEEE division), all Float32, every multiply and add rounded on
+     * its own (no fused multiply-add), component-wise:
+     *     1 Euler:    nxt = pos + vec * h
+     *     2 midpoint: k2 = D(pos + vec * half, vec) ;  nxt = pos + k2 * h
+     *     3 RK4:      k2 = D(pos + vec * half, vec) ;  k3 = D(pos + k2 * half, k2) ;  k4 = D(pos + k3 * h, k3) ;
+     *                 s = ((vec + 2 * k2) + 2 * k3) + k4 ;  nxt = pos + s * sixth          (the sum is not renormalised)
+     * A stage whose D is NONE ends the pass exactly like an invalid nxt does (stream.jl:657): pos is not emitted.  Stage positions
+     * are not tested against bounds or mask by themselves: corners outside the volume and masked voxels contribute nothing to D,
+     * and an empty blend is NONE.  k1 is the CARRIED direction vec -- with smooth_coeff > 0 that is the smoothed direction, not a
+     * fresh sample of the field at pos, which costs RK4 some of its accuracy (CPU restatement, circles of radius 9-16 voxels,
+     * step 0.5: drift <= 0.002 voxel without smoothing, 0.06-0.12 with smooth_coeff 0.2; midpoint <= 0.002 either way; Euler
+     * 0.8-1.3 and 1.1-1.9).  Values 1, 2, 3 with the microscopy regime or LCMs: FIB_ERR_UNSUPPORTED. */
     int32_t interp;
     /* microscopy regime with 2-D orientation-angle inputs (one frame per volume, stream.jl:147-172): StreamWork sets the search
      * distance of the through-plane axis -- the one with the largest voxel size -- to 0 (stream.jl:153-155).  0: none (a cubic
@@ -272,6 +292,12 @@ typedef struct {
      * vectors by the host-language wrapper, cos / sin or cosd / sind like the constructor does: ovec stays [nvox*3].) */
     int32_t search_flat_axis;
 } fib_stream_params;
+
+/* values of fib_stream_params.interp */
+#define FIB_STREAM_NEAREST 0        /* nearest voxel, forward Euler: the reference (stream.jl:512-520) */
+#define FIB_STREAM_TRILINEAR 1      /* trilinear blend, forward Euler */
+#define FIB_STREAM_TRILINEAR_RK2 2  /* trilinear blend, midpoint rule */
+#define FIB_STREAM_TRILINEAR_RK4 3  /* trilinear blend, classical Runge-Kutta */
 
 typedef struct fib_stream_job fib_stream_job;
 /* Grow-only scratch arena of the tracer, owned by the caller (the reference's per-thread StreamWork scratch, stream.jl:43-60):

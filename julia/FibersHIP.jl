@@ -19,6 +19,11 @@ const FIB_MASK_OUTPUTS_ZEROED = Cint(0x100)
 # as Threads.@threads shards the z loop in dti.jl:258 / gqi.jl:132 / dsi.jl:197; round-robin seeds for stream).  Without
 # fib_init the set is every visible GPU.  Results do not depend on the set.
 const FIB_DEVICE_ALL = Cint(-1)
+# values of fib_stream_params.interp: the reference's nearest-voxel Euler tracker; the trilinear field stepped by Euler, midpoint, RK4
+const FIB_STREAM_NEAREST = Int32(0)
+const FIB_STREAM_TRILINEAR = Int32(1)
+const FIB_STREAM_TRILINEAR_RK2 = Int32(2)
+const FIB_STREAM_TRILINEAR_RK4 = Int32(3)
 fib_init(devs::Vector{<:Integer}=Int[]) = fib_check(ccall((:fib_init, libfibers), Cint, (Cint, Ptr{Cint}), length(devs), Cint.(devs)))
 fib_trim() = ccall((:fib_trim, libfibers), Cint, ())          # buffers kept between calls go back to the driver (plans stay)
 fib_shutdown() = ccall((:fib_shutdown, libfibers), Cvoid, ())
@@ -200,7 +205,7 @@ struct FibStreamParams
   cosang_thresh::Float32; step_size::Float32; smooth_coeff::Float32
   search_dist::Int32; search_cosang::Float32          # microscopy regime (stream.jl:83, 547-619) when search_dist > 0
   ws::Ptr{Cvoid}                                      # optional tracer workspace (fibd_stream_ws_create); C_NULL for the host-buffer calls
-  interp::Int32                                       # 0: nearest voxel (stream.jl:514); 1: trilinear blend (not in the reference)
+  interp::Int32                                       # FIB_STREAM_*: 0 nearest voxel (stream.jl:514); 1 trilinear blend, 2 / 3 the same stepped by RK2 / RK4 (not in the reference)
   search_flat_axis::Int32                             # microscopy regime + 2-D angle inputs: 1..3 = the through-plane axis (search distance 0, stream.jl:153-155); 0: none
 end
 
@@ -219,9 +224,15 @@ function stream(ovec::Union{MRI,Vector{MRI}}; f::Union{MRI,Vector{MRI},Nothing}=
                 ang_thresh::Union{Real,Nothing}=45, step_size::Union{Real,Nothing}=.5,
                 smooth_coeff::Union{Real,Nothing}=.2, search_dist::Integer=15, search_ang::Real=10,
                 lcms::Union{MRI,Nothing}=nothing, lcm_thresh::Real=.099, rng_seed::Integer=rand(UInt64),
-                device::Integer=0)
+                device::Integer=0, interp::Symbol=:nearest, integrator::Symbol=:euler)
   ovecs = isa(ovec, MRI) ? MRI[ovec] : ovec
   fs    = isa(f, MRI) ? MRI[f] : f
+  # interp = :trilinear and integrator = :rk2 | :rk4 are NOT in the reference (fib_stream_params.interp in include/fibers_hip.h)
+  interp in (:nearest, :trilinear) || error("interp must be :nearest or :trilinear")
+  integrator in (:euler, :rk2, :rk4) || error("integrator must be :euler, :rk2 or :rk4")
+  interp == :nearest && integrator != :euler && error("integrator $(integrator) needs interp = :trilinear")
+  interp_code = interp == :nearest ? FIB_STREAM_NEAREST :
+                integrator == :euler ? FIB_STREAM_TRILINEAR : integrator == :rk2 ? FIB_STREAM_TRILINEAR_RK2 : FIB_STREAM_TRILINEAR_RK4
   nx, ny, nz = size(ovecs[1].vol)[1:3]
   # 2-D orientation angles (one frame) become 3-D vectors here, with the reference's own arithmetic (stream.jl:147-172):
   # through-plane = the dimension with the largest voxel size, cos / sin (radians) or cosd / sind (degrees) in the other two
@@ -255,7 +266,7 @@ function stream(ovec::Union{MRI,Vector{MRI}}; f::Union{MRI,Vector{MRI},Nothing}=
   sublist = nsub > 0 ? hcat([Float32.(rand(Uniform(-.5+eps(), .5-eps()), 3)) for _ in 1:nsub]...) : zeros(Float32, 3, 1)
   prm = Ref(FibStreamParams(nx, ny, nz, length(ovecs), len_min, len_max,
                             cosd(Float32(ang_thresh)), Float32(step_size), Float32(smooth_coeff),
-                            domicro ? Int32(search_dist) : Int32(0), cosd(Float32(search_ang)), C_NULL, Int32(0),
+                            domicro ? Int32(search_dist) : Int32(0), cosd(Float32(search_ang)), C_NULL, interp_code,
                             domicro ? flat_axis : Int32(0)))                   # micro_search_dist[thrudim] = 0, stream.jl:153-155
   pv = [pointer(o.vol) for o in ovecs]
   pf = isnothing(fs) ? C_NULL : [pointer(x.vol) for x in fs]
