@@ -19,3 +19,5 @@ from .nifti import (dsi_write, dti_write, gqi_write, load_nifti, mri_read, mri_r
                     read_struct)
 from .trk import str_add, stream_to_trk, tract_header, trk_read, trk_write  # noqa: F401
 from .xform import Xform, str_merge, str_xform, xfm_apply, xfm_compose, xfm_inv, xfm_read, xfm_rotate  # noqa: F401
+from .tractmap import (str_density, str_density_device, str_sample, str_sample_device, str_stats, str_stats_device,  # noqa: F401
+                       str_work_size)

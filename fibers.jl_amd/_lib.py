@@ -8,6 +8,8 @@ LIB_PATH = os.environ.get("FIBERS_HIP_LIB") or os.path.join(_HERE, "libfibers_hi
 
 FIB_OK = 0
 FIB_ERR_CAPACITY = -9
+FIB_DENSITY_ACCUMULATE = 0x100      # OR-ed into the mode of fib(d)_str_density: add to what the map holds
+DENSITY_MODES = {"points": 0, "lines": 1, "endpoints": 2}
 FIB_MASK_OUTPUTS_ZEROED = 0x100     # OR-ed into mask_dtype: the output arrays are freshly zero-allocated (include/fibers_hip.h)
 DTYPES = {"uint8": 0, "int8": 1, "int16": 2, "uint16": 3, "int32": 4, "uint32": 5,
           "float32": 6, "float64": 7, "int64": 8, "bool": 9}
@@ -94,6 +96,13 @@ _PROTOS = {
     "fibd_stream_pack_trk_xfm": (i32, [vp, C.POINTER(C.c_float * 16), C.POINTER(C.c_float * 3), vp, vp]),
     "fibd_xfm_apply": (i32, [C.POINTER(C.c_float * 16), vp, vp, i64, vp]),
     "fib_xfm_apply": (i32, [i32, C.POINTER(C.c_float * 16), vp, vp, i64]),
+    "fibd_str_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
+    "fibd_str_density": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_str_sample": (i32, [vp, i64, vp, i32, i32, i32, i32, f32, vp, vp]),
+    "fibd_str_stats": (i32, [vp, vp, i64, i64, C.POINTER(C.c_float * 3), vp, i32, vp, vp, C.c_uint64, vp]),
+    "fib_str_density": (i32, [i32, vp, vp, i64, i64, i32, i32, i32, i32, vp, C.POINTER(i64)]),
+    "fib_str_sample": (i32, [i32, vp, i64, vp, i32, i32, i32, i32, f32, vp]),
+    "fib_str_stats": (i32, [i32, vp, vp, i64, i64, C.POINTER(C.c_float * 3), vp, i32, vp]),
     "fibd_stream_trace_lcm": (i32, [C.POINTER(StreamParams), vp, vp, f32, i32, i32, C.c_uint64, vp, i64, vp, i32, vp,
                                     C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]),
     "fibd_stream_pack_flags": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -171,7 +180,7 @@ def shutdown():
 
 def trim():
     """fib_trim: the host tier's buffers kept between calls (pinned ring, its device mirror, fib_stream's device buffers, the tracer's
-    workspace) go back to the driver; plans stay"""
+    workspace, the tract maps' device buffers) go back to the driver; plans stay"""
     check(lib().fib_trim())
 
 

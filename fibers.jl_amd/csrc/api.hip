@@ -149,6 +149,15 @@ struct DevState {
         fib::DevBuf<int64_t> seeds, sidx;
         fib::DevBuf<int32_t> npts;
     } sb;
+    // device buffers of fib_str_density / fib_str_sample / fib_str_stats (grow-only): one chunk of points and what belongs to it, the
+    // resident volume (density map or sampled volume), the offset scratch
+    struct TractMapBufs {
+        fib::DevBuf<float> xyz, vol, scal, props;
+        fib::DevBuf<int32_t> npts;
+        fib::DevBuf<uint32_t> dens;
+        fib::DevBuf<char> work;
+        fib::DevBuf<int64_t> nout;
+    } tm;
 
     int init(int nthreads) {
         if (ready) return FIB_OK;
@@ -177,6 +186,8 @@ struct DevState {
         for (int b = 0; b < NBUF; b++) { pin_in[b].release(); pin_out[b].release(); dev_in[b].release(); dev_out[b].release(); }
         sb.vec.release(); sb.f.release(); sb.fa.release(); sb.field.release(); sb.sub.release(); sb.lcms.release(); sb.xyz.release();
         sb.mask.release(); sb.mout.release(); sb.flags.release(); sb.seeds.release(); sb.sidx.release(); sb.npts.release();
+        tm.xyz.release(); tm.vol.release(); tm.scal.release(); tm.props.release(); tm.npts.release(); tm.dens.release(); tm.work.release();
+        tm.nout.release();
         if (ws) { fibd_stream_ws_destroy(ws); ws = nullptr; }
     }
     void drop_plans() {
@@ -549,6 +560,146 @@ extern "C" int fib_st_recon(int device, const float *vol, int nx, int ny, int nz
         FIB_HIP(hipDeviceSynchronize());
         for (int k = 0; k < 9; k++) RC(d2h(eigvec + k * nvox + plane * z0, d_out.p + k * nout, sizeof(float) * nout));
         for (int k = 0; k < 3; k++) RC(d2h(eigval + k * nvox + plane * z0, d_out.p + (9 + k) * nout, sizeof(float) * nout));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// tract maps: host forms.  One device; the points travel in chunks cut at line boundaries, the volume stays on the device.
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int64_t TM_CHUNK_POINTS = (int64_t)1 << 22;      // 48 MB of points per chunk (a longer line is a chunk of its own)
+
+// npts >= 0 and sum(npts) == npoints, before anything is written
+int tm_host_check(const int32_t *npts, int64_t nlines, int64_t npoints) {
+    FIB_CHECK(nlines >= 0 && npoints >= 0, FIB_ERR_INVALID, "nlines and npoints must not be negative");
+    FIB_CHECK(nlines == 0 || npts, FIB_ERR_INVALID, "NULL npts");
+    int64_t sum = 0;
+    for (int64_t l = 0; l < nlines; l++) {
+        FIB_CHECK(npts[l] >= 0, FIB_ERR_INVALID, "line %lld has a negative point count", (long long)l);
+        sum += npts[l];
+    }
+    FIB_CHECK(sum == npoints, FIB_ERR_INVALID, "the point counts sum to %lld, not to npoints = %lld", (long long)sum, (long long)npoints);
+    return FIB_OK;
+}
+
+// lines [l0, *l1) with at most TM_CHUNK_POINTS points (at least one line), *np their points
+void tm_next_chunk(const int32_t *npts, int64_t nlines, int64_t l0, int64_t *l1, int64_t *np) {
+    int64_t l = l0, n = 0;
+    while (l < nlines && (l == l0 || n + npts[l] <= TM_CHUNK_POINTS)) n += npts[l++];
+    *l1 = l; *np = n;
+}
+
+int tm_worker(int device, Worker &w) {
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "the tract maps run on one device (FIB_DEVICE_ALL is not supported)");
+    std::vector<Worker> ws;
+    RC(workers_for(device, ws));
+    w = ws[0];
+    return FIB_OK;
+}
+}  // namespace
+
+extern "C" int fib_str_density(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
+                               int mode, uint32_t *density, int64_t *n_outside) try {
+    FIB_CHECK(density && n_outside, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
+    const int what = mode & ~FIB_DENSITY_ACCUMULATE;
+    FIB_CHECK(what >= FIB_DENSITY_POINTS && what <= FIB_DENSITY_ENDPOINTS, FIB_ERR_INVALID, "unknown density mode %d", mode);
+    RC(tm_host_check(npts, nlines, npoints));
+    FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    const size_t nvox = (size_t)nx * ny * nz;
+    RC(b.dens.ensure(nvox));
+    RC(b.nout.ensure(1));
+    if (mode & FIB_DENSITY_ACCUMULATE) RC(h2d(b.dens.p, density, sizeof(uint32_t) * nvox));
+    else FIB_HIP(hipMemset(b.dens.p, 0, sizeof(uint32_t) * nvox));
+    int64_t total_out = 0;
+    int64_t p0 = 0;
+    for (int64_t l0 = 0; l0 < nlines;) {
+        int64_t l1, np;
+        tm_next_chunk(npts, nlines, l0, &l1, &np);
+        size_t wb = 0;
+        RC(fibd_str_work_size(l1 - l0, &wb));
+        RC(b.work.ensure(wb));
+        RC(b.npts.ensure((size_t)(l1 - l0)));
+        RC(b.xyz.ensure((size_t)3 * np));
+        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * (size_t)(l1 - l0)));
+        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(fibd_str_density(b.xyz.p, b.npts.p, l1 - l0, np, nx, ny, nz, what | FIB_DENSITY_ACCUMULATE, b.dens.p, b.nout.p, b.work.p, wb, nullptr));
+        int64_t out = 0;
+        RC(d2h(&out, b.nout.p, sizeof out));                   // (a blocking copy on the NULL stream: behind the kernels)
+        FIB_CHECK(out >= 0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
+        total_out += out;
+        p0 += np; l0 = l1;
+    }
+    RC(d2h(density, b.dens.p, sizeof(uint32_t) * nvox));
+    *n_outside = total_out;
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_str_sample(int device, const float *xyz, int64_t npoints, const float *vol, int nx, int ny, int nz, int nframes, float outside,
+                              float *scalars) try {
+    FIB_CHECK(npoints >= 0, FIB_ERR_INVALID, "npoints must not be negative");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
+    FIB_CHECK(npoints == 0 || (xyz && vol && scalars), FIB_ERR_INVALID, "NULL argument");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    if (npoints == 0) return FIB_OK;
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    const size_t nvox = (size_t)nx * ny * nz;
+    RC(b.vol.ensure(nvox * nframes));
+    RC(h2d(b.vol.p, vol, sizeof(float) * nvox * nframes));
+    const int64_t chunk = std::max<int64_t>(1, TM_CHUNK_POINTS / std::max(1, nframes / 3));
+    RC(b.xyz.ensure((size_t)3 * std::min(chunk, npoints)));
+    RC(b.scal.ensure((size_t)nframes * std::min(chunk, npoints)));
+    for (int64_t p0 = 0; p0 < npoints; p0 += chunk) {
+        const int64_t np = std::min(chunk, npoints - p0);
+        RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(fibd_str_sample(b.xyz.p, np, b.vol.p, nx, ny, nz, nframes, outside, b.scal.p, nullptr));
+        RC(d2h(scalars + p0 * nframes, b.scal.p, sizeof(float) * (size_t)nframes * np));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_str_stats(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const float volres[3],
+                             const float *scalars, int nscalars, float *props) try {
+    FIB_CHECK(volres, FIB_ERR_INVALID, "NULL volres");
+    FIB_CHECK(nscalars >= 0, FIB_ERR_INVALID, "nscalars must not be negative");
+    RC(tm_host_check(npts, nlines, npoints));
+    FIB_CHECK(npoints == 0 || (xyz && (nscalars == 0 || scalars)), FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nlines == 0 || props, FIB_ERR_INVALID, "NULL props");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    const int ncol = 1 + nscalars;
+    int64_t p0 = 0;
+    for (int64_t l0 = 0; l0 < nlines;) {
+        int64_t l1, np;
+        tm_next_chunk(npts, nlines, l0, &l1, &np);
+        size_t wb = 0;
+        RC(fibd_str_work_size(l1 - l0, &wb));
+        RC(b.work.ensure(wb));
+        RC(b.npts.ensure((size_t)(l1 - l0)));
+        RC(b.xyz.ensure((size_t)3 * np));
+        RC(b.scal.ensure((size_t)nscalars * np));
+        RC(b.props.ensure((size_t)ncol * (l1 - l0)));
+        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * (size_t)(l1 - l0)));
+        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        if (np && nscalars) RC(h2d(b.scal.p, scalars + p0 * nscalars, sizeof(float) * (size_t)nscalars * np));
+        RC(fibd_str_stats(b.xyz.p, b.npts.p, l1 - l0, np, volres, b.scal.p, nscalars, b.props.p, b.work.p, wb, nullptr));
+        RC(d2h(props + l0 * ncol, b.props.p, sizeof(float) * (size_t)ncol * (l1 - l0)));
+        p0 += np; l0 = l1;
     }
     return FIB_OK;
 } FIB_API_CATCH

@@ -383,6 +383,65 @@ int fibd_stream_all_npts(fib_stream_job *job, int32_t *all_npts, void *stream);
 void fib_stream_job_destroy(fib_stream_job *job);
 
 /* ------------------------------------------------------------------------------------ */
+/* Tract maps: density, along-tract sampling, line statistics (NOT in the reference)     */
+/* ------------------------------------------------------------------------------------ */
+/* Inputs are PACKED LINES as fibd_stream_run / fibd_stream_pack emit them and `Tract` holds them: xyz float32 [npoints][3] (x, y, z
+ * of a point adjacent, 1-based voxel coordinates), npts int32 [nlines], lines one after the other.  Points need only be 4-byte
+ * aligned (views into a larger buffer), as for fibd_xfm_apply.  These definitions are this project's own; they are the contract.
+ *
+ * VOXEL OF A POINT.  v = rint(p) per component, ties to even (the tracer's rule, stream.jl:514).  The point is INSIDE iff all three
+ * components are finite and 1 <= v_x <= nx, 1 <= v_y <= ny, 1 <= v_z <= nz, tested on the float value before any conversion to an
+ * integer (+-1e30, +-Inf and NaN are simply outside).  Linear index lin(v) = (v_x-1) + nx*((v_y-1) + ny*(v_z-1)), 64-bit.
+ *
+ * DENSITY D, uint32 [nx*ny*nz]; `mode` is one of
+ *   FIB_DENSITY_POINTS     D[v] = number of inside points with voxel v;
+ *   FIB_DENSITY_LINES      D[v] = number of lines that have AT LEAST ONE inside point with voxel v: a line counts once per voxel
+ *                          however often it samples it or comes back to it (track density).  Exact for lines of any length (lines of
+ *                          up to 256 points are de-duplicated in LDS, longer ones through a bitmap over the voxels they span);
+ *                          volumes of 2^31 voxels or more: FIB_ERR_UNSUPPORTED in this mode;
+ *   FIB_DENSITY_ENDPOINTS  for every line with npts >= 1, +1 at the voxel of its first point and +1 at the voxel of its last point
+ *                          (a one-point line adds 2 to one voxel), each only if inside;
+ * optionally OR-ed with
+ *   FIB_DENSITY_ACCUMULATE add to what D holds; without it the call zero-fills D first.  Tractograms that arrive in batches sum into
+ *                          one map, and integer sums make the result independent of batch and arrival order (two runs: same bytes).
+ * n_outside (int64): the number of points (POINTS, LINES) or line ends (ENDPOINTS) that were not inside, so that
+ * sum(D) + n_outside = npoints in mode POINTS and = 2 * #{npts >= 1} in mode ENDPOINTS (on a zero-filled D).  Counts wrap at 2^32.
+ * Lines with npts = 0 are legal and contribute nothing.  npts < 0 or sum(npts) != npoints is FIB_ERR_INVALID: the host form checks
+ * before anything is written; the device form cannot without a host round trip -- its offset scan sees both, the kernels behind it
+ * then add nothing and *n_outside_dev is set to -1 (D is zero-filled, or with ACCUMULATE left as it was; never partly counted).
+ *
+ * SAMPLE S, float32 [npoints][nframes] (point-major, the order of .trk records and Tract.scalars): S[i][f] = vol[f][lin(v_i)] if
+ * point i is inside, else `outside` (NaN allowed).  vol planar float32 [nframes][nvox] = MRI.vol.  Nearest voxel only.
+ *
+ * LINE STATISTICS P, float32 [nlines][1 + nscalars] (line-major, Tract.properties):
+ *   column 0       length in mm: the sum over the line's consecutive point pairs of
+ *                  sqrt(((x1-x0)*r_x)*((x1-x0)*r_x) + ((y1-y0)*r_y)*((y1-y0)*r_y) + ((z1-z0)*r_z)*((z1-z0)*r_z)), every operation in
+ *                  float64 on the float32 inputs (r = volres as float32), the three squares added left to right, no fused
+ *                  multiply-add, the sum rounded to float32 once.  0 for npts <= 1.
+ *   column 1 + c   the mean of column c of the per-point scalars [npoints][nscalars] over the line's points: float64 sum, divided by
+ *                  npts in float64, rounded once.  NaN samples propagate; npts = 0 gives NaN (0/0).
+ * The ORDER of either sum is free (lanes reduce a line in parallel): an n-term float64 sum in any order differs from the sequential
+ * one by at most n * 2^-53 * sum|t_i|, and rounding to float32 moves either by at most one float32 ulp.  The device form writes no
+ * row at all for an input its offset scan refuses (npts < 0, sum(npts) != npoints). */
+#define FIB_DENSITY_POINTS 0
+#define FIB_DENSITY_LINES 1
+#define FIB_DENSITY_ENDPOINTS 2
+#define FIB_DENSITY_ACCUMULATE 0x100
+/* bytes of device scratch fibd_str_density / fibd_str_stats need for nlines lines (the int64 offset of every line's first point and the
+ * scan's block totals); 8-byte aligned */
+int fibd_str_work_size(int64_t nlines, size_t *bytes);
+/* density: xyz, npts, density, n_outside_dev (one int64) and work are device pointers.  Asynchronous on `stream`, no allocation and no
+ * synchronisation inside.  Adds are vector atomics on uint32, one per run of consecutive points in the same voxel. */
+int fibd_str_density(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz, int mode,
+                     uint32_t *density, int64_t *n_outside_dev, void *work, size_t work_bytes, void *stream);
+/* sample: one pass over the points.  nlines is not needed (a sample belongs to a point).  npoints = 0 does nothing. */
+int fibd_str_sample(const float *xyz, int64_t npoints, const float *vol, int nx, int ny, int nz, int nframes, float outside,
+                    float *scalars, void *stream);
+/* statistics: scalars may be NULL when nscalars = 0 (props is then [nlines][1]: the lengths) */
+int fibd_str_stats(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const float volres[3], const float *scalars,
+                   int nscalars, float *props, void *work, size_t work_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Host-buffer drop-in entry points (what the Julia wrapper ccalls)                       */
 /* ------------------------------------------------------------------------------------ */
 
@@ -398,8 +457,9 @@ void fib_stream_job_destroy(fib_stream_job *job);
  * the default of FIB_DEVICE_ALL without fib_init).  fib_shutdown releases every cached plan, stream and buffer.
  * What a worker KEEPS between calls (grow-only, so that the next call of the same size allocates nothing): its pinned staging ring and the
  * ring's device mirror (3 x (rows in + rows out) x chunk x 4 bytes each: ~1.9 GB of host and of device memory after fib_gqi_rec on 270
- * frames), the device buffers of fib_stream (orientation field, seeds, and the packed result: 1.5 GB after 129 M points) and the tracer's
- * workspace (scratch for every line in flight).  A process that shares the GPU with other users of its memory calls fib_trim() when it
+ * frames), the device buffers of fib_stream (orientation field, seeds, and the packed result: 1.5 GB after 129 M points), the tracer's
+ * workspace (scratch for every line in flight) and the device buffers of fib_str_density / fib_str_sample / fib_str_stats (one chunk of
+ * points with its counts, samples and statistics, the density or sampled volume, the offset scratch).  A process that shares the GPU with other users of its memory calls fib_trim() when it
  * is done with a batch: everything listed above goes back to the driver (plans are kept: small, and costly to rebuild), the next call
  * re-allocates what it needs.  fib_trim waits for calls in flight; it returns FIB_OK. */
 #define FIB_DEVICE_ALL (-1)
@@ -436,6 +496,17 @@ int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sig
 int fib_xfm_apply(int device, const float vox2vox[16], const float *in, float *out, int64_t npoints);
 int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, float *adc, float *s0);
+/* host-buffer forms of the tract maps (fibd_str_density / fibd_str_sample / fibd_str_stats above): every array is host memory.  The
+ * points are the large operand: they go to the device in chunks cut at line boundaries (str_sample: at points), while the density
+ * volume and the sampled volume stay resident for the call.  density is read only with FIB_DENSITY_ACCUMULATE and always written;
+ * *n_outside receives this call's count.  npts < 0 or sum(npts) != npoints: FIB_ERR_INVALID before anything is written.
+ * device = FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED (FIB_DENSITY_ACCUMULATE is the building block for splitting a tractogram). */
+int fib_str_density(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz, int mode,
+                    uint32_t *density, int64_t *n_outside);
+int fib_str_sample(int device, const float *xyz, int64_t npoints, const float *vol, int nx, int ny, int nz, int nframes, float outside,
+                   float *scalars);
+int fib_str_stats(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const float volres[3],
+                  const float *scalars, int nscalars, float *props);
 /* gqi_rec(dwi, mask, odf_dirs, sigma)::GQI (gqi.jl:109) */
 int fib_gqi_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, const float *bvec,

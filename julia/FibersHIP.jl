@@ -332,3 +332,53 @@ function str_xform(xfm::Xform{Float32}, tr::Tract{Float32}; device::Integer=0)
   trnew.xyz = [moved[:, off[i]+1:off[i+1]] for i in 1:length(n)]
   return trnew
 end
+
+# ---- tract maps (NOT in the reference; the definitions are the "Tract maps" section of include/fibers_hip.h) ----------------------
+const FIB_DENSITY_MODES = Dict(:points => 0, :lines => 1, :endpoints => 2)
+const FIB_DENSITY_ACCUMULATE = 0x100
+
+"packed lines of a Tract: (xyz [3 x npoints], npts Int32[nlines])"
+function str_packed(tr::Tract{Float32})
+  npts = Int32[size(x, 2) for x in tr.xyz]
+  xyz  = isempty(npts) ? Matrix{Float32}(undef, 3, 0) : reduce(hcat, tr.xyz)
+  return xyz, npts
+end
+
+"""str_density(tr; mode = :lines | :points | :endpoints, dims, out) -> (D::Array{UInt32,3}, n_outside) — path density of a tractogram:
+points per voxel, lines per voxel (each line once per voxel it visits), or line ends per voxel.  `out`: an earlier map to add to."""
+function str_density(tr::Tract{Float32}; mode::Symbol=:lines, dims=Int.(tr.dim), out::Union{Array{UInt32,3},Nothing}=nothing, device::Integer=0)
+  haskey(FIB_DENSITY_MODES, mode) || error("mode must be :points, :lines or :endpoints")
+  xyz, npts = str_packed(tr)
+  code = FIB_DENSITY_MODES[mode] | (isnothing(out) ? 0 : FIB_DENSITY_ACCUMULATE)
+  D = isnothing(out) ? zeros(UInt32, dims[1], dims[2], dims[3]) : out
+  nout = Ref{Int64}(0)
+  GC.@preserve xyz npts D fib_check(ccall((:fib_str_density, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Int64, Int64, Cint, Cint, Cint, Cint, Ptr{UInt32}, Ref{Int64}),
+      device, xyz, npts, length(npts), size(xyz, 2), size(D, 1), size(D, 2), size(D, 3), code, D, nout))
+  return D, nout[]
+end
+
+"str_sample(tr, vol; outside) -> one [nframes x npts] matrix per line (the layout of Tract.scalars): vol[:, :, :, f] at every point's nearest voxel"
+function str_sample(tr::Tract{Float32}, vol::Array{Float32,4}; outside::Real=0, device::Integer=0)
+  xyz, npts = str_packed(tr)
+  nf = size(vol, 4)
+  S = Matrix{Float32}(undef, nf, size(xyz, 2))
+  GC.@preserve xyz vol S fib_check(ccall((:fib_str_sample, libfibers), Cint,
+      (Cint, Ptr{Float32}, Int64, Ptr{Float32}, Cint, Cint, Cint, Cint, Cfloat, Ptr{Float32}),
+      device, xyz, size(xyz, 2), vol, size(vol, 1), size(vol, 2), size(vol, 3), nf, Float32(outside), S))
+  off = cumsum(vcat(0, Int.(npts)))
+  return [S[:, off[i]+1:off[i+1]] for i in 1:length(npts)]
+end
+
+"str_stats(tr) -> [1 + n_scalars x nlines] (the layout of Tract.properties): length in mm, then the mean of every scalar along the line"
+function str_stats(tr::Tract{Float32}; device::Integer=0)
+  xyz, npts = str_packed(tr)
+  ns = isempty(tr.scalars) ? 0 : size(tr.scalars[1], 1)
+  sc = ns == 0 ? Matrix{Float32}(undef, 0, 0) : reduce(hcat, tr.scalars)          # [ns x npoints]: a point's scalars adjacent
+  P = Matrix{Float32}(undef, 1 + ns, length(npts))
+  res = Float32.(tr.voxel_size)
+  GC.@preserve xyz npts sc P res fib_check(ccall((:fib_str_stats, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Int64, Int64, Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Float32}),
+      device, xyz, npts, length(npts), size(xyz, 2), res, sc, ns, P))
+  return P
+end
