@@ -43,6 +43,15 @@ __device__ __forceinline__ void dti_finish(const float d[7], float o[16]) {
 #pragma unroll
     for (int k = 0; k < 16; k++) o[k] = r.o[k];
 }
+// dti_maps, dti.jl:325-335
+__device__ __forceinline__ void dti_maps(float e1, float e2, float e3, float o[16]) {
+    float rd = e2 + e3;
+    const float md = (e1 + rd) / 3.0f;
+    rd = rd / 2.0f;
+    const float num = (e1 - md) * (e1 - md) + (e2 - md) * (e2 - md) + (e3 - md) * (e3 - md);
+    const float den = e1 * e1 + e2 * e2 + e3 * e3;
+    o[13] = rd; o[14] = md; o[15] = sqrtf(num / den * 1.5f);
+}
 __device__ __forceinline__ void dti_finish_inl(const float d[7], float o[16]) {
     float w[3], ev[3][3];
     o[0] = expf(d[6]);
@@ -51,12 +60,7 @@ __device__ __forceinline__ void dti_finish_inl(const float d[7], float o[16]) {
     o[1] = e1; o[2] = e2; o[3] = e3;
 #pragma unroll
     for (int c = 0; c < 3; c++) { o[4 + c] = ev[2][c]; o[7 + c] = ev[1][c]; o[10 + c] = ev[0][c]; }
-    float rd = e2 + e3;
-    const float md = (e1 + rd) / 3.0f;
-    rd = rd / 2.0f;
-    const float num = (e1 - md) * (e1 - md) + (e2 - md) * (e2 - md) + (e3 - md) * (e3 - md);
-    const float den = e1 * e1 + e2 * e2 + e3 * e3;
-    o[13] = rd; o[14] = md; o[15] = sqrtf(num / den * 1.5f);
+    dti_maps(e1, e2, e3, o);
 }
 
 template <int V> struct VecT;
@@ -225,9 +229,25 @@ __device__ void jacobi_sym(double (&A)[N][N], double (&Q)[N][N]) {
     }
 }
 
+// The eigen-decomposition and the maps of a fitted tensor by float64 Jacobi, for the tensors on which the closed form breaks
+// down: a positive subset of rank below 7 (coplanar directions) leaves a row of the tensor exactly zero, and sym3_eigen then
+// divides 0 by 0 or normalises rounding noise.  o[0] (S0) is left as it is.
+__device__ void dti_finish_jacobi(const float d[7], float o[16]) {
+    double A[3][3] = {{d[0], d[1], d[2]}, {d[1], d[3], d[4]}, {d[2], d[4], d[5]}}, Q[3][3];
+    jacobi_sym<3>(A, Q);
+    int i1 = 0, i2 = 1, i3 = 2;                                          // descending: eigval1 >= eigval2 >= eigval3
+    if (A[i1][i1] < A[i2][i2]) { const int t = i1; i1 = i2; i2 = t; }
+    if (A[i2][i2] < A[i3][i3]) { const int t = i2; i2 = i3; i3 = t; }
+    if (A[i1][i1] < A[i2][i2]) { const int t = i1; i1 = i2; i2 = t; }
+    const float e1 = (float)A[i1][i1], e2 = (float)A[i2][i2], e3 = (float)A[i3][i3];
+    o[1] = e1; o[2] = e2; o[3] = e3;
+    for (int c = 0; c < 3; c++) { o[4 + c] = (float)Q[c][i1]; o[7 + c] = (float)Q[c][i2]; o[10 + c] = (float)Q[c][i3]; }
+    dti_maps(e1, e2, e3, o);
+}
+
 // The complete per-voxel fit (dti.jl:286-303) for the voxels the fast kernel could not finish: exact
-// positive count, accurate logf; all positive -> d = pA*log(s); else npos > 6 with a positive b0 -> row-subset
-// least squares (== pinv(A[ipos,:]) * log(s[ipos]), float64 normal equations + Jacobi, LinearAlgebra.pinv's
+// positive count; all positive -> d = pA*log(s) with the accurate logf; else npos > 6 with a positive b0 -> row-subset
+// least squares (== pinv(A[ipos,:]) * log(s[ipos]), float64 logarithms, normal equations + Jacobi, LinearAlgebra.pinv's
 // rank cut-off); else zeros.  design/coef: [nvol][8].  One thread per listed voxel; count[1] += subset solves.
 template <int NP>
 __global__ __launch_bounds__(64) void fit_partial_kernel(const float *__restrict__ dwi, const float *__restrict__ design,
@@ -244,7 +264,7 @@ __global__ __launch_bounds__(64) void fit_partial_kernel(const float *__restrict
         if (s > 0.0f) { npos++; b0pos |= coef[8 * i + 7] != 0.0f; }     // dti.jl:291-292, any(ipos[ib0])
     }
     float d[NP];
-    bool solved = true;
+    bool solved = true, rankdef = false;                                 // rankdef: the subset's pinv dropped a direction
     if (npos == nvol) {                                                  // dti.jl:294-296
         for (int j = 0; j < NP; j++) d[j] = 0.0f;
         for (int i = 0; i < nvol; i++) {
@@ -258,7 +278,9 @@ __global__ __launch_bounds__(64) void fit_partial_kernel(const float *__restrict
         for (int i = 0; i < nvol; i++) {
             const float s = dwi[(int64_t)i * nvox + vox];
             if (!(s > 0.0f)) continue;                                   // A[ipos, :]
-            const double l = (double)logf(s);
+            // the logarithm in float64 like the rest of this solve: a subset that barely over-determines the 7 unknowns
+            // (npos 8, cond 1e3) turns logf's last-place error into 1e-5 of the tensor; rounded once, at d
+            const double l = log((double)s);
             double a[NP];
             for (int j = 0; j < NP; j++) a[j] = (double)design[8 * i + j];
             for (int j = 0; j < NP; j++) {
@@ -275,7 +297,7 @@ __global__ __launch_bounds__(64) void fit_partial_kernel(const float *__restrict
         for (int r = 0; r < NP; r++) {
             double acc = 0.0;
             for (int j = 0; j < NP; j++) {
-                if (!(N[j][j] > cut)) continue;
+                if (!(N[j][j] > cut)) { rankdef = true; continue; }
                 double proj = 0.0;
                 for (int k = 0; k < NP; k++) proj += Q[k][j] * rhs[k];
                 acc += Q[r][j] * proj / N[j][j];
@@ -289,6 +311,10 @@ __global__ __launch_bounds__(64) void fit_partial_kernel(const float *__restrict
     if constexpr (NP == 7) {
         float o[16];
         dti_finish(d, o);
+        bool vfin = true, dfin = true;
+        for (int k = 4; k < 13; k++) vfin &= fabsf(o[k]) <= 2.0f;       // (false for NaN)
+        for (int k = 0; k < 6; k++) dfin &= fabsf(d[k]) < INFINITY;
+        if ((rankdef || !vfin) && dfin) dti_finish_jacobi(d, o);
         out.s0[vox] = o[0]; out.l1[vox] = o[1]; out.l2[vox] = o[2]; out.l3[vox] = o[3];
         for (int c = 0; c < 3; c++) {
             out.e1[c * nvox + vox] = o[4 + c];
