@@ -21,3 +21,5 @@ from .trk import str_add, stream_to_trk, tract_header, trk_read, trk_write  # no
 from .xform import Xform, str_merge, str_xform, xfm_apply, xfm_compose, xfm_inv, xfm_read, xfm_rotate  # noqa: F401
 from .tractmap import (str_density, str_density_device, str_sample, str_sample_device, str_stats, str_stats_device,  # noqa: F401
                        str_work_size)
+from .tractsel import (Connectome, str_connectome, str_connectome_device, str_gather_device, str_roi_pack_device, str_select,  # noqa: F401
+                       str_select_device, str_select_work_size, str_take)

@@ -10,6 +10,7 @@ FIB_OK = 0
 FIB_ERR_CAPACITY = -9
 FIB_DENSITY_ACCUMULATE = 0x100      # OR-ed into the mode of fib(d)_str_density: add to what the map holds
 DENSITY_MODES = {"points": 0, "lines": 1, "endpoints": 2}
+FIB_CONNECTOME_ACCUMULATE = 0x100   # flags of fib(d)_str_connectome: add to what C and W hold
 FIB_MASK_OUTPUTS_ZEROED = 0x100     # OR-ed into mask_dtype: the output arrays are freshly zero-allocated (include/fibers_hip.h)
 DTYPES = {"uint8": 0, "int8": 1, "int16": 2, "uint16": 3, "int32": 4, "uint32": 5,
           "float32": 6, "float64": 7, "int64": 8, "bool": 9}
@@ -103,6 +104,17 @@ _PROTOS = {
     "fib_str_density": (i32, [i32, vp, vp, i64, i64, i32, i32, i32, i32, vp, C.POINTER(i64)]),
     "fib_str_sample": (i32, [i32, vp, i64, vp, i32, i32, i32, i32, f32, vp]),
     "fib_str_stats": (i32, [i32, vp, vp, i64, i64, C.POINTER(C.c_float * 3), vp, i32, vp]),
+    "fibd_str_roi_pack": (i32, [vp, i32, i64, vp, vp]),
+    "fibd_str_select_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
+    "fibd_str_select": (i32, [vp, vp, i64, i64, i32, i32, i32, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, i32, i32, vp, vp, vp, vp,
+                              C.c_uint64, vp]),
+    "fibd_str_gather": (i32, [vp, vp, i64, i64, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_str_connectome": (i32, [vp, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_float * 3), vp, vp, i64, i32, i32, vp, vp, vp, vp, vp,
+                                  C.c_uint64, vp]),
+    "fib_str_select": (i32, [i32, vp, vp, i64, i64, i32, i32, i32, C.POINTER(vp), i32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, i32, i32,
+                             vp, vp, C.POINTER(i64)]),
+    "fib_str_connectome": (i32, [i32, vp, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_float * 3), vp, vp, i64, i32, i32, vp, vp, vp,
+                                 C.POINTER(i64)]),
     "fibd_stream_trace_lcm": (i32, [C.POINTER(StreamParams), vp, vp, f32, i32, i32, C.c_uint64, vp, i64, vp, i32, vp,
                                     C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]),
     "fibd_stream_pack_flags": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -180,7 +192,7 @@ def shutdown():
 
 def trim():
     """fib_trim: the host tier's buffers kept between calls (pinned ring, its device mirror, fib_stream's device buffers, the tracer's
-    workspace, the tract maps' device buffers) go back to the driver; plans stay"""
+    workspace, the device buffers of the tract maps, the selection and the connectome) go back to the driver; plans stay"""
     check(lib().fib_trim())
 
 

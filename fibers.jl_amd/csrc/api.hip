@@ -157,6 +157,11 @@ struct DevState {
         fib::DevBuf<uint32_t> dens;
         fib::DevBuf<char> work;
         fib::DevBuf<int64_t> nout;
+        // fib_str_select / fib_str_connectome: the ROIs and their bit volume, keep and hits of a chunk; labels, remap, C, W, assign
+        fib::DevBuf<uint8_t> rois, keep;
+        fib::DevBuf<uint32_t> roibits, hits, cmat;
+        fib::DevBuf<int32_t> labels, remap, assign;
+        fib::DevBuf<double> wmat;
     } tm;
 
     int init(int nthreads) {
@@ -188,6 +193,8 @@ struct DevState {
         sb.mask.release(); sb.mout.release(); sb.flags.release(); sb.seeds.release(); sb.sidx.release(); sb.npts.release();
         tm.xyz.release(); tm.vol.release(); tm.scal.release(); tm.props.release(); tm.npts.release(); tm.dens.release(); tm.work.release();
         tm.nout.release();
+        tm.rois.release(); tm.keep.release(); tm.roibits.release(); tm.hits.release(); tm.cmat.release(); tm.labels.release(); tm.remap.release();
+        tm.assign.release(); tm.wmat.release();
         if (ws) { fibd_stream_ws_destroy(ws); ws = nullptr; }
     }
     void drop_plans() {
@@ -591,7 +598,7 @@ void tm_next_chunk(const int32_t *npts, int64_t nlines, int64_t l0, int64_t *l1,
 }
 
 int tm_worker(int device, Worker &w) {
-    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "the tract maps run on one device (FIB_DEVICE_ALL is not supported)");
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "the tract maps, the selection and the connectome run on one device (FIB_DEVICE_ALL is not supported)");
     std::vector<Worker> ws;
     RC(workers_for(device, ws));
     w = ws[0];
@@ -701,6 +708,126 @@ extern "C" int fib_str_stats(int device, const float *xyz, const int32_t *npts, 
         RC(d2h(props + l0 * ncol, b.props.p, sizeof(float) * (size_t)ncol * (l1 - l0)));
         p0 += np; l0 = l1;
     }
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// tract selection and connectome: host forms.  One device; the points travel in chunks cut at line boundaries, the ROI bit volume /
+// the label volume and C, W stay on the device.
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_str_select(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
+                              const uint8_t *const *rois, int nroi, uint64_t visit_all, uint64_t visit_none, uint64_t end_any, uint64_t end_both,
+                              int32_t min_npts, int32_t max_npts, uint8_t *keep, uint32_t *hits, int64_t *counts) try {
+    FIB_CHECK(nroi >= 0 && nroi <= 32, FIB_ERR_INVALID, "fib_str_select takes 0 to 32 ROIs (one bit each of a 32-bit word), not %d", nroi);
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
+    FIB_CHECK(counts && (nlines <= 0 || keep) && (nroi == 0 || rois), FIB_ERR_INVALID, "NULL argument");
+    for (int r = 0; r < nroi; r++) FIB_CHECK(rois[r], FIB_ERR_INVALID, "ROI %d is NULL", r);
+    const uint64_t used = visit_all | visit_none | end_any | end_both;
+    FIB_CHECK((used >> 32) == 0 && (nroi == 32 || (used >> nroi) == 0), FIB_ERR_INVALID, "a mask names an ROI beyond the %d given", nroi);
+    FIB_CHECK(min_npts >= 0 && max_npts >= 0, FIB_ERR_INVALID, "min_npts and max_npts must not be negative");
+    RC(tm_host_check(npts, nlines, npoints));
+    FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    const size_t nvox = (size_t)nx * ny * nz;
+    RC(b.nout.ensure(3));
+    if (nroi) {
+        RC(b.rois.ensure(nvox * nroi));
+        RC(b.roibits.ensure(nvox));
+        for (int r = 0; r < nroi; r++) RC(h2d(b.rois.p + nvox * r, rois[r], nvox));
+        RC(fibd_str_roi_pack(b.rois.p, nroi, (int64_t)nvox, b.roibits.p, nullptr));
+    }
+    int64_t total[2] = {0, 0};
+    int64_t p0 = 0;
+    for (int64_t l0 = 0; l0 < nlines;) {
+        int64_t l1, np;
+        tm_next_chunk(npts, nlines, l0, &l1, &np);
+        const size_t nl = (size_t)(l1 - l0);
+        size_t wb = 0;
+        RC(fibd_str_select_work_size(l1 - l0, &wb));
+        RC(b.work.ensure(wb));
+        RC(b.npts.ensure(nl));
+        RC(b.xyz.ensure((size_t)3 * np));
+        RC(b.keep.ensure(nl));
+        if (hits) RC(b.hits.ensure(3 * nl));
+        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * nl));
+        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(fibd_str_select(b.xyz.p, b.npts.p, l1 - l0, np, nx, ny, nz, nroi ? b.roibits.p : nullptr, visit_all, visit_none, end_any, end_both, min_npts,
+                           max_npts, b.keep.p, hits ? b.hits.p : nullptr, b.nout.p, b.work.p, wb, nullptr));
+        int64_t got[2] = {0, 0};
+        RC(d2h(got, b.nout.p, sizeof got));                    // (a blocking copy on the NULL stream: behind the kernels)
+        FIB_CHECK(got[0] >= 0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
+        RC(d2h(keep + l0, b.keep.p, nl));
+        if (hits) RC(d2h(hits + 3 * l0, b.hits.p, sizeof(uint32_t) * 3 * nl));
+        total[0] += got[0]; total[1] += got[1];
+        p0 += np; l0 = l1;
+    }
+    counts[0] = total[0]; counts[1] = total[1];
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_str_connectome(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
+                                  const float volres[3], const int32_t *labels, const int32_t *remap, int64_t nremap, int nnodes, int flags,
+                                  uint32_t *cmat, double *wmat, int32_t *assign, int64_t *n_lines) try {
+    FIB_CHECK((flags & ~FIB_CONNECTOME_ACCUMULATE) == 0, FIB_ERR_INVALID, "unknown connectome flags 0x%x", flags);
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
+    FIB_CHECK(nnodes >= 1 && nnodes < (1 << 24), FIB_ERR_INVALID, "the number of nodes must be between 1 and 2^24 - 1");
+    FIB_CHECK(labels && cmat && n_lines, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(!wmat || volres, FIB_ERR_INVALID, "the lengths of W need volres");
+    FIB_CHECK(nremap >= 0 && (nremap == 0 || remap), FIB_ERR_INVALID, "nremap entries need a remap array");
+    RC(tm_host_check(npts, nlines, npoints));
+    FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    const size_t nvox = (size_t)nx * ny * nz, cells = (size_t)(nnodes + 1) * (size_t)(nnodes + 1);
+    RC(b.nout.ensure(3));
+    RC(b.labels.ensure(nvox));
+    RC(h2d(b.labels.p, labels, sizeof(int32_t) * nvox));
+    if (nremap) { RC(b.remap.ensure((size_t)nremap)); RC(h2d(b.remap.p, remap, sizeof(int32_t) * (size_t)nremap)); }
+    RC(b.cmat.ensure(cells));
+    if (wmat) RC(b.wmat.ensure(cells));
+    if (flags & FIB_CONNECTOME_ACCUMULATE) {
+        RC(h2d(b.cmat.p, cmat, sizeof(uint32_t) * cells));
+        if (wmat) RC(h2d(b.wmat.p, wmat, sizeof(double) * cells));
+    } else {
+        FIB_HIP(hipMemset(b.cmat.p, 0, sizeof(uint32_t) * cells));
+        if (wmat) FIB_HIP(hipMemset(b.wmat.p, 0, sizeof(double) * cells));
+    }
+    int64_t total = 0;
+    int64_t p0 = 0;
+    for (int64_t l0 = 0; l0 < nlines;) {
+        int64_t l1, np;
+        tm_next_chunk(npts, nlines, l0, &l1, &np);
+        const size_t nl = (size_t)(l1 - l0);
+        size_t wb = 0;
+        RC(fibd_str_select_work_size(l1 - l0, &wb));
+        RC(b.work.ensure(wb));
+        RC(b.npts.ensure(nl));
+        RC(b.xyz.ensure((size_t)3 * np));
+        if (assign) RC(b.assign.ensure(2 * nl));
+        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * nl));
+        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(fibd_str_connectome(b.xyz.p, b.npts.p, l1 - l0, np, nx, ny, nz, volres, b.labels.p, nremap ? b.remap.p : nullptr, nremap, nnodes,
+                               FIB_CONNECTOME_ACCUMULATE, b.cmat.p, wmat ? b.wmat.p : nullptr, assign ? b.assign.p : nullptr, b.nout.p, b.work.p, wb,
+                               nullptr));
+        int64_t got = 0;
+        RC(d2h(&got, b.nout.p, sizeof got));
+        FIB_CHECK(got >= 0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
+        if (assign) RC(d2h(assign + 2 * l0, b.assign.p, sizeof(int32_t) * 2 * nl));
+        total += got;
+        p0 += np; l0 = l1;
+    }
+    RC(d2h(cmat, b.cmat.p, sizeof(uint32_t) * cells));
+    if (wmat) RC(d2h(wmat, b.wmat.p, sizeof(double) * cells));
+    *n_lines = total;
     return FIB_OK;
 } FIB_API_CATCH
 

@@ -442,6 +442,75 @@ int fibd_str_stats(const float *xyz, const int32_t *npts, int64_t nlines, int64_
                    int nscalars, float *props, void *work, size_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Tract selection and connectomes: ROI filters, label matrix (NOT in the reference)     */
+/* ------------------------------------------------------------------------------------ */
+/* Inputs are PACKED LINES exactly as for the tract maps above (xyz float32 [npoints][3], 4-byte alignment suffices; npts int32
+ * [nlines]); the VOXEL OF A POINT, the INSIDE test and lin(v) are the ones defined there and nothing else.  These definitions are
+ * this project's own; they are the contract.  npts is INVALID if any entry is negative or sum(npts) != npoints; the device forms see
+ * that in their offset scan (no host round trip) and refuse as said under each function.
+ *
+ * ROI BIT VOLUME roibits, uint32 [nvox]: bit r is set iff ROI r (r < 32) is non-zero at that voxel, so that one 4-byte gather per
+ * point serves up to 32 ROIs.  fibd_str_roi_pack makes it from rois, planar uint8 [nroi][nvox] (any non-zero byte sets the bit;
+ * bits nroi..31 are 0).
+ *
+ * SELECTION.  Per-line predicates, all three 0 for an empty line:
+ *   visit  the OR of roibits[lin(v)] over the line's inside points;
+ *   end0   roibits at the voxel of the first point if that point is inside, else 0;
+ *   end1   the same for the last point (a one-point line has end0 == end1).
+ * The RULE is four masks and a point-count window.  A line is KEPT iff all of
+ *   (visit & visit_all) == visit_all          it passes through every ROI of visit_all
+ *   (visit & visit_none) == 0                 and through none of visit_none
+ *   ((end0 | end1) & end_any) == end_any      every ROI of end_any holds at least one of its ends
+ *   (end0 & end1 & end_both) == end_both      every ROI of end_both holds both
+ *   min_npts <= npts and (max_npts == 0 or npts <= max_npts)
+ * hold.  With every mask 0 and the window (0, 0) every line is kept, lines with npts = 0 included.  The masks are 32-bit; they
+ * travel as uint64_t, as every unsigned scalar of this ABI does, and a bit above bit 31 is FIB_ERR_INVALID.  roibits may be NULL
+ * when all four masks are 0 (the predicates are then 0).
+ * Outputs: keep uint8 [nlines], 0 or 1; hits uint32 [nlines][3] = {visit, end0, end1}, may be NULL; counts int64 [2] in device
+ * memory = {kept lines, kept points}.  INVALID npts: keep is zero-filled, hits is left untouched, counts = {-1, -1}.
+ *
+ * COMPACTION (gather) takes ANY keep flags, not only those of the selection: a line is kept iff keep[line] != 0.  The kept lines are
+ * copied in input order (stable): xyz_out [kept points][3], npts_out [nkept], optionally index_out int64 [nkept] = the line's index
+ * in the input (what carries seed_index, properties or anything else per line) and scalars_out [kept points][nscalars] from scalars
+ * [npoints][nscalars].  The copies are byte-identical (32-bit words: NaN payloads and -0.0 survive).  counts int64 [3] in device
+ * memory = {kept lines, kept points, status}: the true totals and status 0; if a total exceeds cap_lines / cap_points the totals are
+ * still true, status is -1 and NOTHING is written to the four outputs; INVALID npts: {-1, -1, 0} and nothing is written.  There is
+ * never a partial result.
+ *
+ * CONNECTOME.  labels int32 [nvox]; remap int32 [nremap] or NULL for the identity; L = nnodes, the number of nodes.  NODE OF A LINE
+ * END: 0 if the end point is outside; else x = labels[lin(v)], y = remap[x] (remap NULL: y = x; x outside 0 <= x < nremap: y = 0),
+ * and the node is y if 1 <= y <= L, else 0.  Node 0 means "unassigned".  For every line with npts >= 1 let a, b be the nodes of its
+ * first and last point, i = min(a, b), j = max(a, b):
+ *   C[i][j] += 1, and if i != j also C[j][i] += 1.  C is uint32 [L+1][L+1], row-major, symmetric; row and column 0 hold the
+ *              unassigned ends; a self-connection counts once, on the diagonal.  The sum of the upper triangle with the diagonal
+ *              is #{npts >= 1} (on a zero-filled C).  Counts wrap at 2^32.
+ *   W[i][j] (and W[j][i] if i != j) += the line's length in mm.  W is float64 [L+1][L+1], may be NULL.  The length is the column-0
+ *              sum of the LINE STATISTICS above (the same float64 terms, r = volres), kept in float64 and NOT rounded to float32.
+ *              The order of both sums is free (lanes sum a line, atomic adds sum a cell): against sequential float64 sums
+ *              |W - W_seq| <= (n_max + m) * 2^-52 * W_seq per cell, n_max the points of the longest of the cell's m lines.  A
+ *              cell with C = 0 is exactly 0.  When W is NULL no length is computed and volres may be NULL.
+ *   assign     int32 [nlines][2] = (a, b) in line order (first end, last end), (0, 0) for empty lines; may be NULL.
+ * *n_lines_dev (int64, device) = the number of lines counted (#{npts >= 1}), or -1 for INVALID npts, and then nothing is added and
+ * assign is not written.  flags: 0, or FIB_CONNECTOME_ACCUMULATE to add to what C and W hold (without it the call zero-fills them
+ * first, for an INVALID npts too).  Integer counts make C independent of batch and arrival order (same bytes). */
+#define FIB_CONNECTOME_ACCUMULATE 0x100
+/* rois, roibits: device pointers.  nroi 0..32.  Asynchronous on `stream`. */
+int fibd_str_roi_pack(const uint8_t *rois, int nroi, int64_t nvox, uint32_t *roibits, void *stream);
+/* bytes of device scratch fibd_str_select / fibd_str_gather / fibd_str_connectome need for nlines lines (three int64 per line and
+ * per block of the scan: each line's first point, its place among the kept lines and among their points); 8-byte aligned */
+int fibd_str_select_work_size(int64_t nlines, size_t *bytes);
+/* All three: every array is a device pointer; asynchronous on `stream`, no allocation and no synchronisation inside. */
+int fibd_str_select(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz, const uint32_t *roibits,
+                    uint64_t visit_all, uint64_t visit_none, uint64_t end_any, uint64_t end_both, int32_t min_npts, int32_t max_npts,
+                    uint8_t *keep, uint32_t *hits, int64_t *counts, void *work, size_t work_bytes, void *stream);
+int fibd_str_gather(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const uint8_t *keep, const float *scalars,
+                    int nscalars, int64_t cap_lines, int64_t cap_points, float *xyz_out, int32_t *npts_out, int64_t *index_out,
+                    float *scalars_out, int64_t *counts, void *work, size_t work_bytes, void *stream);
+int fibd_str_connectome(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz, const float volres[3],
+                        const int32_t *labels, const int32_t *remap, int64_t nremap, int nnodes, int flags, uint32_t *cmat, double *wmat,
+                        int32_t *assign, int64_t *n_lines_dev, void *work, size_t work_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Host-buffer drop-in entry points (what the Julia wrapper ccalls)                       */
 /* ------------------------------------------------------------------------------------ */
 
@@ -459,7 +528,8 @@ int fibd_str_stats(const float *xyz, const int32_t *npts, int64_t nlines, int64_
  * ring's device mirror (3 x (rows in + rows out) x chunk x 4 bytes each: ~1.9 GB of host and of device memory after fib_gqi_rec on 270
  * frames), the device buffers of fib_stream (orientation field, seeds, and the packed result: 1.5 GB after 129 M points), the tracer's
  * workspace (scratch for every line in flight) and the device buffers of fib_str_density / fib_str_sample / fib_str_stats (one chunk of
- * points with its counts, samples and statistics, the density or sampled volume, the offset scratch).  A process that shares the GPU with other users of its memory calls fib_trim() when it
+ * points with its counts, samples and statistics, the density or sampled volume, the offset scratch) and of fib_str_select /
+ * fib_str_connectome (the ROI bit volume and the ROIs it was packed from, keep and hits of a chunk, labels, remap, C, W, assign).  A process that shares the GPU with other users of its memory calls fib_trim() when it
  * is done with a batch: everything listed above goes back to the driver (plans are kept: small, and costly to rebuild), the next call
  * re-allocates what it needs.  fib_trim waits for calls in flight; it returns FIB_OK. */
 #define FIB_DEVICE_ALL (-1)
@@ -507,6 +577,19 @@ int fib_str_sample(int device, const float *xyz, int64_t npoints, const float *v
                    float *scalars);
 int fib_str_stats(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const float volres[3],
                   const float *scalars, int nscalars, float *props);
+/* host-buffer forms of the selection and the connectome (fibd_str_select / fibd_str_connectome above): every array is host memory.
+ * The points go to the device in chunks cut at line boundaries; the ROI bit volume (packed on the device from rois, nroi pointers to
+ * uint8 [nvox] volumes, nroi <= 32 or FIB_ERR_INVALID) or the label volume, and C / W, stay resident for the call.  fib_str_select
+ * returns keep [nlines], hits [nlines][3] (may be NULL) and counts[2] (host).  Compacting HOST arrays by keep is a host copy and
+ * belongs to the caller's language: there is no host form of the gather.  fib_str_connectome accumulates chunk after chunk into one
+ * C / W (read only with FIB_CONNECTOME_ACCUMULATE, always written; wmat and assign may be NULL); *n_lines = the lines counted.
+ * npts < 0 or sum(npts) != npoints: FIB_ERR_INVALID before anything is written.  device = FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED. */
+int fib_str_select(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
+                   const uint8_t *const *rois, int nroi, uint64_t visit_all, uint64_t visit_none, uint64_t end_any, uint64_t end_both,
+                   int32_t min_npts, int32_t max_npts, uint8_t *keep, uint32_t *hits, int64_t *counts);
+int fib_str_connectome(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
+                       const float volres[3], const int32_t *labels, const int32_t *remap, int64_t nremap, int nnodes, int flags,
+                       uint32_t *cmat, double *wmat, int32_t *assign, int64_t *n_lines);
 /* gqi_rec(dwi, mask, odf_dirs, sigma)::GQI (gqi.jl:109) */
 int fib_gqi_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, const float *bvec,

@@ -382,3 +382,102 @@ function str_stats(tr::Tract{Float32}; device::Integer=0)
       device, xyz, npts, length(npts), size(xyz, 2), res, sc, ns, P))
   return P
 end
+
+# ---- tract selection and connectomes (NOT in the reference; "Tract selection and connectomes" in include/fibers_hip.h) --------------
+const FIB_CONNECTOME_ACCUMULATE = 0x100
+
+"the kept lines of a Tract (a host copy): xyz, scalars, properties of the lines whose flag is set, in order"
+function str_take(tr::Tract{Float32}, keep::AbstractVector{Bool})
+  trnew = deepcopy(tr)
+  trnew.xyz = tr.xyz[keep]
+  isempty(tr.scalars) || (trnew.scalars = tr.scalars[keep])
+  isempty(tr.properties) || (trnew.properties = tr.properties[:, keep])
+  trnew.npts = Int32[size(x, 2) for x in trnew.xyz]
+  trnew.n_count = length(trnew.xyz)
+  return trnew
+end
+
+"""str_select(tr; include, exclude, end_in, both_ends_in, min_npts, max_npts) -> Tract — the lines that pass through every volume of
+`include` and none of `exclude`, have an end in every volume of `end_in` and both ends in every volume of `both_ends_in` (volumes:
+`Array{UInt8,3}` of `tr.dim`, non-zero inside; 32 in all), with min_npts <= npts (<= max_npts unless 0).  Also returns keep and hits."""
+function str_select(tr::Tract{Float32}; include=Array{UInt8,3}[], exclude=Array{UInt8,3}[], end_in=Array{UInt8,3}[], both_ends_in=Array{UInt8,3}[],
+                    min_npts::Integer=0, max_npts::Integer=0, device::Integer=0)
+  groups = (include, exclude, end_in, both_ends_in)
+  rois = Array{UInt8,3}[r for g in groups for r in g]
+  length(rois) <= 32 || error("one call takes 32 regions")
+  masks, bit = UInt64[], 0
+  for g in groups
+    push!(masks, reduce(|, (UInt64(1) << (bit + k - 1) for k in 1:length(g)); init=UInt64(0)))
+    bit += length(g)
+  end
+  xyz, npts = str_packed(tr)
+  dims = Int.(tr.dim)
+  keep = Vector{UInt8}(undef, length(npts))
+  hits = Matrix{UInt32}(undef, 3, length(npts))
+  counts = zeros(Int64, 2)
+  ptrs = Ptr{UInt8}[pointer(r) for r in rois]
+  GC.@preserve xyz npts rois ptrs keep hits counts fib_check(ccall((:fib_str_select, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Int64, Int64, Cint, Cint, Cint, Ptr{Ptr{UInt8}}, Cint, UInt64, UInt64, UInt64, UInt64, Int32, Int32,
+       Ptr{UInt8}, Ptr{UInt32}, Ptr{Int64}),
+      device, xyz, npts, length(npts), size(xyz, 2), dims[1], dims[2], dims[3], ptrs, length(rois), masks[1], masks[2], masks[3], masks[4],
+      min_npts, max_npts, keep, hits, counts))
+  return str_take(tr, keep .!= 0), keep, hits
+end
+
+"""str_connectome(tr, labels; ids, lengths) -> (C::Matrix{UInt32}, mean_length::Matrix{Float64}, ids, assign) — lines between every pair
+of nodes of the label volume (`Array{Int32,3}` of `tr.dim`), and their mean length in mm; node k = ids[k], row / column 1 of the
+matrices (node 0) holds the ends that are outside or in no node."""
+function str_connectome(tr::Tract{Float32}, labels::Array{Int32,3}; ids=sort(unique(labels[labels .> 0])), lengths::Bool=true, device::Integer=0)
+  L = length(ids)
+  remap = zeros(Int32, maximum(ids) + 1)
+  for (k, v) in enumerate(ids); remap[v + 1] = k; end
+  xyz, npts = str_packed(tr)
+  Cm = zeros(UInt32, L + 1, L + 1)
+  W = zeros(Float64, L + 1, L + 1)
+  assign = Matrix{Int32}(undef, 2, length(npts))
+  nl = Ref{Int64}(0)
+  res = Float32.(tr.voxel_size)
+  GC.@preserve xyz npts labels remap Cm W assign res fib_check(ccall((:fib_str_connectome, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Int64, Int64, Cint, Cint, Cint, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Int64, Cint, Cint,
+       Ptr{UInt32}, Ptr{Float64}, Ptr{Int32}, Ref{Int64}),
+      device, xyz, npts, length(npts), size(xyz, 2), size(labels, 1), size(labels, 2), size(labels, 3), res, labels, remap, length(remap), L, 0,
+      Cm, lengths ? pointer(W) : Ptr{Float64}(C_NULL), assign, nl))
+  return Cm, (lengths ? map((w, c) -> c > 0 ? w / c : 0.0, W, Cm) : nothing), ids, assign
+end
+
+# device tier: the same kernels on device pointers (a caller that holds them, e.g. through AMDGPU.jl, passes them as Ptr{Cvoid})
+fibd_str_roi_pack(rois::Ptr{Cvoid}, nroi::Integer, nvox::Integer, roibits::Ptr{Cvoid}, stream::Ptr{Cvoid}=C_NULL) =
+  fib_check(ccall((:fibd_str_roi_pack, libfibers), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}), rois, nroi, nvox, roibits, stream))
+
+function fibd_str_select_work_size(nlines::Integer)
+  b = Ref{UInt64}(0)
+  fib_check(ccall((:fibd_str_select_work_size, libfibers), Cint, (Int64, Ref{UInt64}), nlines, b))
+  return Int(b[])
+end
+
+fibd_str_select(xyz::Ptr{Cvoid}, npts::Ptr{Cvoid}, nlines::Integer, npoints::Integer, dims, roibits::Ptr{Cvoid}, visit_all::UInt64, visit_none::UInt64,
+                end_any::UInt64, end_both::UInt64, min_npts::Integer, max_npts::Integer, keep::Ptr{Cvoid}, hits::Ptr{Cvoid}, counts::Ptr{Cvoid},
+                work::Ptr{Cvoid}, work_bytes::Integer, stream::Ptr{Cvoid}=C_NULL) =
+  fib_check(ccall((:fibd_str_select, libfibers), Cint,
+      (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Cint, Cint, Ptr{Cvoid}, UInt64, UInt64, UInt64, UInt64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid},
+       Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Ptr{Cvoid}),
+      xyz, npts, nlines, npoints, dims[1], dims[2], dims[3], roibits, visit_all, visit_none, end_any, end_both, min_npts, max_npts, keep, hits,
+      counts, work, work_bytes, stream))
+
+fibd_str_gather(xyz::Ptr{Cvoid}, npts::Ptr{Cvoid}, nlines::Integer, npoints::Integer, keep::Ptr{Cvoid}, scalars::Ptr{Cvoid}, nscalars::Integer,
+                cap_lines::Integer, cap_points::Integer, xyz_out::Ptr{Cvoid}, npts_out::Ptr{Cvoid}, index_out::Ptr{Cvoid}, scalars_out::Ptr{Cvoid},
+                counts::Ptr{Cvoid}, work::Ptr{Cvoid}, work_bytes::Integer, stream::Ptr{Cvoid}=C_NULL) =
+  fib_check(ccall((:fibd_str_gather, libfibers), Cint,
+      (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+       Ptr{Cvoid}, UInt64, Ptr{Cvoid}),
+      xyz, npts, nlines, npoints, keep, scalars, nscalars, cap_lines, cap_points, xyz_out, npts_out, index_out, scalars_out, counts, work,
+      work_bytes, stream))
+
+fibd_str_connectome(xyz::Ptr{Cvoid}, npts::Ptr{Cvoid}, nlines::Integer, npoints::Integer, dims, volres::Vector{Float32}, labels::Ptr{Cvoid},
+                    remap::Ptr{Cvoid}, nremap::Integer, nnodes::Integer, flags::Integer, cmat::Ptr{Cvoid}, wmat::Ptr{Cvoid}, assign::Ptr{Cvoid},
+                    n_lines::Ptr{Cvoid}, work::Ptr{Cvoid}, work_bytes::Integer, stream::Ptr{Cvoid}=C_NULL) =
+  fib_check(ccall((:fibd_str_connectome, libfibers), Cint,
+      (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Cint, Cint, Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid},
+       Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Ptr{Cvoid}),
+      xyz, npts, nlines, npoints, dims[1], dims[2], dims[3], volres, labels, remap, nremap, nnodes, flags, cmat, wmat, assign, n_lines, work,
+      work_bytes, stream))
