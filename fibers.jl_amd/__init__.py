@@ -23,3 +23,5 @@ from .tractmap import (str_density, str_density_device, str_sample, str_sample_d
                        str_work_size)
 from .tractsel import (Connectome, str_connectome, str_connectome_device, str_gather_device, str_roi_pack_device, str_select,  # noqa: F401
                        str_select_device, str_select_work_size, str_take)
+from .bundle import (Bundles, str_assign_device, str_bundles, str_centroids, str_centroids_device, str_profile, str_resample,  # noqa: F401
+                     str_resample_device)

@@ -11,6 +11,7 @@ FIB_ERR_CAPACITY = -9
 FIB_DENSITY_ACCUMULATE = 0x100      # OR-ed into the mode of fib(d)_str_density: add to what the map holds
 DENSITY_MODES = {"points": 0, "lines": 1, "endpoints": 2}
 FIB_CONNECTOME_ACCUMULATE = 0x100   # flags of fib(d)_str_connectome: add to what C and W hold
+FIB_CENTROIDS_ACCUMULATE = 0x100    # flags of fib(d)_str_centroids: add to what sums and counts hold
 FIB_MASK_OUTPUTS_ZEROED = 0x100     # OR-ed into mask_dtype: the output arrays are freshly zero-allocated (include/fibers_hip.h)
 DTYPES = {"uint8": 0, "int8": 1, "int16": 2, "uint16": 3, "int32": 4, "uint32": 5,
           "float32": 6, "float64": 7, "int64": 8, "bool": 9}
@@ -115,6 +116,12 @@ _PROTOS = {
                              vp, vp, C.POINTER(i64)]),
     "fib_str_connectome": (i32, [i32, vp, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_float * 3), vp, vp, i64, i32, i32, vp, vp, vp,
                                  C.POINTER(i64)]),
+    "fibd_str_resample": (i32, [vp, vp, i64, i64, C.POINTER(C.c_float * 3), i32, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_str_assign": (i32, [vp, i64, i32, vp, i32, C.POINTER(C.c_float * 3), f32, vp, vp, vp, vp, vp]),
+    "fibd_str_centroids": (i32, [vp, i64, i32, vp, vp, i32, i32, vp, vp, vp]),
+    "fib_str_resample": (i32, [i32, vp, vp, i64, i64, C.POINTER(C.c_float * 3), i32, vp, vp]),
+    "fib_str_assign": (i32, [i32, vp, i64, i32, vp, i32, C.POINTER(C.c_float * 3), f32, vp, vp, vp, vp]),
+    "fib_str_centroids": (i32, [i32, vp, i64, i32, vp, vp, i32, i32, vp, vp]),
     "fibd_stream_trace_lcm": (i32, [C.POINTER(StreamParams), vp, vp, f32, i32, i32, C.c_uint64, vp, i64, vp, i32, vp,
                                     C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]),
     "fibd_stream_pack_flags": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -192,7 +199,7 @@ def shutdown():
 
 def trim():
     """fib_trim: the host tier's buffers kept between calls (pinned ring, its device mirror, fib_stream's device buffers, the tracer's
-    workspace, the device buffers of the tract maps, the selection and the connectome) go back to the driver; plans stay"""
+    workspace, the device buffers of the tract maps, the selection, the connectome and the bundle tools) go back to the driver; plans stay"""
     check(lib().fib_trim())
 
 

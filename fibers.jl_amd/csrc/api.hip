@@ -162,6 +162,13 @@ struct DevState {
         fib::DevBuf<uint32_t> roibits, hits, cmat;
         fib::DevBuf<int32_t> labels, remap, assign;
         fib::DevBuf<double> wmat;
+        // fib_str_resample / fib_str_assign / fib_str_centroids: the equal-length lines of a chunk, the models, label / dist / flip of a
+        // chunk, all distances, sums and counts
+        fib::DevBuf<float> lines, models, dist, dall;
+        fib::DevBuf<int32_t> label;
+        fib::DevBuf<uint8_t> flip;
+        fib::DevBuf<double> sums;
+        fib::DevBuf<uint32_t> bcnt;
     } tm;
 
     int init(int nthreads) {
@@ -195,6 +202,8 @@ struct DevState {
         tm.nout.release();
         tm.rois.release(); tm.keep.release(); tm.roibits.release(); tm.hits.release(); tm.cmat.release(); tm.labels.release(); tm.remap.release();
         tm.assign.release(); tm.wmat.release();
+        tm.lines.release(); tm.models.release(); tm.dist.release(); tm.dall.release(); tm.label.release(); tm.flip.release(); tm.sums.release();
+        tm.bcnt.release();
         if (ws) { fibd_stream_ws_destroy(ws); ws = nullptr; }
     }
     void drop_plans() {
@@ -828,6 +837,125 @@ extern "C" int fib_str_connectome(int device, const float *xyz, const int32_t *n
     RC(d2h(cmat, b.cmat.p, sizeof(uint32_t) * cells));
     if (wmat) RC(d2h(wmat, b.wmat.p, sizeof(double) * cells));
     *n_lines = total;
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// bundle tools: host forms.  One device; the lines travel in chunks, the models and sums / counts stay on the device.
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_str_resample(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const float volres[3], int K,
+                                const uint8_t *flip, float *out) try {
+    FIB_CHECK(K >= 2 && K <= 256, FIB_ERR_UNSUPPORTED, "fib_str_resample gives 2 to 256 points per line, not %d", K);
+    FIB_CHECK(volres, FIB_ERR_INVALID, "NULL volres");
+    RC(tm_host_check(npts, nlines, npoints));
+    FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
+    FIB_CHECK(nlines == 0 || out, FIB_ERR_INVALID, "NULL out");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    RC(b.nout.ensure(3));
+    const int64_t max_lines = std::max<int64_t>(1, TM_CHUNK_POINTS / K);       // the output of a chunk is no larger than its largest input
+    int64_t p0 = 0;
+    for (int64_t l0 = 0; l0 < nlines;) {
+        int64_t l1, np;
+        tm_next_chunk(npts, nlines, l0, &l1, &np);
+        if (l1 - l0 > max_lines) { l1 = l0 + max_lines; np = 0; for (int64_t l = l0; l < l1; l++) np += npts[l]; }
+        const size_t nl = (size_t)(l1 - l0);
+        size_t wb = 0;
+        RC(fibd_str_work_size(l1 - l0, &wb));
+        RC(b.work.ensure(wb));
+        RC(b.npts.ensure(nl));
+        RC(b.xyz.ensure((size_t)3 * np));
+        RC(b.lines.ensure((size_t)3 * K * nl));
+        if (flip) RC(b.flip.ensure(nl));
+        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * nl));
+        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        if (flip) RC(h2d(b.flip.p, flip + l0, nl));
+        RC(fibd_str_resample(b.xyz.p, b.npts.p, l1 - l0, np, volres, K, flip ? b.flip.p : nullptr, b.lines.p, b.nout.p, b.work.p, wb, nullptr));
+        int64_t got = 0;
+        RC(d2h(&got, b.nout.p, sizeof got));                   // (a blocking copy on the NULL stream: behind the kernels)
+        FIB_CHECK(got == l1 - l0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
+        RC(d2h(out + (size_t)3 * K * l0, b.lines.p, sizeof(float) * 3 * K * nl));
+        p0 += np; l0 = l1;
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_str_assign(int device, const float *lines, int64_t nlines, int K, const float *models, int nmodels, const float volres[3],
+                              float thresh_mm, int32_t *label, float *dist, uint8_t *flip, float *dist_all) try {
+    FIB_CHECK(nlines >= 0, FIB_ERR_INVALID, "nlines must not be negative");
+    FIB_CHECK(K >= 1 && K <= 256, FIB_ERR_UNSUPPORTED, "lines of 1 to 256 points each, not %d", K);
+    FIB_CHECK(nmodels >= 1 && nmodels < (1 << 24), FIB_ERR_INVALID, "the number of models must be between 1 and 2^24 - 1");
+    FIB_CHECK(models && volres && (nlines == 0 || (lines && label && dist && flip)), FIB_ERR_INVALID, "NULL argument");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    const size_t row = (size_t)3 * K;
+    RC(b.models.ensure(row * nmodels));
+    RC(h2d(b.models.p, models, sizeof(float) * row * nmodels));
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(TM_CHUNK_POINTS / K, dist_all ? ((int64_t)1 << 26) / nmodels : nlines));
+    for (int64_t l0 = 0; l0 < nlines; l0 += chunk) {
+        const size_t nl = (size_t)std::min(chunk, nlines - l0);
+        RC(b.lines.ensure(row * nl));
+        RC(b.label.ensure(nl));
+        RC(b.dist.ensure(nl));
+        RC(b.flip.ensure(nl));
+        if (dist_all) RC(b.dall.ensure(nl * nmodels));
+        RC(h2d(b.lines.p, lines + row * l0, sizeof(float) * row * nl));
+        RC(fibd_str_assign(b.lines.p, (int64_t)nl, K, b.models.p, nmodels, volres, thresh_mm, b.label.p, b.dist.p, b.flip.p, dist_all ? b.dall.p : nullptr,
+                           nullptr));
+        RC(d2h(label + l0, b.label.p, sizeof(int32_t) * nl));
+        RC(d2h(dist + l0, b.dist.p, sizeof(float) * nl));
+        RC(d2h(flip + l0, b.flip.p, nl));
+        if (dist_all) RC(d2h(dist_all + (size_t)l0 * nmodels, b.dall.p, sizeof(float) * nl * nmodels));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_str_centroids(int device, const float *lines, int64_t nlines, int K, const int32_t *label, const uint8_t *flip, int nmodels,
+                                 int flags, double *sums, uint32_t *counts) try {
+    FIB_CHECK((flags & ~FIB_CENTROIDS_ACCUMULATE) == 0, FIB_ERR_INVALID, "unknown centroid flags 0x%x", flags);
+    FIB_CHECK(nlines >= 0, FIB_ERR_INVALID, "nlines must not be negative");
+    FIB_CHECK(K >= 1 && K <= 256, FIB_ERR_UNSUPPORTED, "lines of 1 to 256 points each, not %d", K);
+    FIB_CHECK(nmodels >= 1 && nmodels < (1 << 24), FIB_ERR_INVALID, "the number of models must be between 1 and 2^24 - 1");
+    FIB_CHECK(sums && counts && (nlines == 0 || (lines && label)), FIB_ERR_INVALID, "NULL argument");
+    Worker wk;
+    RC(tm_worker(device, wk));
+    std::lock_guard<std::mutex> lk(wk->mu);
+    fib::DeviceGuard guard;
+    RC(wk->init(copy_threads(1)));
+    auto &b = wk->tm;
+    const size_t row = (size_t)3 * K, cells = row * nmodels;
+    RC(b.sums.ensure(cells));
+    RC(b.bcnt.ensure((size_t)nmodels));
+    if (flags & FIB_CENTROIDS_ACCUMULATE) {
+        RC(h2d(b.sums.p, sums, sizeof(double) * cells));
+        RC(h2d(b.bcnt.p, counts, sizeof(uint32_t) * (size_t)nmodels));
+    } else {
+        FIB_HIP(hipMemset(b.sums.p, 0, sizeof(double) * cells));
+        FIB_HIP(hipMemset(b.bcnt.p, 0, sizeof(uint32_t) * (size_t)nmodels));
+    }
+    const int64_t chunk = std::max<int64_t>(1, TM_CHUNK_POINTS / K);
+    for (int64_t l0 = 0; l0 < nlines; l0 += chunk) {
+        const size_t nl = (size_t)std::min(chunk, nlines - l0);
+        RC(b.lines.ensure(row * nl));
+        RC(b.label.ensure(nl));
+        if (flip) RC(b.flip.ensure(nl));
+        RC(h2d(b.lines.p, lines + row * l0, sizeof(float) * row * nl));
+        RC(h2d(b.label.p, label + l0, sizeof(int32_t) * nl));
+        if (flip) RC(h2d(b.flip.p, flip + l0, nl));
+        RC(fibd_str_centroids(b.lines.p, (int64_t)nl, K, b.label.p, flip ? b.flip.p : nullptr, nmodels, FIB_CENTROIDS_ACCUMULATE, b.sums.p, b.bcnt.p,
+                              nullptr));
+        FIB_HIP(hipStreamSynchronize(nullptr));                // (the chunk's buffers are written again)
+    }
+    RC(d2h(sums, b.sums.p, sizeof(double) * cells));
+    RC(d2h(counts, b.bcnt.p, sizeof(uint32_t) * (size_t)nmodels));
     return FIB_OK;
 } FIB_API_CATCH
 

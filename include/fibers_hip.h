@@ -511,6 +511,64 @@ int fibd_str_connectome(const float *xyz, const int32_t *npts, int64_t nlines, i
                         int32_t *assign, int64_t *n_lines_dev, void *work, size_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Bundle tools: resampling, MDF assignment, centroids (NOT in the reference)            */
+/* ------------------------------------------------------------------------------------ */
+/* What a tractography user does right after "I have a million lines": bring every line to the same number of points, compare it with
+ * a set of model bundles, and work per bundle.  Inputs of RESAMPLE are PACKED LINES exactly as for the tract maps above; npts is
+ * INVALID as defined there.  These definitions are this project's own; they are the contract.  r = volres as float32; every
+ * operation below is IEEE float64 on the float32 inputs, rounded one by one, NO fused multiply-add.
+ *
+ * RESAMPLE gives every line K points (2 <= K <= 256, else FIB_ERR_UNSUPPORTED), equidistant in arc length in mm: out float32
+ * [nlines][K][3].  For a line with points p_0 .. p_{n-1}:
+ *   l_i (i = 0 .. n-2)  the length of segment i: exactly the term of the LINE STATISTICS length above,
+ *                       sqrt(((x1-x0)*r_x)*((x1-x0)*r_x) + ((y1-y0)*r_y)*((y1-y0)*r_y) + ((z1-z0)*r_z)*((z1-z0)*r_z)), squares added left to right;
+ *   c_0 = 0, c_{i+1} = c_i + l_i, T = c_{n-1}.  The order of these additions is free on the device (any-order float64 prefix sums
+ *                       are each within (n-1) * 2^-53 * T of the exact ones), but ONE set of c serves both the search and the
+ *                       interpolation below.  (The shipped kernel adds them in sequence, which is what makes c non-decreasing and
+ *                       gives every output row exactly one owner.)
+ *   row 0 is a bit copy of p_0 and row K-1 a bit copy of p_{n-1}.  For 0 < k < K-1:
+ *                       t_k = (T * (double)k) / (double)(K-1);  j = the largest i <= n-2 with c_i <= t_k;
+ *                       a = (t_k - c_j) / (c_{j+1} - c_j) clamped to [0, 1], or 0 if that denominator is not > 0;
+ *                       each component is (double)p_j + a * ((double)p_{j+1} - (double)p_j), rounded to float32 once.
+ *   n = 1: all K rows are bit copies of p_0.  n = 0, or n >= 2 and T not finite (a NaN or +-Inf coordinate): every component of all
+ *   K rows is the quiet NaN 0x7FC00000, rows 0 and K-1 included.  Coordinates of +-1e30 make T huge but finite: legal.  Duplicated
+ *   consecutive points (the tracer emits the seed twice) are segments of length 0 that own no row; a line of equal points gives copies.
+ *   flip, uint8 [nlines] or NULL: for a line whose flag is non-zero, output row k holds what row K-1-k would have held, bit for bit.
+ *   A line's result depends on the line alone -- not on its index, its neighbours or the batch it arrives in: two runs, or the same
+ *   lines in another order, give the same bytes per line; the host form equals the device form byte for byte.
+ *   *status_dev (int64, device) = the number of lines written (nlines), or -1 for an INVALID npts, and then nothing is written to out.
+ *
+ * ASSIGN: the MDF (mean direct-flip) distance of every line to every model bundle, the nearest model and the orientation.  lines
+ * float32 [nlines][K][3] and models float32 [nmodels][K][3], both in voxel coordinates (K >= 1; 1 <= nmodels < 2^24).  For a pair
+ * (a, m):  d_dir = (sum_{k=0}^{K-1} |(a_k - m_k) o r|) / K,  d_flip = the same sum with m_{K-1-k};  each norm is the term l above on
+ * the pair of points (a_k first: (m - a) is NOT used; the three components are ((double)a_c - (double)m_c) * (double)r_c); the sum
+ * runs over k SEQUENTIALLY from 0 in float64, then one float64 division by (double)K.  f = (d_flip < d_dir), d = f ? d_flip : d_dir.
+ * A NaN d compares as larger than everything.  Per line:
+ *   label int32   the first m that attains the minimum d (float64, strict <) if that d <= (double)thresh_mm, else -1; -1 when every
+ *                 d is NaN (and for a NaN thresh_mm);
+ *   dist float32  the minimum d rounded to float32 once, written whatever the threshold says; NaN if every d is NaN;
+ *   flip uint8    f of the pair that gives dist (whatever the threshold says), 0 if every d is NaN;
+ *   dist_all      float32 [nlines][nmodels], every d rounded once; may be NULL.
+ * Every NaN that dist and dist_all hold is the quiet NaN 0x7FC00000.
+ * The k-sum is sequential and every term an IEEE float64 value: everything this call writes is BIT-IDENTICAL to a NumPy restatement.
+ *
+ * CENTROIDS: per-bundle sums of oriented lines, so that assign -> centroids -> assign is a refinement loop that stays on the device.
+ * For every line with 0 <= label < nmodels:  counts[label] += 1 (uint32, wraps at 2^32) and sums[label][k][c] += (double) of the line's
+ * row (flip ? K-1-k : k), component c; sums float64 [nmodels][K][3].  Other labels contribute nothing; flip may be NULL (all 0).  flags:
+ * 0, or FIB_CENTROIDS_ACCUMULATE to add to what the outputs hold (without it the call zero-fills them first).  The order of the
+ * float64 additions is free: against the sequential sum |sums - sums_seq| <= (N_b - 1) * 2^-52 * sum|t| per cell, N_b the lines of
+ * the bundle; a bundle without lines is exactly 0 (on zero-filled outputs).  counts are exact and independent of batch and order. */
+#define FIB_CENTROIDS_ACCUMULATE 0x100
+/* All three: every array is a device pointer; asynchronous on `stream`, no allocation and no synchronisation inside.  work is sized by
+ * fibd_str_work_size(nlines). */
+int fibd_str_resample(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const float volres[3], int K,
+                      const uint8_t *flip, float *out, int64_t *status_dev, void *work, size_t work_bytes, void *stream);
+int fibd_str_assign(const float *lines, int64_t nlines, int K, const float *models, int nmodels, const float volres[3],
+                    float thresh_mm, int32_t *label, float *dist, uint8_t *flip, float *dist_all, void *stream);
+int fibd_str_centroids(const float *lines, int64_t nlines, int K, const int32_t *label, const uint8_t *flip, int nmodels,
+                       int flags, double *sums, uint32_t *counts, void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Host-buffer drop-in entry points (what the Julia wrapper ccalls)                       */
 /* ------------------------------------------------------------------------------------ */
 
@@ -529,7 +587,8 @@ int fibd_str_connectome(const float *xyz, const int32_t *npts, int64_t nlines, i
  * frames), the device buffers of fib_stream (orientation field, seeds, and the packed result: 1.5 GB after 129 M points), the tracer's
  * workspace (scratch for every line in flight) and the device buffers of fib_str_density / fib_str_sample / fib_str_stats (one chunk of
  * points with its counts, samples and statistics, the density or sampled volume, the offset scratch) and of fib_str_select /
- * fib_str_connectome (the ROI bit volume and the ROIs it was packed from, keep and hits of a chunk, labels, remap, C, W, assign).  A process that shares the GPU with other users of its memory calls fib_trim() when it
+ * fib_str_connectome (the ROI bit volume and the ROIs it was packed from, keep and hits of a chunk, labels, remap, C, W, assign) and of
+ * fib_str_resample / fib_str_assign / fib_str_centroids (the equal-length lines of a chunk, the models, label / dist / flip, sums, counts).  A process that shares the GPU with other users of its memory calls fib_trim() when it
  * is done with a batch: everything listed above goes back to the driver (plans are kept: small, and costly to rebuild), the next call
  * re-allocates what it needs.  fib_trim waits for calls in flight; it returns FIB_OK. */
 #define FIB_DEVICE_ALL (-1)
@@ -590,6 +649,18 @@ int fib_str_select(int device, const float *xyz, const int32_t *npts, int64_t nl
 int fib_str_connectome(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
                        const float volres[3], const int32_t *labels, const int32_t *remap, int64_t nremap, int nnodes, int flags,
                        uint32_t *cmat, double *wmat, int32_t *assign, int64_t *n_lines);
+/* host-buffer forms of the bundle tools (fibd_str_resample / fibd_str_assign / fibd_str_centroids above): every array is host memory.
+ * The lines go to the device in chunks cut at line boundaries; the models, and sums / counts, stay resident for the call.  Everything
+ * fib_str_resample and fib_str_assign write equals the device form's output byte for byte (a line's result depends on the line
+ * alone); fib_str_centroids adds chunk after chunk into one sums / counts (read only with FIB_CENTROIDS_ACCUMULATE, always written):
+ * counts equal the device form's, sums are within the bound stated above.  npts < 0 or sum(npts) != npoints: FIB_ERR_INVALID before
+ * anything is written.  device = FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED. */
+int fib_str_resample(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, const float volres[3], int K,
+                     const uint8_t *flip, float *out);
+int fib_str_assign(int device, const float *lines, int64_t nlines, int K, const float *models, int nmodels, const float volres[3],
+                   float thresh_mm, int32_t *label, float *dist, uint8_t *flip, float *dist_all);
+int fib_str_centroids(int device, const float *lines, int64_t nlines, int K, const int32_t *label, const uint8_t *flip, int nmodels,
+                      int flags, double *sums, uint32_t *counts);
 /* gqi_rec(dwi, mask, odf_dirs, sigma)::GQI (gqi.jl:109) */
 int fib_gqi_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, const float *bvec,

@@ -445,6 +445,46 @@ function str_connectome(tr::Tract{Float32}, labels::Array{Int32,3}; ids=sort(uni
   return Cm, (lengths ? map((w, c) -> c > 0 ? w / c : 0.0, W, Cm) : nothing), ids, assign
 end
 
+# ---- bundle tools (NOT in the reference; "Bundle tools" in include/fibers_hip.h) -----------------------------------------------------
+const FIB_CENTROIDS_ACCUMULATE = 0x100
+
+"""str_resample(tr, K; flip) -> [3 x K x nlines] — every line with K points (2 to 256) equidistant in arc length in mm (tr.voxel_size);
+`flip`: per-line flags, a flagged line comes out reversed.  Lines without points or with a NaN / Inf coordinate are NaN."""
+function str_resample(tr::Tract{Float32}, K::Integer=20; flip::Union{Vector{UInt8},Nothing}=nothing, device::Integer=0)
+  xyz, npts = str_packed(tr)
+  out = Array{Float32,3}(undef, 3, K, length(npts))
+  res = Float32.(tr.voxel_size)
+  fl = isnothing(flip) ? UInt8[] : flip
+  GC.@preserve xyz npts res fl out fib_check(ccall((:fib_str_resample, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Int64, Int64, Ptr{Float32}, Cint, Ptr{UInt8}, Ptr{Float32}),
+      device, xyz, npts, length(npts), size(xyz, 2), res, K, isnothing(flip) ? Ptr{UInt8}(C_NULL) : pointer(fl), out))
+  return out
+end
+
+"""str_assign(lines, models, voxel_size, thresh_mm) -> (label, dist, flip) — lines [3 x K x nlines], models [3 x K x nmodels]: the
+nearest model of every line by MDF distance in mm (0-based index, -1 beyond `thresh_mm`), the distance, and 1 where the line runs
+against its model."""
+function str_assign(lines::Array{Float32,3}, models::Array{Float32,3}, voxel_size, thresh_mm::Real; device::Integer=0)
+  K, nl, nm = size(lines, 2), size(lines, 3), size(models, 3)
+  size(models, 2) == K || error("models and lines must have the same number of points")
+  label, dist, flip = Vector{Int32}(undef, nl), Vector{Float32}(undef, nl), Vector{UInt8}(undef, nl)
+  res = Float32.(voxel_size)
+  GC.@preserve lines models res label dist flip fib_check(ccall((:fib_str_assign, libfibers), Cint,
+      (Cint, Ptr{Float32}, Int64, Cint, Ptr{Float32}, Cint, Ptr{Float32}, Cfloat, Ptr{Int32}, Ptr{Float32}, Ptr{UInt8}, Ptr{Float32}),
+      device, lines, nl, K, models, nm, res, Float32(thresh_mm), label, dist, flip, Ptr{Float32}(C_NULL)))
+  return label, dist, flip
+end
+
+"str_centroids(lines, label, flip, nmodels) -> (sums [3 x K x nmodels] Float64, counts UInt32[nmodels]): per-bundle sums of the oriented lines"
+function str_centroids(lines::Array{Float32,3}, label::Vector{Int32}, flip::Vector{UInt8}, nmodels::Integer; device::Integer=0)
+  K, nl = size(lines, 2), size(lines, 3)
+  sums, counts = zeros(Float64, 3, K, nmodels), zeros(UInt32, nmodels)
+  GC.@preserve lines label flip sums counts fib_check(ccall((:fib_str_centroids, libfibers), Cint,
+      (Cint, Ptr{Float32}, Int64, Cint, Ptr{Int32}, Ptr{UInt8}, Cint, Cint, Ptr{Float64}, Ptr{UInt32}),
+      device, lines, nl, K, label, flip, nmodels, 0, sums, counts))
+  return sums, counts
+end
+
 # device tier: the same kernels on device pointers (a caller that holds them, e.g. through AMDGPU.jl, passes them as Ptr{Cvoid})
 fibd_str_roi_pack(rois::Ptr{Cvoid}, nroi::Integer, nvox::Integer, roibits::Ptr{Cvoid}, stream::Ptr{Cvoid}=C_NULL) =
   fib_check(ccall((:fibd_str_roi_pack, libfibers), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}), rois, nroi, nvox, roibits, stream))
