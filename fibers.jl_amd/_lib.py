@@ -29,6 +29,15 @@ class DtiOut(C.Structure):
                 ("s0", "eigval1", "eigval2", "eigval3", "eigvec1", "eigvec2", "eigvec3", "rd", "md", "fa")]
 
 
+class DkiParams(C.Structure):
+    _fields_ = [("min_signal", C.c_float), ("min_diffusivity", C.c_float), ("min_kurtosis", C.c_float), ("max_kurtosis", C.c_float)]
+
+
+class DkiOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("s0", "eigval1", "eigval2", "eigval3", "eigvec1", "eigvec2", "eigvec3", "rd", "md", "fa", "mk", "ak", "rk", "kt")]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("nvec", C.c_int32),
                 ("len_min", C.c_int32), ("len_max", C.c_int32),
@@ -63,6 +72,11 @@ _PROTOS = {
     "fib_dti_plan_create": (i32, [i32, vp, vp, i32, C.POINTER(vp)]),
     "fib_dti_plan_destroy": (None, [vp]),
     "fib_dti_plan_tables": (i32, [vp, vp, vp, C.POINTER(i32)]),
+    "fib_dki_design": (i32, [vp, vp, i32, vp, vp, C.POINTER(i32)]),
+    "fib_dki_plan_create": (i32, [i32, vp, vp, i32, vp, i32, C.POINTER(DkiParams), C.POINTER(vp)]),
+    "fib_dki_plan_destroy": (None, [vp]),
+    "fib_dki_plan_tables": (i32, [vp, vp, vp, vp]),
+    "fibd_dki_fit": (i32, [vp, vp, vp, i64, C.POINTER(DkiOut), vp]),
     "fib_gqi_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, f32, C.POINTER(vp)]),
     "fib_dsi_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, i32, C.POINTER(vp)]),
     "fib_gqi_plan_create_fmt": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, f32, i32, C.POINTER(vp)]),
@@ -132,6 +146,7 @@ _PROTOS = {
     "fib_shutdown": (None, []),
     "fib_dti_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, C.POINTER(DtiOut)]),
     "fib_adc_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "fib_dki_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, C.POINTER(DkiParams), C.POINTER(DkiOut)]),
     "fib_gqi_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, P3, P3]),
     "fib_dsi_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, P3, P3]),
     "fib_rumba_plan_create": (i32, [i32, vp, vp, i32, vp, i32, f32, f32, f32, f32, C.POINTER(vp)]),

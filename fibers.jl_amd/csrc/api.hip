@@ -126,7 +126,12 @@ struct PinBuf {                                          // grow-only pinned hos
     ~PinBuf() { release(); }
 };
 
-struct CachedPlan { std::string key; void *plan = nullptr; int kind = 0; uint64_t stamp = 0; };   // kind 0: dti/adc, 1: odf
+struct CachedPlan { std::string key; void *plan = nullptr; int kind = 0; uint64_t stamp = 0; };   // kind 0: dti/adc, 1: odf, 2: dki
+inline void destroy_cached(const CachedPlan &c) {
+    if (c.kind == 0) fib_dti_plan_destroy((fib_dti_plan *)c.plan);
+    else if (c.kind == 1) fib_odf_plan_destroy((fib_odf_plan *)c.plan);
+    else fib_dki_plan_destroy((fib_dki_plan *)c.plan);
+}
 
 struct DevState {
     int device = 0;
@@ -207,9 +212,7 @@ struct DevState {
         if (ws) { fibd_stream_ws_destroy(ws); ws = nullptr; }
     }
     void drop_plans() {
-        for (auto &c : plans) {
-            if (c.kind == 0) fib_dti_plan_destroy((fib_dti_plan *)c.plan); else fib_odf_plan_destroy((fib_odf_plan *)c.plan);
-        }
+        for (auto &c : plans) destroy_cached(c);
         plans.clear();
     }
     ~DevState() {
@@ -277,7 +280,7 @@ int cached_plan(DevState &d, int kind, const std::string &key, MakeFn make, void
     if (d.plans.size() >= 4) {                           // evict the least recently used
         size_t lru = 0;
         for (size_t i = 1; i < d.plans.size(); i++) if (d.plans[i].stamp < d.plans[lru].stamp) lru = i;
-        if (d.plans[lru].kind == 0) fib_dti_plan_destroy((fib_dti_plan *)d.plans[lru].plan); else fib_odf_plan_destroy((fib_odf_plan *)d.plans[lru].plan);
+        destroy_cached(d.plans[lru]);
         d.plans.erase(d.plans.begin() + lru);
     }
     d.plans.push_back(CachedPlan{key, p, kind, ++d.clock});
@@ -492,6 +495,54 @@ extern "C" int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz,
         return run_chunks(d, v0, v1, nvox, ins, mask, mask_dtype, outs, pick_chunk(use ? use->nlive : v1 - v0, nvol, 2),
                           [&](int, int64_t, int64_t n, const float *din, const uint8_t *dm, float *b, hipStream_t st) -> int {
                               return fibd_adc_fit(plan, din, dm, n, b, b + n, st);
+                          }, use, zeroed);
+    });
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// dki_fit
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_dki_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
+                           const void *mask, int mask_dtype, const float *bval, const float *bvec,
+                           const float *verts, int nverts, const fib_dki_params *params, const fib_dki_out *out) try {
+    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
+    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    FIB_CHECK(dwi && mask && out && verts, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0 && nverts >= 2, FIB_ERR_INVALID, "volume dimensions and the vertex count must be positive");
+    const bool zeroed = (mask_dtype & FIB_MASK_OUTPUTS_ZEROED) != 0;
+    mask_dtype &= ~FIB_MASK_OUTPUTS_ZEROED;
+    FIB_CHECK(dtype_size(mask_dtype) > 0, FIB_ERR_INVALID, "unknown mask dtype %d", mask_dtype);
+    FIB_CHECK(out->s0 && out->eigval1 && out->eigval2 && out->eigval3 && out->eigvec1 && out->eigvec2 && out->eigvec3 && out->rd && out->md && out->fa &&
+              out->mk && out->ak && out->rk, FIB_ERR_INVALID, "NULL output volume");
+    const int64_t nvox = (int64_t)nx * ny * nz;
+    std::vector<Worker> ws;
+    RC(workers_for(device, ws));
+    const std::vector<Rows> ins = {{dwi, nullptr, nvol}};
+    std::vector<Rows> outs = {{nullptr, out->s0, 1}, {nullptr, out->eigval1, 1}, {nullptr, out->eigval2, 1}, {nullptr, out->eigval3, 1},
+                              {nullptr, out->eigvec1, 3}, {nullptr, out->eigvec2, 3}, {nullptr, out->eigvec3, 3},
+                              {nullptr, out->rd, 1}, {nullptr, out->md, 1}, {nullptr, out->fa, 1},
+                              {nullptr, out->mk, 1}, {nullptr, out->ak, 1}, {nullptr, out->rk, 1}};
+    const bool want_kt = out->kt != nullptr;
+    if (want_kt) outs.push_back({nullptr, out->kt, 15});
+    std::string key;
+    key_add(key, bval, sizeof(float) * nvol);
+    key_add(key, bvec, sizeof(float) * 3 * nvol);
+    key_add(key, verts, sizeof(float) * 3 * nverts);
+    key_add(key, params, params ? sizeof *params : 0);
+    return for_each_worker(ws, [&](int i, DevState &d) -> int {
+        int64_t v0, v1;
+        slab(nvox, (int)ws.size(), i, v0, v1);
+        void *pp = nullptr;
+        RC(cached_plan(d, 2, key, [&](void **o) { fib_dki_plan *q = nullptr; int rc = fib_dki_plan_create(d.device, bval, bvec, nvol, verts, nverts, params, &q); *o = q; return rc; }, &pp));
+        const fib_dki_plan *plan = (const fib_dki_plan *)pp;
+        LiveMap lm;
+        const LiveMap *use = nullptr;
+        RC(live_map_for(d, mask, mask_dtype, v0, v1, lm, &use));
+        return run_chunks(d, v0, v1, nvox, ins, mask, mask_dtype, outs, pick_chunk(use ? use->nlive : v1 - v0, nvol, want_kt ? 34 : 19),
+                          [&](int, int64_t, int64_t n, const float *din, const uint8_t *dm, float *b, hipStream_t st) -> int {
+                              fib_dki_out dev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 7 * n, b + 10 * n, b + 13 * n, b + 14 * n, b + 15 * n,
+                                              b + 16 * n, b + 17 * n, b + 18 * n, want_kt ? b + 19 * n : nullptr};
+                              return fibd_dki_fit(plan, din, dm, n, &dev, st);
                           }, use, zeroed);
     });
 } FIB_API_CATCH

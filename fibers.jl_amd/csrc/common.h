@@ -103,9 +103,16 @@ struct ProfScope {
 };
 
 // ---- host-side work-struct mathematics (setup.cpp) ----------------------------------------
-// pinv of a column-major float32 [m x n] matrix (n <= 8): float64 one-sided Jacobi SVD,
+// pinv of a column-major float32 [m x n] matrix (n <= 8 for DTI / ADC, 22 for DKI): float64 one-sided Jacobi SVD,
 // Julia's LinearAlgebra.pinv cut-off (singular values <= eps(Float32)*min(m,n)*smax dropped).
 void host_pinv(const float *A, int m, int n, float *pA /* [n x m] column-major */);
+// the same on a float64 matrix, not rounded; returns the rank under that cut-off
+int host_pinv(const double *A, int m, int n, double *pA /* [n x m] column-major */);
+// DKI: the design A [nvol x 22] column-major with b in ms/um^2 and pA = pinv(A) [22 x nvol] with rows 0-5 scaled by 1e-3
+// and rows 6-20 by 1e-6 (the fit's unknowns in mm^2/s and mm^4/s^2), both float64; returns the rank of A under host_pinv's cut-off.
+// host_dki_dir_row: the 6 quadratic (off-diagonals doubled) and 15 multiplicity-weighted quartic monomials of a direction
+int host_dki_design(const float *bval, const float *bvec, int nvol, double *A, double *pA);
+void host_dki_dir_row(double x, double y, double z, double row[21]);
 // DTIwork / ADCwork design matrix (dti.jl:129-140, 66-69); A column-major [nvol x np]
 void host_dti_design(const float *bval, const float *bvec, int nvol, int np, float *A);
 // GQIwork system matrix (gqi.jl:67-69): A column-major [nvert x nvol]

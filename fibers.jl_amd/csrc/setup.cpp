@@ -51,7 +51,7 @@ int use_device(int device) {
 // ------------------------------------------------------------------------------------------
 // pinv: one-sided (Hestenes) Jacobi SVD in float64
 // ------------------------------------------------------------------------------------------
-void host_pinv(const float *A, int m, int n, float *pA) {
+int host_pinv(const double *A, int m, int n, double *pA) {
     std::vector<double> U((size_t)m * n), V((size_t)n * n, 0.0), sig(n);
     for (size_t i = 0; i < (size_t)m * n; i++) U[i] = A[i];
     for (int j = 0; j < n; j++) V[j + (size_t)n * j] = 1.0;
@@ -87,8 +87,19 @@ void host_pinv(const float *A, int m, int n, float *pA) {
             double acc = 0;
             for (int j = 0; j < n; j++)
                 if (sig[j] > tol) acc += V[r + (size_t)n * j] * U[i + (size_t)m * j] / (sig[j] * sig[j]);
-            pA[r + (size_t)n * i] = (float)acc;   // U columns are unnormalised: u = U/sig
+            pA[r + (size_t)n * i] = acc;          // U columns are unnormalised: u = U/sig
         }
+    int rank = 0;
+    for (int j = 0; j < n; j++) rank += sig[j] > tol;
+    return rank;
+}
+
+// the float form: the same arithmetic on the widened matrix, rounded once
+void host_pinv(const float *A, int m, int n, float *pA) {
+    std::vector<double> Ad((size_t)m * n), pd((size_t)m * n);
+    for (size_t i = 0; i < (size_t)m * n; i++) Ad[i] = A[i];
+    (void)host_pinv(Ad.data(), m, n, pd.data());
+    for (size_t i = 0; i < (size_t)m * n; i++) pA[i] = (float)pd[i];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -111,6 +122,41 @@ void host_dti_design(const float *bval, const float *bvec, int nvol, int np, flo
         A[i + 5 * nvol] = (gz * gz) * nb;
         A[i + 6 * nvol] = 1.0f;                 // dti.jl:140
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// DKI design matrix and pseudo-inverse (float64, b in ms/um^2)
+// ------------------------------------------------------------------------------------------
+// the 15 quartic monomials x^a y^b z^c of the kurtosis tensor in the order of d[6..20], and how often each occurs in
+// sum_ijkl n_i n_j n_k n_l V_ijkl
+const int dki_pow[15][3] = {{4, 0, 0}, {0, 4, 0}, {0, 0, 4}, {3, 1, 0}, {3, 0, 1}, {1, 3, 0}, {0, 3, 1}, {1, 0, 3}, {0, 1, 3},
+                            {2, 2, 0}, {2, 0, 2}, {0, 2, 2}, {2, 1, 1}, {1, 2, 1}, {1, 1, 2}};
+const double dki_mult[15] = {1, 1, 1, 4, 4, 4, 4, 4, 4, 6, 6, 6, 12, 12, 12};
+
+void host_dki_dir_row(double x, double y, double z, double row[21]) {
+    row[0] = x * x; row[1] = 2.0 * x * y; row[2] = 2.0 * x * z; row[3] = y * y; row[4] = 2.0 * y * z; row[5] = z * z;
+    const double px[5] = {1.0, x, x * x, x * x * x, (x * x) * (x * x)};
+    const double py[5] = {1.0, y, y * y, y * y * y, (y * y) * (y * y)};
+    const double pz[5] = {1.0, z, z * z, z * z * z, (z * z) * (z * z)};
+    for (int k = 0; k < 15; k++) row[6 + k] = dki_mult[k] * (px[dki_pow[k][0]] * py[dki_pow[k][1]] * pz[dki_pow[k][2]]);
+}
+
+int host_dki_design(const float *bval, const float *bvec, int nvol, double *A, double *pA) {
+    const int np = 22;
+    for (int i = 0; i < nvol; i++) {
+        const double b = (double)bval[i] / 1000.0;                    // ms/um^2: the columns -b, b^2/6 and 1 within 1e2 of each other
+        double row[21];
+        host_dki_dir_row(bvec[i], bvec[i + nvol], bvec[i + 2 * nvol], row);
+        for (int k = 0; k < 6; k++) A[i + (size_t)nvol * k] = -b * row[k];
+        for (int k = 6; k < 21; k++) A[i + (size_t)nvol * k] = (b * b / 6.0) * row[k];
+        A[i + (size_t)nvol * 21] = 1.0;
+    }
+    const int rank = host_pinv(A, nvol, np, pA);
+    for (int i = 0; i < nvol; i++) {                                  // back to s/mm^2: D in mm^2/s, V in mm^4/s^2
+        for (int k = 0; k < 6; k++) pA[k + (size_t)np * i] *= 1e-3;
+        for (int k = 6; k < 21; k++) pA[k + (size_t)np * i] *= 1e-6;
+    }
+    return rank;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -393,4 +439,18 @@ extern "C" int fib_device_count(void) try {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+} FIB_API_CATCH
+
+extern "C" int fib_dki_design(const float *bval, const float *bvec, int nvol, float *A, float *pA, int *rank) try {
+    if (rank) *rank = 0;
+    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
+    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    std::vector<double> Ad((size_t)nvol * 22), pd((size_t)nvol * 22);
+    const int r = fib::host_dki_design(bval, bvec, nvol, Ad.data(), pd.data());
+    if (rank) *rank = r;
+    if (A) for (size_t i = 0; i < Ad.size(); i++) A[i] = (float)Ad[i];
+    if (pA) for (size_t i = 0; i < pd.size(); i++) pA[i] = (float)pd[i];
+    FIB_CHECK(r == 22, FIB_ERR_INVALID, "DKI needs a b ~ 0 frame and at least two non-zero shells with 15 or more distinct directions "
+              "(the design has rank %d of 22 on %d frames)", r, nvol);
+    return FIB_OK;
 } FIB_API_CATCH

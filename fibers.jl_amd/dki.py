@@ -1,0 +1,148 @@
+"""dki_fit: diffusion kurtosis imaging (not in the reference; the definition is DESIGN.md §5).
+
+`dki_fit(dwi, mask)` takes host `MRI`s and goes through the host-buffer C ABI (fib_dki_fit); `DkiPlan` + `dki_fit_device` are
+the device-resident form on torch tensors (fibd_dki_fit).  `dki_design` builds the fit's tables on the host (no GPU needed)."""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .dti import DTI_FIELDS, _check_tables, _chk_dev, _dwi_arg, _mask_checked, _stream_ptr
+from .mri import MRI
+from .odf import ODF, sphere_642
+
+DKI_FIELDS = DTI_FIELDS + ("mk", "ak", "rk", "kt")
+# the 15 independent elements of the kurtosis tensor, in the order of `kt`'s frames, and how often each occurs in the full tensor
+KT_ORDER = ("xxxx", "yyyy", "zzzz", "xxxy", "xxxz", "xyyy", "yyyz", "xzzz", "yzzz", "xxyy", "xxzz", "yyzz", "xxyz", "xyyz", "xyzz")
+KT_MULT = (1, 1, 1, 4, 4, 4, 4, 4, 4, 6, 6, 6, 12, 12, 12)
+DEFAULTS = dict(min_signal=1e-4, min_diffusivity=1e-6, min_kurtosis=-3.0 / 7.0, max_kurtosis=10.0)
+
+
+@dataclass
+class DKI:
+    """Container for outputs of a DKI fit: the ten `DTI` fields (of the kurtosis-corrected diffusion tensor), mean / axial / radial
+    kurtosis and the kurtosis tensor W (15 frames in KT_ORDER)"""
+    s0: MRI
+    eigval1: MRI
+    eigval2: MRI
+    eigval3: MRI
+    eigvec1: MRI
+    eigvec2: MRI
+    eigvec3: MRI
+    rd: MRI
+    md: MRI
+    fa: MRI
+    mk: MRI
+    ak: MRI
+    rk: MRI
+    kt: MRI
+
+
+def _nframes(k):
+    return 3 if "vec" in k else (15 if k == "kt" else 1)
+
+
+def _params(min_signal, min_diffusivity, min_kurtosis, max_kurtosis):
+    return _lib.DkiParams(min_signal, min_diffusivity, min_kurtosis, max_kurtosis)
+
+
+def _verts(odf_dirs: ODF):
+    return np.asfortranarray(odf_dirs.vertices, dtype=np.float32)
+
+
+def dki_design(bval, bvec):
+    """The fit's tables, built on the host in float64 and rounded once: (A [nvol, 22] with b in ms/um^2, pA [22, nvol] scaled to
+    mm^2/s and mm^4/s^2, rank).  A scheme whose design has a rank below 22 raises FibersError (code -1)."""
+    bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
+    nvol = int(bval.shape[0])
+    bv = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
+    if bv.shape[0] != nvol:
+        raise ValueError("gradient table must be [%d x 3], got %s" % (nvol, bv.shape))
+    A = np.zeros((nvol, 22), np.float32, order="F")
+    pA = np.zeros((22, nvol), np.float32, order="F")
+    rank = C.c_int(0)
+    _lib.check(_lib.lib().fib_dki_design(bval.ctypes.data, bv.ctypes.data, nvol, A.ctypes.data, pA.ctypes.data, C.byref(rank)))
+    return A, pA, int(rank.value)
+
+
+def dki_fit(dwi: MRI, mask: MRI, odf_dirs: ODF = sphere_642, min_signal: float = DEFAULTS["min_signal"],
+            min_diffusivity: float = DEFAULTS["min_diffusivity"], min_kurtosis: float = DEFAULTS["min_kurtosis"],
+            max_kurtosis: float = DEFAULTS["max_kurtosis"], device: int = 0) -> DKI:
+    """Fit the diffusion and kurtosis tensors to multi-shell DWIs and return a `DKI` structure.  mk is the mean of the apparent
+    kurtosis over the half sphere of `odf_dirs`.  device: a GPU index, or _lib.DEVICE_ALL for the device set declared with
+    fibers_jl_amd.init() (z-slab sharding, as dti_fit)."""
+    bval, bvec = _check_tables(dwi)
+    L = _lib.lib()
+    vol = _dwi_arg(dwi)
+    nx, ny, nz, nvol = vol.shape
+    m, mdt = _mask_checked(mask, (nx, ny, nz))
+    v = _verts(odf_dirs)
+    outs = {k: MRI.like(mask if isinstance(mask, MRI) else dwi, _nframes(k)) for k in DKI_FIELDS}
+    o = _lib.DkiOut(*[outs[k].vol.ctypes.data for k in DKI_FIELDS])
+    p = _params(min_signal, min_diffusivity, min_kurtosis, max_kurtosis)
+    _lib.check(L.fib_dki_fit(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
+                             bval.ctypes.data, bvec.ctypes.data, v.ctypes.data, v.shape[0], C.byref(p), C.byref(o)))
+    return DKI(**outs)
+
+
+class DkiPlan:
+    """The DKI tables (pseudo-inverse columns, direction table of `odf_dirs`, limits) resident on one GPU"""
+
+    def __init__(self, bval, bvec, odf_dirs: ODF = sphere_642, min_signal: float = DEFAULTS["min_signal"],
+                 min_diffusivity: float = DEFAULTS["min_diffusivity"], min_kurtosis: float = DEFAULTS["min_kurtosis"],
+                 max_kurtosis: float = DEFAULTS["max_kurtosis"], device: int = 0):
+        self._h = C.c_void_p()
+        self.device = device
+        bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
+        self.nvol = int(bval.shape[0])
+        bv = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
+        if bv.shape[0] != self.nvol:
+            raise ValueError("gradient table must be [%d x 3], got %s" % (self.nvol, bv.shape))
+        v = _verts(odf_dirs)
+        self.ndir = odf_dirs.nvert
+        p = _params(min_signal, min_diffusivity, min_kurtosis, max_kurtosis)
+        _lib.check(_lib.lib().fib_dki_plan_create(device, bval.ctypes.data, bv.ctypes.data, self.nvol, v.ctypes.data, v.shape[0],
+                                                  C.byref(p), C.byref(self._h)))
+
+    def tables(self):
+        """(A [nvol, 22], pA [22, nvol], dirs [ndir, 21])"""
+        A = np.zeros((self.nvol, 22), np.float32, order="F")
+        pA = np.zeros((22, self.nvol), np.float32, order="F")
+        dirs = np.zeros((self.ndir, 21), np.float32)
+        _lib.check(_lib.lib().fib_dki_plan_tables(self._h, A.ctypes.data, pA.ctypes.data, dirs.ctypes.data))
+        return A, pA, dirs
+
+    def close(self):
+        if self._h:
+            _lib.lib().fib_dki_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def dki_fit_device(plan: DkiPlan, dwi, mask, out=None, stream=None, kt=True):
+    """dwi: float32 CUDA tensor [nvol, nvox] (planar), mask: uint8 CUDA tensor [nvox].  Returns a dict of tensors: scalars [nvox],
+    eigenvectors [3, nvox], kt [15, nvox].  `out` without a "kt" entry (or kt=False when the outputs are allocated here) skips
+    the kurtosis tensor."""
+    import torch
+    _chk_dev(dwi, torch.float32, "dwi")
+    _chk_dev(mask, torch.uint8, "mask")
+    nvox = mask.numel()
+    if dwi.numel() != nvox * plan.nvol:
+        raise ValueError("dwi has %d elements, expected nvol*nvox = %d" % (dwi.numel(), nvox * plan.nvol))
+    if out is None:
+        out = {k: torch.empty((_nframes(k), nvox) if _nframes(k) > 1 else (nvox,), dtype=torch.float32, device=dwi.device)
+               for k in DKI_FIELDS if kt or k != "kt"}
+    for k in DKI_FIELDS:
+        if k in out:
+            _chk_dev(out[k], torch.float32, k)
+            if out[k].numel() != _nframes(k) * nvox:
+                raise ValueError("out[%r] has %d elements, expected %d" % (k, out[k].numel(), _nframes(k) * nvox))
+    o = _lib.DkiOut(*[out[k].data_ptr() if k in out else None for k in DKI_FIELDS])
+    _lib.check(_lib.lib().fibd_dki_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, C.byref(o), _stream_ptr(stream)))
+    return out

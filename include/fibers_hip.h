@@ -166,6 +166,40 @@ int fibd_st_recon(const float *vol, int nx, int ny, int nz, int zin0, int nzin, 
  * per-voxel pinv branch (dti.jl:297-298, 206-207); synchronises `stream`. */
 int fibd_dti_last_partial_count(const fib_dti_plan *plan, void *stream, int64_t *count);
 
+/* ---- diffusion kurtosis imaging (not in the reference; definition in DESIGN.md §5) ----
+ * ln S = ln S0 - b g'Dg + (b^2 / 6) sum g_i g_j g_k g_l V_ijkl with V = MD^2 W.  22 unknowns per voxel: d[0..5] = Dxx Dxy Dxz Dyy Dyz Dzz,
+ * d[6..20] = V in the monomial order xxxx yyyy zzzz xxxy xxxz xyyy yyyz xzzz yzzz xxyy xxzz yyzz xxyz xyyz xyzz, d[21] = ln S0. */
+typedef struct fib_dki_plan fib_dki_plan;
+typedef struct {
+    float min_signal;        /* samples are clamped to this from below before the logarithm (1e-4) */
+    float min_diffusivity;   /* floor of D(n) in K(n) = V(n) / D(n)^2 (1e-6) */
+    float min_kurtosis;      /* K(n) is clipped to [min_kurtosis, max_kurtosis] (-3/7, 10); no clip when min >= max */
+    float max_kurtosis;
+} fib_dki_params;
+/* the ten volumes of fib_dti_out, then mean / axial / radial kurtosis [nvox] and the kurtosis tensor W [15][nvox] (NULL: not written) */
+typedef struct {
+    float *s0, *eigval1, *eigval2, *eigval3;
+    float *eigvec1, *eigvec2, *eigvec3;
+    float *rd, *md, *fa;
+    float *mk, *ak, *rk, *kt;
+} fib_dki_out;
+/* Host only (no device needed): the design A [nvol x 22] with b in ms/um^2 and pA [22 x nvol] = pinv(A) with rows 0-5 scaled by 1e-3 and
+ * rows 6-20 by 1e-6, so that d = pA log(s) is in mm^2/s and mm^4/s^2; both built in float64 and rounded once, column-major; A, pA may be
+ * NULL.  *rank: the rank of A under pinv's cut-off sigma > eps(Float32) * min(m, n) * sigma_max.  A rank below 22 is FIB_ERR_INVALID
+ * (DKI needs a b ~ 0 frame and two non-zero shells); the tables and *rank are filled all the same. */
+int fib_dki_design(const float *bval, const float *bvec, int nvol, float *A, float *pA, int *rank);
+/* verts [nverts x 3] column-major: mk is the mean of K(n) over rows 0 .. nverts/2 - 1.  params NULL: the defaults. */
+int fib_dki_plan_create(int device, const float *bval, const float *bvec, int nvol, const float *verts, int nverts,
+                        const fib_dki_params *params, fib_dki_plan **plan);
+void fib_dki_plan_destroy(fib_dki_plan *plan);
+/* host copies: A, pA as fib_dki_design's; dirs [nverts/2][21] row-major, the 6 quadratic (off-diagonals doubled) and 15
+ * multiplicity-weighted quartic monomials of every direction of mk.  Any of them may be NULL. */
+int fib_dki_plan_tables(const fib_dki_plan *plan, float *A, float *pA, float *dirs);
+/* dwi [nvol][nvox] planar, mask uint8 [nvox].  Every output is written in every voxel: zeros outside the mask and where max(s) <= 0 or a
+ * sample is NaN; elsewhere d = pA log(max(s, min_signal)) (no row-subset fit: the clamp is the rule for non-positive samples). */
+int fibd_dki_fit(const fib_dki_plan *plan, const float *dwi, const uint8_t *mask, int64_t nvox,
+                 const fib_dki_out *out, void *stream);
+
 /* gqi_rec / dsi_rec volume loop + find_peaks! + peak/qa extraction (gqi.jl:132-162,
  * dsi.jl:197-261).  odf [nvox*nvert] planar; pdf [nvox*nvol] (DSI plans only, else NULL);
  * peak[k] [nvox*3] planar, qa[k] [nvox].  `flags` is a bit set:
@@ -607,6 +641,10 @@ void fib_shutdown(void);
 int fib_dti_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, const float *bvec,
                 const fib_dti_out *out);
+/* dki_fit: fibd_dki_fit on host arrays, sharded and chunked like fib_dti_fit; the same missing-table errors.  kt [nvox*15] or NULL. */
+int fib_dki_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
+                const void *mask, int mask_dtype, const float *bval, const float *bvec,
+                const float *verts, int nverts, const fib_dki_params *params, const fib_dki_out *out);
 /* adc_fit(dwi::MRI, mask::MRI) (dti.jl:164) */
 /* host-buffer form of fibd_st_eigen (structens.jl:13-37) */
 int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigvec, float *eigval);

@@ -73,6 +73,60 @@ function adc_fit(dwi::MRI, mask::MRI; device::Integer=0)
   return adc, s0
 end
 
+# layout: fib_dki_params sizeof 16: min_signal@0 min_diffusivity@4 min_kurtosis@8 max_kurtosis@12
+struct FibDkiParams
+  min_signal::Cfloat; min_diffusivity::Cfloat; min_kurtosis::Cfloat; max_kurtosis::Cfloat
+end
+
+# layout: fib_dki_out sizeof 112: s0@0 eigval1@8 eigval2@16 eigval3@24 eigvec1@32 eigvec2@40 eigvec3@48 rd@56 md@64 fa@72 mk@80 ak@88 rk@96 kt@104
+struct FibDkiOut
+  s0::Ptr{Float32}; eigval1::Ptr{Float32}; eigval2::Ptr{Float32}; eigval3::Ptr{Float32}
+  eigvec1::Ptr{Float32}; eigvec2::Ptr{Float32}; eigvec3::Ptr{Float32}
+  rd::Ptr{Float32}; md::Ptr{Float32}; fa::Ptr{Float32}
+  mk::Ptr{Float32}; ak::Ptr{Float32}; rk::Ptr{Float32}; kt::Ptr{Float32}
+end
+
+"Container for outputs of a DKI fit: the fields of `DTI`, mean / axial / radial kurtosis and the kurtosis tensor W (15 frames)"
+struct DKI
+  s0::MRI; eigval1::MRI; eigval2::MRI; eigval3::MRI; eigvec1::MRI; eigvec2::MRI; eigvec3::MRI; rd::MRI; md::MRI; fa::MRI
+  mk::MRI; ak::MRI; rk::MRI; kt::MRI
+end
+
+"dki_design(bval, bvec) — the DKI design (b in ms/um^2), its scaled pseudo-inverse and its rank, on the host (include/fibers_hip.h)"
+function dki_design(bval::Vector{Float32}, bvec::Matrix{Float32})
+  nvol = length(bval)
+  A = zeros(Float32, nvol, 22); pA = zeros(Float32, 22, nvol); rank = Ref{Cint}(0)
+  fib_check(ccall((:fib_dki_design, libfibers), Cint, (Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Float32}, Ptr{Float32}, Ref{Cint}),
+                  bval, bvec, nvol, A, pA, rank))
+  return A, pA, Int(rank[])
+end
+
+"dki_fit(dwi, mask, odf_dirs) — diffusion kurtosis fit with MK / AK / RK maps (not in the reference; DESIGN.md §5)"
+function dki_fit(dwi::MRI, mask::MRI, odf_dirs::ODF=sphere_642; min_signal::Real=1f-4, min_diffusivity::Real=1f-6,
+                 min_kurtosis::Real=-3f0/7f0, max_kurtosis::Real=10f0, device::Integer=0)
+  isempty(dwi.bval) && error("Missing b-value table from input DWI structure")
+  isempty(dwi.bvec) && error("Missing gradient table from input DWI structure")
+  nx, ny, nz, nvol = size(dwi.vol)
+  S0 = MRI(mask, 1, Float32); E1 = MRI(mask, 1, Float32); E2 = MRI(mask, 1, Float32); E3 = MRI(mask, 1, Float32)
+  V1 = MRI(mask, 3, Float32); V2 = MRI(mask, 3, Float32); V3 = MRI(mask, 3, Float32)
+  RD = MRI(mask, 1, Float32); MD = MRI(mask, 1, Float32); FA = MRI(mask, 1, Float32)
+  MK = MRI(mask, 1, Float32); AK = MRI(mask, 1, Float32); RK = MRI(mask, 1, Float32); KT = MRI(mask, 15, Float32)
+  vol = dwi.vol::Array{Float32,4}; m = mask.vol; verts = odf_dirs.vertices
+  par = Ref(FibDkiParams(min_signal, min_diffusivity, min_kurtosis, max_kurtosis))
+  GC.@preserve vol m verts S0 E1 E2 E3 V1 V2 V3 RD MD FA MK AK RK KT begin
+    out = Ref(FibDkiOut(pointer(S0.vol), pointer(E1.vol), pointer(E2.vol), pointer(E3.vol),
+                        pointer(V1.vol), pointer(V2.vol), pointer(V3.vol),
+                        pointer(RD.vol), pointer(MD.vol), pointer(FA.vol),
+                        pointer(MK.vol), pointer(AK.vol), pointer(RK.vol), pointer(KT.vol)))
+    fib_check(ccall((:fib_dki_fit, libfibers), Cint,
+                    (Cint, Ptr{Float32}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32},
+                     Ptr{Float32}, Cint, Ref{FibDkiParams}, Ref{FibDkiOut}),
+                    device, vol, nx, ny, nz, nvol, m, FIB_DTYPE[eltype(m)] | FIB_MASK_OUTPUTS_ZEROED, dwi.bval, dwi.bvec,
+                    verts, size(verts, 1), par, out))
+  end
+  return DKI(S0, E1, E2, E3, V1, V2, V3, RD, MD, FA, MK, AK, RK, KT)
+end
+
 "find_peaks(odf, odf_dirs) — find_peaks!(W) (gqi.jl:180-201) for a whole ODF volume [nx,ny,nz,nvert]:
  returns (isort_top [nx,ny,nz,3] 1-based first-half vertex rows, 0 where absent; nvalid [nx,ny,nz])"
 function find_peaks(odf::MRI, odf_dirs::ODF=sphere_642; device::Integer=0)
