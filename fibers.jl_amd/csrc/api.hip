@@ -11,6 +11,11 @@
 //   * the only exchange step of the fits, odfmax = maximum(mean(odf, dims=4)) (gqi.jl:164, dsi.jl:263), is one float per
 //     chunk: reduced on the host, then qa ./= odfmax runs on every device before the qa volumes are copied out;
 //   * plans (the reference's work structs) are cached per device, keyed by the tables they were built from.
+// The voxel fits share their argument handling (fit_call) and their per-worker body (fit_run); what a form keeps is its own checks, its
+// rows, its plan and the layout of a chunk on the device.
+// The tractogram forms (fib_str_*) run on one device and copy chunk after chunk with blocking copies: each takes a TmLease (the worker,
+// its lock, the device, the buffer set); the five that take lines of any length walk them with tm_walk_lines, in the chunks that
+// fibh::next_line_chunk cuts (host_tier.h), and keep a body per chunk.
 #include <sched.h>
 #include <sys/mman.h>
 
@@ -126,12 +131,8 @@ struct PinBuf {                                          // grow-only pinned hos
     ~PinBuf() { release(); }
 };
 
-struct CachedPlan { std::string key; void *plan = nullptr; int kind = 0; uint64_t stamp = 0; };   // kind 0: dti/adc, 1: odf, 2: dki
-inline void destroy_cached(const CachedPlan &c) {
-    if (c.kind == 0) fib_dti_plan_destroy((fib_dti_plan *)c.plan);
-    else if (c.kind == 1) fib_odf_plan_destroy((fib_odf_plan *)c.plan);
-    else fib_dki_plan_destroy((fib_dki_plan *)c.plan);
-}
+// a cached plan of any type: `destroy` releases it and tells the plan types apart (plan cache, below)
+struct CachedPlan { std::string key; void *plan = nullptr; void (*destroy)(void *) = nullptr; uint64_t stamp = 0; };
 
 struct DevState {
     int device = 0;
@@ -153,7 +154,7 @@ struct DevState {
         fib::DevBuf<uint8_t> mask, mout, flags;
         fib::DevBuf<int64_t> seeds, sidx;
         fib::DevBuf<int32_t> npts;
-    } sb;
+    };
     // device buffers of fib_str_density / fib_str_sample / fib_str_stats (grow-only): one chunk of points and what belongs to it, the
     // resident volume (density map or sampled volume), the offset scratch
     struct TractMapBufs {
@@ -174,7 +175,10 @@ struct DevState {
         fib::DevBuf<uint8_t> flip;
         fib::DevBuf<double> sums;
         fib::DevBuf<uint32_t> bcnt;
-    } tm;
+    };
+    // each set is created by its first user (stream_worker, TmLease) and released as a whole by trim()
+    std::unique_ptr<StreamBufs> sb;
+    std::unique_ptr<TractMapBufs> tm;
 
     int init(int nthreads) {
         if (ready) return FIB_OK;
@@ -201,18 +205,12 @@ struct DevState {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(s_in); (void)hipStreamSynchronize(s_cmp); (void)hipStreamSynchronize(s_out);
         for (int b = 0; b < NBUF; b++) { pin_in[b].release(); pin_out[b].release(); dev_in[b].release(); dev_out[b].release(); }
-        sb.vec.release(); sb.f.release(); sb.fa.release(); sb.field.release(); sb.sub.release(); sb.lcms.release(); sb.xyz.release();
-        sb.mask.release(); sb.mout.release(); sb.flags.release(); sb.seeds.release(); sb.sidx.release(); sb.npts.release();
-        tm.xyz.release(); tm.vol.release(); tm.scal.release(); tm.props.release(); tm.npts.release(); tm.dens.release(); tm.work.release();
-        tm.nout.release();
-        tm.rois.release(); tm.keep.release(); tm.roibits.release(); tm.hits.release(); tm.cmat.release(); tm.labels.release(); tm.remap.release();
-        tm.assign.release(); tm.wmat.release();
-        tm.lines.release(); tm.models.release(); tm.dist.release(); tm.dall.release(); tm.label.release(); tm.flip.release(); tm.sums.release();
-        tm.bcnt.release();
+        sb.reset();
+        tm.reset();
         if (ws) { fibd_stream_ws_destroy(ws); ws = nullptr; }
     }
     void drop_plans() {
-        for (auto &c : plans) destroy_cached(c);
+        for (auto &c : plans) c.destroy(c.plan);
         plans.clear();
     }
     ~DevState() {
@@ -272,18 +270,24 @@ int workers_for(int device, std::vector<Worker> &out) {
 // ---- plan cache ----------------------------------------------------------------------------------------------------------------
 void key_add(std::string &k, const void *p, size_t bytes) { k.append((const char *)&bytes, sizeof bytes); if (p) k.append((const char *)p, bytes); }
 
-template <typename MakeFn>
-int cached_plan(DevState &d, int kind, const std::string &key, MakeFn make, void **plan) {
-    for (auto &c : d.plans) if (c.kind == kind && c.key == key) { c.stamp = ++d.clock; *plan = c.plan; return FIB_OK; }
-    void *p = nullptr;
+template <typename Plan, void (*Destroy)(Plan *)>
+void destroy_plan(void *p) { Destroy(static_cast<Plan *>(p)); }
+
+// the worker's plan of type Plan for `key`, made by make(Plan **) where the cache has none.  An entry matches on its key and its
+// destroy function: plans of different types never stand for each other, whatever their keys.
+template <typename Plan, void (*Destroy)(Plan *), typename MakeFn>
+int cached_plan(DevState &d, const std::string &key, MakeFn make, Plan **plan) {
+    void (*const destroy)(void *) = &destroy_plan<Plan, Destroy>;
+    for (auto &c : d.plans) if (c.destroy == destroy && c.key == key) { c.stamp = ++d.clock; *plan = static_cast<Plan *>(c.plan); return FIB_OK; }
+    Plan *p = nullptr;
     RC(make(&p));
     if (d.plans.size() >= 4) {                           // evict the least recently used
         size_t lru = 0;
         for (size_t i = 1; i < d.plans.size(); i++) if (d.plans[i].stamp < d.plans[lru].stamp) lru = i;
-        destroy_cached(d.plans[lru]);
+        d.plans[lru].destroy(d.plans[lru].plan);
         d.plans.erase(d.plans.begin() + lru);
     }
-    d.plans.push_back(CachedPlan{key, p, kind, ++d.clock});
+    d.plans.push_back(CachedPlan{key, p, destroy, ++d.clock});
     *plan = p;
     return FIB_OK;
 }
@@ -425,78 +429,89 @@ extern "C" void fib_shutdown(void) try {
 // dti_fit / adc_fit
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {
+// What the voxel fits (fib_dti_fit, fib_adc_fit, fib_dki_fit, the ODF forms) share of a call's arguments, in the order every form checks
+// them: the tables, the tessellation where there is one (tess_ok), the form's pointer arguments (ptrs_ok), the dimensions (with
+// dims_more_ok: what else the form counts among them, under its own dims_msg), the FIB_MASK_OUTPUTS_ZEROED bit, the mask type, the
+// form's output volumes (outs_ok, outs_msg), the workers.
+struct FitCall {
+    int mask_dtype = 0;                                  // without the FIB_MASK_OUTPUTS_ZEROED bit
+    bool zeroed = false;
+    int64_t nvox = 0;
+    std::vector<Worker> ws;
+};
+int fit_call(FitCall &c, int device, const float *bval, int nvol, bool bvec_ok, bool ptrs_ok, int nx, int ny, int nz, int mask_dtype, bool outs_ok,
+             const char *outs_msg = "NULL output volume", bool tess_ok = true, bool dims_more_ok = true,
+             const char *dims_msg = "volume dimensions must be positive") {
+    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
+    FIB_CHECK(bvec_ok, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    FIB_CHECK(tess_ok, FIB_ERR_INVALID, "invalid ODF tessellation");
+    FIB_CHECK(ptrs_ok, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0 && dims_more_ok, FIB_ERR_INVALID, "%s", dims_msg);
+    c.zeroed = (mask_dtype & FIB_MASK_OUTPUTS_ZEROED) != 0;
+    c.mask_dtype = mask_dtype & ~FIB_MASK_OUTPUTS_ZEROED;
+    FIB_CHECK(dtype_size(c.mask_dtype) > 0, FIB_ERR_INVALID, "unknown mask dtype %d", c.mask_dtype);
+    FIB_CHECK(outs_ok, FIB_ERR_INVALID, "%s", outs_msg);
+    c.nvox = (int64_t)nx * ny * nz;
+    return workers_for(device, c.ws);
+}
+
+// A fit on every worker of the call: its slab of the volume, its plan (plan_for(d, &plan)), the slab's live map where packing pays, the
+// chunks.  fit(plan, din, dmask, n, dout, stream) is the form's fibd_* call on one chunk: n voxels, the rows of `outs` back to back in dout.
+template <typename Plan, typename PlanFor, typename Fit>
+int fit_run(const FitCall &c, const std::vector<Rows> &ins, const void *mask, const std::vector<Rows> &outs, PlanFor plan_for, Fit fit) {
+    int rows_in = 0, rows_out = 0;
+    for (auto &r : ins) rows_in += r.nrows;
+    for (auto &r : outs) rows_out += r.nrows;
+    return for_each_worker(c.ws, [&](int i, DevState &d) -> int {
+        int64_t v0, v1;
+        slab(c.nvox, (int)c.ws.size(), i, v0, v1);
+        Plan *plan = nullptr;
+        RC(plan_for(d, &plan));
+        LiveMap lm;
+        const LiveMap *use = nullptr;
+        RC(live_map_for(d, mask, c.mask_dtype, v0, v1, lm, &use));
+        return run_chunks(d, v0, v1, c.nvox, ins, mask, c.mask_dtype, outs, pick_chunk(use ? use->nlive : v1 - v0, rows_in, rows_out),
+                          [&](int, int64_t, int64_t n, const float *din, const uint8_t *dm, float *b, hipStream_t st) -> int {
+                              return fit(plan, din, dm, n, b, st);
+                          }, use, c.zeroed);
+    });
+}
+
 int dti_plan_for(DevState &d, const float *bval, const float *bvec, int nvol, fib_dti_plan **plan) {
     std::string key;
     key_add(key, bval, sizeof(float) * nvol);
     key_add(key, bvec, bvec ? sizeof(float) * 3 * nvol : 0);
-    void *p = nullptr;
-    RC(cached_plan(d, 0, key, [&](void **out) { fib_dti_plan *q = nullptr; int rc = fib_dti_plan_create(d.device, bval, bvec, nvol, &q); *out = q; return rc; }, &p));
-    *plan = (fib_dti_plan *)p;
-    return FIB_OK;
+    return cached_plan<fib_dti_plan, fib_dti_plan_destroy>(d, key, [&](fib_dti_plan **p) { return fib_dti_plan_create(d.device, bval, bvec, nvol, p); }, plan);
 }
 }  // namespace
 
 extern "C" int fib_dti_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                            const void *mask, int mask_dtype, const float *bval, const float *bvec,
                            const fib_dti_out *out) try {
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
-    FIB_CHECK(dwi && mask && out, FIB_ERR_INVALID, "NULL argument");
-    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
-    const bool zeroed = (mask_dtype & FIB_MASK_OUTPUTS_ZEROED) != 0;
-    mask_dtype &= ~FIB_MASK_OUTPUTS_ZEROED;
-    FIB_CHECK(dtype_size(mask_dtype) > 0, FIB_ERR_INVALID, "unknown mask dtype %d", mask_dtype);
-    FIB_CHECK(out->s0 && out->eigval1 && out->eigval2 && out->eigval3 && out->eigvec1 && out->eigvec2 && out->eigvec3 && out->rd && out->md && out->fa,
-              FIB_ERR_INVALID, "NULL output volume");
-    const int64_t nvox = (int64_t)nx * ny * nz;
-    std::vector<Worker> ws;
-    RC(workers_for(device, ws));
+    FitCall c;
+    RC(fit_call(c, device, bval, nvol, bvec != nullptr, dwi && mask && out, nx, ny, nz, mask_dtype,
+                out && out->s0 && out->eigval1 && out->eigval2 && out->eigval3 && out->eigvec1 && out->eigvec2 && out->eigvec3 && out->rd && out->md && out->fa));
     const std::vector<Rows> ins = {{dwi, nullptr, nvol}};
     const std::vector<Rows> outs = {{nullptr, out->s0, 1}, {nullptr, out->eigval1, 1}, {nullptr, out->eigval2, 1}, {nullptr, out->eigval3, 1},
                                     {nullptr, out->eigvec1, 3}, {nullptr, out->eigvec2, 3}, {nullptr, out->eigvec3, 3},
                                     {nullptr, out->rd, 1}, {nullptr, out->md, 1}, {nullptr, out->fa, 1}};
-    return for_each_worker(ws, [&](int i, DevState &d) -> int {
-        int64_t v0, v1;
-        slab(nvox, (int)ws.size(), i, v0, v1);
-        fib_dti_plan *plan = nullptr;
-        RC(dti_plan_for(d, bval, bvec, nvol, &plan));
-        LiveMap lm;
-        const LiveMap *use = nullptr;
-        RC(live_map_for(d, mask, mask_dtype, v0, v1, lm, &use));
-        return run_chunks(d, v0, v1, nvox, ins, mask, mask_dtype, outs, pick_chunk(use ? use->nlive : v1 - v0, nvol, 16),
-                          [&](int, int64_t, int64_t n, const float *din, const uint8_t *dm, float *b, hipStream_t st) -> int {
-                              fib_dti_out dev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 7 * n, b + 10 * n, b + 13 * n, b + 14 * n, b + 15 * n};
-                              return fibd_dti_fit(plan, din, dm, n, &dev, st);
-                          }, use, zeroed);
-    });
+    return fit_run<fib_dti_plan>(c, ins, mask, outs, [&](DevState &d, fib_dti_plan **p) { return dti_plan_for(d, bval, bvec, nvol, p); },
+                                 [](const fib_dti_plan *plan, const float *din, const uint8_t *dm, int64_t n, float *b, hipStream_t st) -> int {
+                                     fib_dti_out dev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 7 * n, b + 10 * n, b + 13 * n, b + 14 * n, b + 15 * n};
+                                     return fibd_dti_fit(plan, din, dm, n, &dev, st);
+                                 });
 } FIB_API_CATCH
 
 extern "C" int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                            const void *mask, int mask_dtype, const float *bval, float *adc, float *s0) try {
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(dwi && mask && adc && s0, FIB_ERR_INVALID, "NULL argument");
-    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
-    const bool zeroed = (mask_dtype & FIB_MASK_OUTPUTS_ZEROED) != 0;
-    mask_dtype &= ~FIB_MASK_OUTPUTS_ZEROED;
-    FIB_CHECK(dtype_size(mask_dtype) > 0, FIB_ERR_INVALID, "unknown mask dtype %d", mask_dtype);
-    const int64_t nvox = (int64_t)nx * ny * nz;
-    std::vector<Worker> ws;
-    RC(workers_for(device, ws));
+    FitCall c;
+    RC(fit_call(c, device, bval, nvol, true, dwi && mask && adc && s0, nx, ny, nz, mask_dtype, true));
     const std::vector<Rows> ins = {{dwi, nullptr, nvol}};
     const std::vector<Rows> outs = {{nullptr, adc, 1}, {nullptr, s0, 1}};
-    return for_each_worker(ws, [&](int i, DevState &d) -> int {
-        int64_t v0, v1;
-        slab(nvox, (int)ws.size(), i, v0, v1);
-        fib_dti_plan *plan = nullptr;
-        RC(dti_plan_for(d, bval, nullptr, nvol, &plan));
-        LiveMap lm;
-        const LiveMap *use = nullptr;
-        RC(live_map_for(d, mask, mask_dtype, v0, v1, lm, &use));
-        return run_chunks(d, v0, v1, nvox, ins, mask, mask_dtype, outs, pick_chunk(use ? use->nlive : v1 - v0, nvol, 2),
-                          [&](int, int64_t, int64_t n, const float *din, const uint8_t *dm, float *b, hipStream_t st) -> int {
-                              return fibd_adc_fit(plan, din, dm, n, b, b + n, st);
-                          }, use, zeroed);
-    });
+    return fit_run<fib_dti_plan>(c, ins, mask, outs, [&](DevState &d, fib_dti_plan **p) { return dti_plan_for(d, bval, nullptr, nvol, p); },
+                                 [](const fib_dti_plan *plan, const float *din, const uint8_t *dm, int64_t n, float *b, hipStream_t st) -> int {
+                                     return fibd_adc_fit(plan, din, dm, n, b, b + n, st);
+                                 });
 } FIB_API_CATCH
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -505,18 +520,11 @@ extern "C" int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz,
 extern "C" int fib_dki_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                            const void *mask, int mask_dtype, const float *bval, const float *bvec,
                            const float *verts, int nverts, const fib_dki_params *params, const fib_dki_out *out) try {
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
-    FIB_CHECK(dwi && mask && out && verts, FIB_ERR_INVALID, "NULL argument");
-    FIB_CHECK(nx > 0 && ny > 0 && nz > 0 && nverts >= 2, FIB_ERR_INVALID, "volume dimensions and the vertex count must be positive");
-    const bool zeroed = (mask_dtype & FIB_MASK_OUTPUTS_ZEROED) != 0;
-    mask_dtype &= ~FIB_MASK_OUTPUTS_ZEROED;
-    FIB_CHECK(dtype_size(mask_dtype) > 0, FIB_ERR_INVALID, "unknown mask dtype %d", mask_dtype);
-    FIB_CHECK(out->s0 && out->eigval1 && out->eigval2 && out->eigval3 && out->eigvec1 && out->eigvec2 && out->eigvec3 && out->rd && out->md && out->fa &&
-              out->mk && out->ak && out->rk, FIB_ERR_INVALID, "NULL output volume");
-    const int64_t nvox = (int64_t)nx * ny * nz;
-    std::vector<Worker> ws;
-    RC(workers_for(device, ws));
+    FitCall c;
+    RC(fit_call(c, device, bval, nvol, bvec != nullptr, dwi && mask && out && verts, nx, ny, nz, mask_dtype,
+                out && out->s0 && out->eigval1 && out->eigval2 && out->eigval3 && out->eigvec1 && out->eigvec2 && out->eigvec3 && out->rd && out->md && out->fa &&
+                    out->mk && out->ak && out->rk,
+                "NULL output volume", true, nverts >= 2, "volume dimensions and the vertex count must be positive"));
     const std::vector<Rows> ins = {{dwi, nullptr, nvol}};
     std::vector<Rows> outs = {{nullptr, out->s0, 1}, {nullptr, out->eigval1, 1}, {nullptr, out->eigval2, 1}, {nullptr, out->eigval3, 1},
                               {nullptr, out->eigvec1, 3}, {nullptr, out->eigvec2, 3}, {nullptr, out->eigvec3, 3},
@@ -529,22 +537,16 @@ extern "C" int fib_dki_fit(int device, const float *dwi, int nx, int ny, int nz,
     key_add(key, bvec, sizeof(float) * 3 * nvol);
     key_add(key, verts, sizeof(float) * 3 * nverts);
     key_add(key, params, params ? sizeof *params : 0);
-    return for_each_worker(ws, [&](int i, DevState &d) -> int {
-        int64_t v0, v1;
-        slab(nvox, (int)ws.size(), i, v0, v1);
-        void *pp = nullptr;
-        RC(cached_plan(d, 2, key, [&](void **o) { fib_dki_plan *q = nullptr; int rc = fib_dki_plan_create(d.device, bval, bvec, nvol, verts, nverts, params, &q); *o = q; return rc; }, &pp));
-        const fib_dki_plan *plan = (const fib_dki_plan *)pp;
-        LiveMap lm;
-        const LiveMap *use = nullptr;
-        RC(live_map_for(d, mask, mask_dtype, v0, v1, lm, &use));
-        return run_chunks(d, v0, v1, nvox, ins, mask, mask_dtype, outs, pick_chunk(use ? use->nlive : v1 - v0, nvol, want_kt ? 34 : 19),
-                          [&](int, int64_t, int64_t n, const float *din, const uint8_t *dm, float *b, hipStream_t st) -> int {
-                              fib_dki_out dev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 7 * n, b + 10 * n, b + 13 * n, b + 14 * n, b + 15 * n,
-                                              b + 16 * n, b + 17 * n, b + 18 * n, want_kt ? b + 19 * n : nullptr};
-                              return fibd_dki_fit(plan, din, dm, n, &dev, st);
-                          }, use, zeroed);
-    });
+    return fit_run<fib_dki_plan>(c, ins, mask, outs,
+                                 [&](DevState &d, fib_dki_plan **p) {
+                                     return cached_plan<fib_dki_plan, fib_dki_plan_destroy>(d, key, [&](fib_dki_plan **q) {
+                                         return fib_dki_plan_create(d.device, bval, bvec, nvol, verts, nverts, params, q); }, p);
+                                 },
+                                 [&](const fib_dki_plan *plan, const float *din, const uint8_t *dm, int64_t n, float *b, hipStream_t st) -> int {
+                                     fib_dki_out dev{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 7 * n, b + 10 * n, b + 13 * n, b + 14 * n, b + 15 * n,
+                                                     b + 16 * n, b + 17 * n, b + 18 * n, want_kt ? b + 19 * n : nullptr};
+                                     return fibd_dki_fit(plan, din, dm, n, &dev, st);
+                                 });
 } FIB_API_CATCH
 
 extern "C" int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigvec, float *eigval) try {
@@ -650,18 +652,47 @@ int tm_host_check(const int32_t *npts, int64_t nlines, int64_t npoints) {
     return FIB_OK;
 }
 
-// lines [l0, *l1) with at most TM_CHUNK_POINTS points (at least one line), *np their points
-void tm_next_chunk(const int32_t *npts, int64_t nlines, int64_t l0, int64_t *l1, int64_t *np) {
-    int64_t l = l0, n = 0;
-    while (l < nlines && (l == l0 || n + npts[l] <= TM_CHUNK_POINTS)) n += npts[l++];
-    *l1 = l; *np = n;
-}
+// One call of a tractogram host form on its worker.  take() refuses FIB_DEVICE_ALL, finds the worker of `device`, waits for its lock,
+// makes the device current (the caller's comes back when the lease goes) and hands out the worker's buffer set, b.
+struct TmLease {
+    Worker wk;
+    std::unique_lock<std::mutex> lk;
+    std::unique_ptr<fib::DeviceGuard> guard;
+    DevState::TractMapBufs *b = nullptr;
+    int take(int device) {
+        FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "the tract maps, the selection and the connectome run on one device (FIB_DEVICE_ALL is not supported)");
+        std::vector<Worker> ws;
+        RC(workers_for(device, ws));
+        wk = ws[0];
+        lk = std::unique_lock<std::mutex>(wk->mu);
+        guard.reset(new fib::DeviceGuard());
+        RC(wk->init(copy_threads(1)));
+        if (!wk->tm) wk->tm.reset(new DevState::TractMapBufs());
+        b = wk->tm.get();
+        return FIB_OK;
+    }
+};
 
-int tm_worker(int device, Worker &w) {
-    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "the tract maps, the selection and the connectome run on one device (FIB_DEVICE_ALL is not supported)");
-    std::vector<Worker> ws;
-    RC(workers_for(device, ws));
-    w = ws[0];
+// The lines of a call in chunks (fibh::next_line_chunk: at most TM_CHUNK_POINTS points and max_lines lines each).  Per chunk: the work
+// area work_size asks for, npts and xyz of the chunk on the device (b.work, b.npts, b.xyz), then body(l0, nl, p0, np, work bytes) for
+// lines [l0, l0 + nl) = points [p0, p0 + np).  Copies block on the NULL stream, so a body's read-back comes behind its kernels.
+template <typename Body>
+int tm_walk_lines(DevState::TractMapBufs &b, const float *xyz, const int32_t *npts, int64_t nlines, int (*work_size)(int64_t, size_t *),
+                  int64_t max_lines, Body body) {
+    int64_t p0 = 0;
+    for (int64_t l0 = 0; l0 < nlines;) {
+        const fibh::LineChunk c = fibh::next_line_chunk(npts, nlines, l0, TM_CHUNK_POINTS, max_lines);
+        const int64_t nl = c.l1 - l0, np = c.np;
+        size_t wb = 0;
+        RC(work_size(nl, &wb));
+        RC(b.work.ensure(wb));
+        RC(b.npts.ensure((size_t)nl));
+        RC(b.xyz.ensure((size_t)3 * np));
+        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * (size_t)nl));
+        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(body(l0, nl, p0, np, wb));
+        p0 += np; l0 = c.l1;
+    }
     return FIB_OK;
 }
 }  // namespace
@@ -674,36 +705,23 @@ extern "C" int fib_str_density(int device, const float *xyz, const int32_t *npts
     FIB_CHECK(what >= FIB_DENSITY_POINTS && what <= FIB_DENSITY_ENDPOINTS, FIB_ERR_INVALID, "unknown density mode %d", mode);
     RC(tm_host_check(npts, nlines, npoints));
     FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
-    Worker wk;
-    RC(tm_worker(device, wk));
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
     const size_t nvox = (size_t)nx * ny * nz;
     RC(b.dens.ensure(nvox));
     RC(b.nout.ensure(1));
     if (mode & FIB_DENSITY_ACCUMULATE) RC(h2d(b.dens.p, density, sizeof(uint32_t) * nvox));
     else FIB_HIP(hipMemset(b.dens.p, 0, sizeof(uint32_t) * nvox));
     int64_t total_out = 0;
-    int64_t p0 = 0;
-    for (int64_t l0 = 0; l0 < nlines;) {
-        int64_t l1, np;
-        tm_next_chunk(npts, nlines, l0, &l1, &np);
-        size_t wb = 0;
-        RC(fibd_str_work_size(l1 - l0, &wb));
-        RC(b.work.ensure(wb));
-        RC(b.npts.ensure((size_t)(l1 - l0)));
-        RC(b.xyz.ensure((size_t)3 * np));
-        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * (size_t)(l1 - l0)));
-        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
-        RC(fibd_str_density(b.xyz.p, b.npts.p, l1 - l0, np, nx, ny, nz, what | FIB_DENSITY_ACCUMULATE, b.dens.p, b.nout.p, b.work.p, wb, nullptr));
+    RC(tm_walk_lines(b, xyz, npts, nlines, fibd_str_work_size, fibh::LINES_UNBOUNDED, [&](int64_t, int64_t nl, int64_t, int64_t np, size_t wb) -> int {
+        RC(fibd_str_density(b.xyz.p, b.npts.p, nl, np, nx, ny, nz, what | FIB_DENSITY_ACCUMULATE, b.dens.p, b.nout.p, b.work.p, wb, nullptr));
         int64_t out = 0;
-        RC(d2h(&out, b.nout.p, sizeof out));                   // (a blocking copy on the NULL stream: behind the kernels)
+        RC(d2h(&out, b.nout.p, sizeof out));
         FIB_CHECK(out >= 0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
         total_out += out;
-        p0 += np; l0 = l1;
-    }
+        return FIB_OK;
+    }));
     RC(d2h(density, b.dens.p, sizeof(uint32_t) * nvox));
     *n_outside = total_out;
     return FIB_OK;
@@ -714,13 +732,10 @@ extern "C" int fib_str_sample(int device, const float *xyz, int64_t npoints, con
     FIB_CHECK(npoints >= 0, FIB_ERR_INVALID, "npoints must not be negative");
     FIB_CHECK(nx > 0 && ny > 0 && nz > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
     FIB_CHECK(npoints == 0 || (xyz && vol && scalars), FIB_ERR_INVALID, "NULL argument");
-    Worker wk;
-    RC(tm_worker(device, wk));
+    TmLease lease;
+    RC(lease.take(device));                                // (no points: FIB_DEVICE_ALL and an unknown device are refused all the same)
     if (npoints == 0) return FIB_OK;
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    auto &b = *lease.b;
     const size_t nvox = (size_t)nx * ny * nz;
     RC(b.vol.ensure(nvox * nframes));
     RC(h2d(b.vol.p, vol, sizeof(float) * nvox * nframes));
@@ -743,32 +758,17 @@ extern "C" int fib_str_stats(int device, const float *xyz, const int32_t *npts, 
     RC(tm_host_check(npts, nlines, npoints));
     FIB_CHECK(npoints == 0 || (xyz && (nscalars == 0 || scalars)), FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nlines == 0 || props, FIB_ERR_INVALID, "NULL props");
-    Worker wk;
-    RC(tm_worker(device, wk));
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
     const int ncol = 1 + nscalars;
-    int64_t p0 = 0;
-    for (int64_t l0 = 0; l0 < nlines;) {
-        int64_t l1, np;
-        tm_next_chunk(npts, nlines, l0, &l1, &np);
-        size_t wb = 0;
-        RC(fibd_str_work_size(l1 - l0, &wb));
-        RC(b.work.ensure(wb));
-        RC(b.npts.ensure((size_t)(l1 - l0)));
-        RC(b.xyz.ensure((size_t)3 * np));
+    return tm_walk_lines(b, xyz, npts, nlines, fibd_str_work_size, fibh::LINES_UNBOUNDED, [&](int64_t l0, int64_t nl, int64_t p0, int64_t np, size_t wb) -> int {
         RC(b.scal.ensure((size_t)nscalars * np));
-        RC(b.props.ensure((size_t)ncol * (l1 - l0)));
-        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * (size_t)(l1 - l0)));
-        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(b.props.ensure((size_t)ncol * nl));
         if (np && nscalars) RC(h2d(b.scal.p, scalars + p0 * nscalars, sizeof(float) * (size_t)nscalars * np));
-        RC(fibd_str_stats(b.xyz.p, b.npts.p, l1 - l0, np, volres, b.scal.p, nscalars, b.props.p, b.work.p, wb, nullptr));
-        RC(d2h(props + l0 * ncol, b.props.p, sizeof(float) * (size_t)ncol * (l1 - l0)));
-        p0 += np; l0 = l1;
-    }
-    return FIB_OK;
+        RC(fibd_str_stats(b.xyz.p, b.npts.p, nl, np, volres, b.scal.p, nscalars, b.props.p, b.work.p, wb, nullptr));
+        return d2h(props + l0 * ncol, b.props.p, sizeof(float) * (size_t)ncol * nl);
+    });
 } FIB_API_CATCH
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -787,12 +787,9 @@ extern "C" int fib_str_select(int device, const float *xyz, const int32_t *npts,
     FIB_CHECK(min_npts >= 0 && max_npts >= 0, FIB_ERR_INVALID, "min_npts and max_npts must not be negative");
     RC(tm_host_check(npts, nlines, npoints));
     FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
-    Worker wk;
-    RC(tm_worker(device, wk));
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
     const size_t nvox = (size_t)nx * ny * nz;
     RC(b.nout.ensure(3));
     if (nroi) {
@@ -802,30 +799,19 @@ extern "C" int fib_str_select(int device, const float *xyz, const int32_t *npts,
         RC(fibd_str_roi_pack(b.rois.p, nroi, (int64_t)nvox, b.roibits.p, nullptr));
     }
     int64_t total[2] = {0, 0};
-    int64_t p0 = 0;
-    for (int64_t l0 = 0; l0 < nlines;) {
-        int64_t l1, np;
-        tm_next_chunk(npts, nlines, l0, &l1, &np);
-        const size_t nl = (size_t)(l1 - l0);
-        size_t wb = 0;
-        RC(fibd_str_select_work_size(l1 - l0, &wb));
-        RC(b.work.ensure(wb));
-        RC(b.npts.ensure(nl));
-        RC(b.xyz.ensure((size_t)3 * np));
-        RC(b.keep.ensure(nl));
-        if (hits) RC(b.hits.ensure(3 * nl));
-        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * nl));
-        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
-        RC(fibd_str_select(b.xyz.p, b.npts.p, l1 - l0, np, nx, ny, nz, nroi ? b.roibits.p : nullptr, visit_all, visit_none, end_any, end_both, min_npts,
+    RC(tm_walk_lines(b, xyz, npts, nlines, fibd_str_select_work_size, fibh::LINES_UNBOUNDED, [&](int64_t l0, int64_t nl, int64_t, int64_t np, size_t wb) -> int {
+        RC(b.keep.ensure((size_t)nl));
+        if (hits) RC(b.hits.ensure((size_t)3 * nl));
+        RC(fibd_str_select(b.xyz.p, b.npts.p, nl, np, nx, ny, nz, nroi ? b.roibits.p : nullptr, visit_all, visit_none, end_any, end_both, min_npts,
                            max_npts, b.keep.p, hits ? b.hits.p : nullptr, b.nout.p, b.work.p, wb, nullptr));
         int64_t got[2] = {0, 0};
-        RC(d2h(got, b.nout.p, sizeof got));                    // (a blocking copy on the NULL stream: behind the kernels)
+        RC(d2h(got, b.nout.p, sizeof got));
         FIB_CHECK(got[0] >= 0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
-        RC(d2h(keep + l0, b.keep.p, nl));
-        if (hits) RC(d2h(hits + 3 * l0, b.hits.p, sizeof(uint32_t) * 3 * nl));
+        RC(d2h(keep + l0, b.keep.p, (size_t)nl));
+        if (hits) RC(d2h(hits + 3 * l0, b.hits.p, sizeof(uint32_t) * 3 * (size_t)nl));
         total[0] += got[0]; total[1] += got[1];
-        p0 += np; l0 = l1;
-    }
+        return FIB_OK;
+    }));
     counts[0] = total[0]; counts[1] = total[1];
     return FIB_OK;
 } FIB_API_CATCH
@@ -841,12 +827,9 @@ extern "C" int fib_str_connectome(int device, const float *xyz, const int32_t *n
     FIB_CHECK(nremap >= 0 && (nremap == 0 || remap), FIB_ERR_INVALID, "nremap entries need a remap array");
     RC(tm_host_check(npts, nlines, npoints));
     FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
-    Worker wk;
-    RC(tm_worker(device, wk));
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
     const size_t nvox = (size_t)nx * ny * nz, cells = (size_t)(nnodes + 1) * (size_t)(nnodes + 1);
     RC(b.nout.ensure(3));
     RC(b.labels.ensure(nvox));
@@ -862,29 +845,18 @@ extern "C" int fib_str_connectome(int device, const float *xyz, const int32_t *n
         if (wmat) FIB_HIP(hipMemset(b.wmat.p, 0, sizeof(double) * cells));
     }
     int64_t total = 0;
-    int64_t p0 = 0;
-    for (int64_t l0 = 0; l0 < nlines;) {
-        int64_t l1, np;
-        tm_next_chunk(npts, nlines, l0, &l1, &np);
-        const size_t nl = (size_t)(l1 - l0);
-        size_t wb = 0;
-        RC(fibd_str_select_work_size(l1 - l0, &wb));
-        RC(b.work.ensure(wb));
-        RC(b.npts.ensure(nl));
-        RC(b.xyz.ensure((size_t)3 * np));
-        if (assign) RC(b.assign.ensure(2 * nl));
-        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * nl));
-        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
-        RC(fibd_str_connectome(b.xyz.p, b.npts.p, l1 - l0, np, nx, ny, nz, volres, b.labels.p, nremap ? b.remap.p : nullptr, nremap, nnodes,
+    RC(tm_walk_lines(b, xyz, npts, nlines, fibd_str_select_work_size, fibh::LINES_UNBOUNDED, [&](int64_t l0, int64_t nl, int64_t, int64_t np, size_t wb) -> int {
+        if (assign) RC(b.assign.ensure((size_t)2 * nl));
+        RC(fibd_str_connectome(b.xyz.p, b.npts.p, nl, np, nx, ny, nz, volres, b.labels.p, nremap ? b.remap.p : nullptr, nremap, nnodes,
                                FIB_CONNECTOME_ACCUMULATE, b.cmat.p, wmat ? b.wmat.p : nullptr, assign ? b.assign.p : nullptr, b.nout.p, b.work.p, wb,
                                nullptr));
         int64_t got = 0;
         RC(d2h(&got, b.nout.p, sizeof got));
         FIB_CHECK(got >= 0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
-        if (assign) RC(d2h(assign + 2 * l0, b.assign.p, sizeof(int32_t) * 2 * nl));
+        if (assign) RC(d2h(assign + 2 * l0, b.assign.p, sizeof(int32_t) * 2 * (size_t)nl));
         total += got;
-        p0 += np; l0 = l1;
-    }
+        return FIB_OK;
+    }));
     RC(d2h(cmat, b.cmat.p, sizeof(uint32_t) * cells));
     if (wmat) RC(d2h(wmat, b.wmat.p, sizeof(double) * cells));
     *n_lines = total;
@@ -901,38 +873,20 @@ extern "C" int fib_str_resample(int device, const float *xyz, const int32_t *npt
     RC(tm_host_check(npts, nlines, npoints));
     FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
     FIB_CHECK(nlines == 0 || out, FIB_ERR_INVALID, "NULL out");
-    Worker wk;
-    RC(tm_worker(device, wk));
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
     RC(b.nout.ensure(3));
     const int64_t max_lines = std::max<int64_t>(1, TM_CHUNK_POINTS / K);       // the output of a chunk is no larger than its largest input
-    int64_t p0 = 0;
-    for (int64_t l0 = 0; l0 < nlines;) {
-        int64_t l1, np;
-        tm_next_chunk(npts, nlines, l0, &l1, &np);
-        if (l1 - l0 > max_lines) { l1 = l0 + max_lines; np = 0; for (int64_t l = l0; l < l1; l++) np += npts[l]; }
-        const size_t nl = (size_t)(l1 - l0);
-        size_t wb = 0;
-        RC(fibd_str_work_size(l1 - l0, &wb));
-        RC(b.work.ensure(wb));
-        RC(b.npts.ensure(nl));
-        RC(b.xyz.ensure((size_t)3 * np));
+    return tm_walk_lines(b, xyz, npts, nlines, fibd_str_work_size, max_lines, [&](int64_t l0, int64_t nl, int64_t, int64_t np, size_t wb) -> int {
         RC(b.lines.ensure((size_t)3 * K * nl));
-        if (flip) RC(b.flip.ensure(nl));
-        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * nl));
-        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
-        if (flip) RC(h2d(b.flip.p, flip + l0, nl));
-        RC(fibd_str_resample(b.xyz.p, b.npts.p, l1 - l0, np, volres, K, flip ? b.flip.p : nullptr, b.lines.p, b.nout.p, b.work.p, wb, nullptr));
+        if (flip) { RC(b.flip.ensure((size_t)nl)); RC(h2d(b.flip.p, flip + l0, (size_t)nl)); }
+        RC(fibd_str_resample(b.xyz.p, b.npts.p, nl, np, volres, K, flip ? b.flip.p : nullptr, b.lines.p, b.nout.p, b.work.p, wb, nullptr));
         int64_t got = 0;
-        RC(d2h(&got, b.nout.p, sizeof got));                   // (a blocking copy on the NULL stream: behind the kernels)
-        FIB_CHECK(got == l1 - l0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
-        RC(d2h(out + (size_t)3 * K * l0, b.lines.p, sizeof(float) * 3 * K * nl));
-        p0 += np; l0 = l1;
-    }
-    return FIB_OK;
+        RC(d2h(&got, b.nout.p, sizeof got));
+        FIB_CHECK(got == nl, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
+        return d2h(out + (size_t)3 * K * l0, b.lines.p, sizeof(float) * 3 * K * (size_t)nl);
+    });
 } FIB_API_CATCH
 
 extern "C" int fib_str_assign(int device, const float *lines, int64_t nlines, int K, const float *models, int nmodels, const float volres[3],
@@ -941,12 +895,9 @@ extern "C" int fib_str_assign(int device, const float *lines, int64_t nlines, in
     FIB_CHECK(K >= 1 && K <= 256, FIB_ERR_UNSUPPORTED, "lines of 1 to 256 points each, not %d", K);
     FIB_CHECK(nmodels >= 1 && nmodels < (1 << 24), FIB_ERR_INVALID, "the number of models must be between 1 and 2^24 - 1");
     FIB_CHECK(models && volres && (nlines == 0 || (lines && label && dist && flip)), FIB_ERR_INVALID, "NULL argument");
-    Worker wk;
-    RC(tm_worker(device, wk));
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
     const size_t row = (size_t)3 * K;
     RC(b.models.ensure(row * nmodels));
     RC(h2d(b.models.p, models, sizeof(float) * row * nmodels));
@@ -976,12 +927,9 @@ extern "C" int fib_str_centroids(int device, const float *lines, int64_t nlines,
     FIB_CHECK(K >= 1 && K <= 256, FIB_ERR_UNSUPPORTED, "lines of 1 to 256 points each, not %d", K);
     FIB_CHECK(nmodels >= 1 && nmodels < (1 << 24), FIB_ERR_INVALID, "the number of models must be between 1 and 2^24 - 1");
     FIB_CHECK(sums && counts && (nlines == 0 || (lines && label)), FIB_ERR_INVALID, "NULL argument");
-    Worker wk;
-    RC(tm_worker(device, wk));
-    std::lock_guard<std::mutex> lk(wk->mu);
-    fib::DeviceGuard guard;
-    RC(wk->init(copy_threads(1)));
-    auto &b = wk->tm;
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
     const size_t row = (size_t)3 * K, cells = row * nmodels;
     RC(b.sums.ensure(cells));
     RC(b.bcnt.ensure((size_t)nmodels));
@@ -1028,33 +976,23 @@ int odf_plan_for(DevState &d, const OdfSpec &s, fib_odf_plan **plan) {
     key_add(key, s.dsi ? (const void *)&s.hann_width : (const void *)&s.sigma, 4);
     const int fmt = fib_odf_default_format();            // the operand format is part of a plan's identity (it may change with the environment)
     key_add(key, &fmt, sizeof(fmt));
-    void *p = nullptr;
-    RC(cached_plan(d, 1, key, [&](void **out) {
-        fib_odf_plan *q = nullptr;
-        const int rc = s.dsi ? fib_dsi_plan_create_fmt(d.device, s.bval, s.bvec, s.nvol, s.verts, s.nverts, s.faces, s.nfaces, s.hann_width, fmt, &q)
-                             : fib_gqi_plan_create_fmt(d.device, s.bval, s.bvec, s.nvol, s.verts, s.nverts, s.faces, s.nfaces, s.sigma, fmt, &q);
-        *out = q;
-        return rc;
-    }, &p));
-    *plan = (fib_odf_plan *)p;
-    return FIB_OK;
+    return cached_plan<fib_odf_plan, fib_odf_plan_destroy>(d, key, [&](fib_odf_plan **q) {
+        return s.dsi ? fib_dsi_plan_create_fmt(d.device, s.bval, s.bvec, s.nvol, s.verts, s.nverts, s.faces, s.nfaces, s.hann_width, fmt, q)
+                     : fib_gqi_plan_create_fmt(d.device, s.bval, s.bvec, s.nvol, s.verts, s.nverts, s.faces, s.nfaces, s.sigma, fmt, q);
+    }, plan);
 }
 
 int odf_rec_host(int device, const OdfSpec &spec, const float *dwi, int nx, int ny, int nz, const void *mask, int mask_dtype,
                  float *pdf, float *odf, float *const peak[3], float *const qa[3]) {
-    FIB_CHECK(spec.bval != nullptr && spec.nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(spec.bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
-    FIB_CHECK(spec.verts && spec.faces && spec.nverts >= 2 && spec.nverts % 2 == 0 && spec.nfaces > 0, FIB_ERR_INVALID, "invalid ODF tessellation");
-    FIB_CHECK(dwi && mask && odf && peak && qa, FIB_ERR_INVALID, "NULL argument");
-    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
-    const bool zeroed = (mask_dtype & FIB_MASK_OUTPUTS_ZEROED) != 0;   // (the qa planes below are written in full either way: their outside value can be NaN)
-    mask_dtype &= ~FIB_MASK_OUTPUTS_ZEROED;
-    FIB_CHECK(dtype_size(mask_dtype) > 0, FIB_ERR_INVALID, "unknown mask dtype %d", mask_dtype);
-    for (int k = 0; k < 3; k++) FIB_CHECK(peak[k] && qa[k], FIB_ERR_INVALID, "NULL peak/qa output volume");
-    const int64_t nvox = (int64_t)nx * ny * nz;
+    FitCall c;
+    RC(fit_call(c, device, spec.bval, spec.nvol, spec.bvec != nullptr, dwi && mask && odf && peak && qa, nx, ny, nz, mask_dtype,
+                peak && qa && peak[0] && qa[0] && peak[1] && qa[1] && peak[2] && qa[2], "NULL peak/qa output volume",
+                spec.verts && spec.faces && spec.nverts >= 2 && spec.nverts % 2 == 0 && spec.nfaces > 0));
+    mask_dtype = c.mask_dtype;
+    const bool zeroed = c.zeroed;                        // (the qa planes below are written in full either way: their outside value can be NaN)
+    const int64_t nvox = c.nvox;
     const int nvol = spec.nvol, nvert = spec.nverts / 2;
-    std::vector<Worker> ws;
-    RC(workers_for(device, ws));
+    const std::vector<Worker> &ws = c.ws;
     const int nw = (int)ws.size();
     const std::vector<Rows> ins = {{dwi, nullptr, nvol}};
     std::vector<Rows> outs;
@@ -1093,7 +1031,7 @@ int odf_rec_host(int device, const OdfSpec &spec, const float *dwi, int nx, int 
                           return fibd_odf_rec(plan, din, dm, n, dpdf, dodf, pk, q, dmax + 2 * k, nvox % 4 != 0 ? FIB_ODF_SEPARATE_PEAKS : 0, st);
                       }, sl.use, zeroed));
         sl.maxes.resize((size_t)2 * nchunks);
-        if (nchunks > 0) FIB_HIP(hipMemcpy(sl.maxes.data(), dmax, sl.maxes.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if (nchunks > 0) RC(d2h(sl.maxes.data(), dmax, sl.maxes.size() * sizeof(float)));
         return FIB_OK;
     }));
     // odfmax = maximum(mean(odf, dims=4)) over the whole volume (gqi.jl:164, dsi.jl:263); maximum() propagates NaN
@@ -1202,16 +1140,25 @@ extern "C" int fib_rumba_rec(int device, const float *dwi, int nx, int ny, int n
 // find_peaks!(W) (gqi.jl:180-201) for nvox ODFs held in host memory: odf [nvox x nvert] planar (vertex-major rows of
 // nvox values, like MRI.vol[:,:,:,v]); isort_top [3 x nvox] planar, 0-based first-half vertex rows, -1 where the
 // tessellation has fewer vertices; nvalid [nvox] = count(odf_peak .> 0) (gqi.jl:200).
+namespace {
+// the peak finders take only the folded neighbour table from a plan: a GQI plan of one dummy frame, destroyed with this object
+struct PeaksPlan {
+    fib_odf_plan *p = nullptr;
+    int create(int device, const float *verts, int nverts, const int32_t *faces, int nfaces) {
+        const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};
+        return fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, &p);
+    }
+    ~PeaksPlan() { fib_odf_plan_destroy(p); }
+};
+}  // namespace
+
 extern "C" int fib_find_peaks(int device, const float *odf, int64_t nvox, const float *verts, int nverts,
                               const int32_t *faces, int nfaces, int32_t *isort_top, int32_t *nvalid) try {
     FIB_CHECK(odf && verts && faces && isort_top && nvalid, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nvox > 0 && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid sizes");
     fib::DeviceGuard guard;
-    // the plan only contributes the folded neighbour table: one dummy frame is enough
-    const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};
-    fib_odf_plan *p = nullptr;
-    RC(fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, &p));
-    struct PlanDel { fib_odf_plan *p; ~PlanDel() { fib_odf_plan_destroy(p); } } del{p};
+    PeaksPlan plan;
+    RC(plan.create(device, verts, nverts, faces, nfaces));
     FIB_HIP(hipSetDevice(device));
     const int nvert = nverts / 2;
     fib::DevBuf<float> d_odf;
@@ -1219,11 +1166,11 @@ extern "C" int fib_find_peaks(int device, const float *odf, int64_t nvox, const 
     RC(d_odf.alloc((size_t)nvox * nvert));
     RC(d_top.alloc((size_t)nvox * 3));
     RC(d_nv.alloc((size_t)nvox));
-    FIB_HIP(hipMemcpy(d_odf.p, odf, (size_t)nvox * nvert * sizeof(float), hipMemcpyHostToDevice));
-    RC(fibd_find_peaks(p, d_odf.p, nvox, d_top.p, d_nv.p, nullptr));
+    RC(h2d(d_odf.p, odf, (size_t)nvox * nvert * sizeof(float)));
+    RC(fibd_find_peaks(plan.p, d_odf.p, nvox, d_top.p, d_nv.p, nullptr));
     FIB_HIP(hipDeviceSynchronize());
-    FIB_HIP(hipMemcpy(isort_top, d_top.p, (size_t)nvox * 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    FIB_HIP(hipMemcpy(nvalid, d_nv.p, (size_t)nvox * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RC(d2h(isort_top, d_top.p, (size_t)nvox * 3 * sizeof(int32_t)));
+    RC(d2h(nvalid, d_nv.p, (size_t)nvox * sizeof(int32_t)));
     return FIB_OK;
 } FIB_API_CATCH
 
@@ -1232,21 +1179,19 @@ extern "C" int fib_find_peaks_work(int device, const float *odf, int64_t nvox, c
     FIB_CHECK(odf && verts && faces && odf_peak && isort && nvalid, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nvox > 0 && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid sizes");
     fib::DeviceGuard guard;
-    const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};      // (the plan only contributes the folded neighbour table)
-    fib_odf_plan *p = nullptr;
-    RC(fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, &p));
-    struct PlanDel { fib_odf_plan *p; ~PlanDel() { fib_odf_plan_destroy(p); } } del{p};
+    PeaksPlan plan;
+    RC(plan.create(device, verts, nverts, faces, nfaces));
     FIB_HIP(hipSetDevice(device));
     const size_t n = (size_t)nvox * (nverts / 2);
     fib::DevBuf<float> d_odf, d_pk;
     fib::DevBuf<int32_t> d_is, d_nv;
     RC(d_odf.alloc(n)); RC(d_pk.alloc(n)); RC(d_is.alloc(n)); RC(d_nv.alloc((size_t)nvox));
-    FIB_HIP(hipMemcpy(d_odf.p, odf, n * sizeof(float), hipMemcpyHostToDevice));
-    RC(fibd_find_peaks_work(p, d_odf.p, nvox, d_pk.p, d_is.p, d_nv.p, nullptr));
+    RC(h2d(d_odf.p, odf, n * sizeof(float)));
+    RC(fibd_find_peaks_work(plan.p, d_odf.p, nvox, d_pk.p, d_is.p, d_nv.p, nullptr));
     FIB_HIP(hipDeviceSynchronize());
-    FIB_HIP(hipMemcpy(odf_peak, d_pk.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    FIB_HIP(hipMemcpy(isort, d_is.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    FIB_HIP(hipMemcpy(nvalid, d_nv.p, (size_t)nvox * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RC(d2h(odf_peak, d_pk.p, n * sizeof(float)));
+    RC(d2h(isort, d_is.p, n * sizeof(int32_t)));
+    RC(d2h(nvalid, d_nv.p, (size_t)nvox * sizeof(int32_t)));
     return FIB_OK;
 } FIB_API_CATCH
 
@@ -1321,8 +1266,10 @@ int stream_worker(DevState &d, int w, int nw, const StreamIn &in, const std::vec
     if (!d.ws) RC(fibd_stream_ws_create(d.device, &d.ws));
     hipStream_t st = d.s_cmp;
     std::unique_ptr<HostTimer> tm(new HostTimer("stream_host_upload_field"));
-    auto &d_vec = d.sb.vec; auto &d_f = d.sb.f; auto &d_fa = d.sb.fa; auto &d_field = d.sb.field; auto &d_sub = d.sb.sub; auto &d_lcms = d.sb.lcms;
-    auto &d_mask = d.sb.mask; auto &d_mout = d.sb.mout;
+    if (!d.sb) d.sb.reset(new DevState::StreamBufs());
+    auto &sb = *d.sb;
+    auto &d_vec = sb.vec; auto &d_f = sb.f; auto &d_fa = sb.fa; auto &d_field = sb.field; auto &d_sub = sb.sub; auto &d_lcms = sb.lcms;
+    auto &d_mask = sb.mask; auto &d_mout = sb.mout;
     RC(d_vec.ensure((size_t)nvox * 3 * nvec));
     RC(d_field.ensure((size_t)nvox * 4 * nvec));
     RC(d_mout.ensure((size_t)nvox));
@@ -1348,7 +1295,7 @@ int stream_worker(DevState &d, int w, int nw, const StreamIn &in, const std::vec
     tm.reset(new HostTimer("stream_host_seeds_trace"));
     std::vector<int64_t> mine;
     for (size_t i = (size_t)w; i < seeds.size(); i += (size_t)nw) mine.push_back(seeds[i]);
-    auto &d_seeds = d.sb.seeds;
+    auto &d_seeds = sb.seeds;
     RC(d_seeds.ensure(mine.size()));
     if (!mine.empty()) RC(h2d(d_seeds.p, mine.data(), sizeof(int64_t) * mine.size()));
     RC(d_sub.ensure((size_t)in.nsub * 3));
@@ -1376,7 +1323,7 @@ int stream_worker(DevState &d, int w, int nw, const StreamIn &in, const std::vec
     if (in.lcms) sh.flags = (uint8_t *)alloc_result((size_t)std::max<int64_t>(np, 1));
     if (!sh.npts || !sh.sidx || !sh.xyz || (in.lcms && !sh.flags)) return fib::fail(FIB_ERR_NOMEM, "out of host memory");
     if (nl > 0) {
-        auto &d_npts = d.sb.npts; auto &d_sidx = d.sb.sidx; auto &d_xyz = d.sb.xyz; auto &d_flags = d.sb.flags;
+        auto &d_npts = sb.npts; auto &d_sidx = sb.sidx; auto &d_xyz = sb.xyz; auto &d_flags = sb.flags;
         RC(d_npts.ensure((size_t)nl));
         RC(d_sidx.ensure((size_t)nl));
         RC(d_xyz.ensure((size_t)np * 3));

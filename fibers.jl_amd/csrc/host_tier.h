@@ -7,7 +7,8 @@
 // the chunk schedule are read by tools, not only by reviewers.
 //
 // Contents: mask element-type conversion; CPU binding; the copy pool; LiveMap (the runs of a mask) + the piece list of a chunk;
-// row gather / scatter; chunk size, chunk schedule, slabs; run_chunks<Dev> -- the three-stage pipeline over voxel chunks.
+// row gather / scatter; chunk size, chunk schedule, slabs; the line-chunk schedule of the tractogram host forms;
+// run_chunks<Dev> -- the three-stage pipeline over voxel chunks.
 #pragma once
 #include <emmintrin.h>
 #include <sched.h>
@@ -283,8 +284,20 @@ inline void slab(int64_t nvox, int n, int i, int64_t &v0, int64_t &v1) {
     v0 = std::min(a * 4, nvox); v1 = std::min(b * 4, nvox);
 }
 
+// ---- the line-chunk schedule of the tractogram host forms (fib_str_*) ------------------------------------------------------
+// Lines travel to the device in chunks cut at line boundaries.  The chunk that starts at line l0 is the longest run [l0, l1) that holds
+// at least one line, at most max_lines lines and at most max_points points -- a line longer than max_points is a chunk of its own.
+// np = the points of the chunk.  l0 >= nlines: the empty chunk {l0, 0}.
+constexpr int64_t LINES_UNBOUNDED = INT64_MAX;
+struct LineChunk { int64_t l1, np; };
+inline LineChunk next_line_chunk(const int32_t *npts, int64_t nlines, int64_t l0, int64_t max_points, int64_t max_lines) {
+    int64_t l = l0, n = 0;
+    while (l < nlines && (l == l0 || (l - l0 < max_lines && n + npts[l] <= max_points))) n += npts[l++];
+    return {l, n};
+}
+
 // ---- the chunk pipeline ----------------------------------------------------------------------------------------------------
-constexpr int NBUF = 3;                                  // ring depth: chunk k uploads while k-1 computes and k-2 downloads
+constexpr int NBUF = 3;                                 // ring depth: chunk k uploads while k-1 computes and k-2 downloads
 enum Stream { S_IN = 0, S_CMP = 1, S_OUT = 2 };          // upload | kernels | download
 enum Event { E_IN = 0, E_CMP = 1, E_OUT = 2 };           // per ring slot: upload done | kernels done | download done
 

@@ -5,7 +5,8 @@
 // queued operations in order, events are generation counters under a mutex, copies are memcpy, and the "fit" of a chunk is arithmetic
 // whose result is known in closed form.  What is checked: the results (every voxel of every output row, zero-filling outside the mask
 // included) and -- by ThreadSanitizer -- that no ring buffer is touched by two stages at once; plus the run arithmetic (LiveMap, piece
-// lists), the chunk schedule, slabs, chunk sizes and the mask element types against brute force.
+// lists), the chunk schedule, slabs, chunk sizes, the mask element types and the line-chunk schedule of the tractogram host forms
+// against brute force.
 #include <cmath>
 #include <cstdio>
 #include <deque>
@@ -203,6 +204,39 @@ static void units() {
             for (int i = 0; i < n; i++) { int64_t a, b; slab(nvox, n, i, a, b); CHECK(a == prev && b >= a && (b % 4 == 0 || b == nvox)); prev = b; }
             CHECK(prev == nvox);
         }
+    // the line-chunk schedule of the tractogram host forms against brute force: point counts with zeros and ones and lines longer
+    // than max_points, small limits, no lines at all, a walk that starts in the middle
+    for (int trial = 0; trial < 60; trial++) {
+        const int64_t nlines = trial < 3 ? trial : (int64_t)(rng() % 400);
+        std::vector<int32_t> npts((size_t)nlines);
+        for (auto &n : npts) { const unsigned r = rng() % 10; n = r < 3 ? 0 : (r < 6 ? 1 : (r < 9 ? (int32_t)(rng() % 12) : (int32_t)(rng() % 200))); }
+        for (int64_t max_points : {1ll, 7ll, 64ll})
+            for (int64_t max_lines : {(int64_t)1, (int64_t)3, LINES_UNBOUNDED}) {
+                const int64_t start = nlines > 0 && trial % 2 ? (int64_t)(rng() % nlines) : 0;
+                int64_t nchunks = 0, l0 = start;
+                for (; l0 < nlines; nchunks++) {
+                    const LineChunk c = next_line_chunk(npts.data(), nlines, l0, max_points, max_lines);
+                    CHECK(c.l1 > l0 && c.l1 <= nlines);                                    // at least one line; chunks follow each other in order
+                    CHECK(c.l1 - l0 <= max_lines);
+                    int64_t sum = 0;
+                    for (int64_t l = l0; l < c.l1; l++) sum += npts[l];
+                    CHECK(c.np == sum);
+                    CHECK(sum <= max_points || c.l1 - l0 == 1);
+                    CHECK(c.l1 == nlines || c.l1 - l0 == max_lines || sum + npts[c.l1] > max_points);   // maximal: the next line would break a limit
+                    // the cut of the form this replaces: greedy by points, then truncated to max_lines and summed again
+                    int64_t g = l0, gn = 0;
+                    while (g < nlines && (g == l0 || gn + npts[g] <= max_points)) gn += npts[g++];
+                    if (g - l0 > max_lines) { g = l0 + max_lines; gn = 0; for (int64_t l = l0; l < g; l++) gn += npts[l]; }
+                    CHECK(c.l1 == g && c.np == gn);
+                    l0 = c.l1;
+                }
+                CHECK(l0 == std::max(start, nlines));                                      // the chunks partition [start, nlines)
+                if (start >= nlines) {                                                     // nothing left: an empty chunk, no line read
+                    const LineChunk c = next_line_chunk(npts.data(), nlines, start, max_points, max_lines);
+                    CHECK(c.l1 == start && c.np == 0 && nchunks == 0);
+                }
+            }
+    }
 }
 
 int main() {

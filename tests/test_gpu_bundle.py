@@ -349,8 +349,8 @@ def test_centroids_on_random_labels(fj, dev, case, K, nmodels):
 
 
 def test_host_forms_over_several_chunks_equal_the_device_forms(fj, dev):
-    """more points than one chunk of the host forms holds (2^22, cut at line boundaries; 2^22 / K lines for the equal-length forms; there
-    is no hook to make it smaller): resample and assign byte for byte, centroid counts exactly and sums within the bound"""
+    """more points than one chunk of the host forms holds (2^22, cut at line boundaries; 2^22 / K lines for the equal-length forms; the
+    limit is a constant: the cuts themselves are checked at small limits on the CPU, tests/host_tier_check.cpp): resample and assign byte for byte, centroid counts exactly and sums within the bound"""
     import torch
     rng = np.random.default_rng(43)
     L = fj.lib()
@@ -382,6 +382,24 @@ def test_host_forms_over_several_chunks_equal_the_device_forms(fj, dev):
     # both are any-order sums of the same N_b terms, each within (N_b - 1) * 2^-52 * sum|t| of the sequential one; sum|t| <= 9 N_b here
     nb = hn.astype(np.float64)[:, None, None]
     assert (np.abs(hs - _np(sums)) <= 2 * np.maximum(nb - 1, 0) * 2.0 ** -52 * 9 * nb).all()
+    fj.trim()
+
+
+def test_resample_host_form_cut_by_lines_equals_the_device_form(fj, dev):
+    """K = 256: a chunk of the host form holds 2^22 / 256 = 16 384 lines whatever their points, so 16 384 + 37 lines of 0 to 3 points are
+    cut by the line limit and not by the point limit (about 25 000 points in all); byte for byte against the device form"""
+    rng = np.random.default_rng(47)
+    K, nl = 256, (1 << 22) // 256 + 37
+    npts = rng.integers(0, 4, nl).astype(np.int32)
+    npnt = int(npts.sum())
+    assert nl == 16384 + 37 and npnt < (1 << 22) and all((npts == n).any() for n in range(4))
+    xyz = (rng.uniform(1, 8, (npnt, 3)) + np.cumsum(rng.standard_normal((npnt, 3)) * 0.3, axis=0) % 1.0).astype(np.float32)
+    flip = rng.integers(0, 2, nl).astype(np.uint8)
+    want = _np(fj.str_resample_device(*_to_dev(dev, xyz, npts), RES, K, flip=_t(dev, flip))[0])
+    got = np.full((nl, K, 3), SENTINEL, np.uint32).view(np.float32)
+    assert fj.lib().fib_str_resample(0, xyz.ctypes.data, npts.ctypes.data, nl, npnt, (C.c_float * 3)(*RES), K, flip.ctypes.data, got.ctypes.data) == 0
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.isnan(got[npts == 0]).all() and np.isfinite(got[npts > 0]).all()     # (every line was written, the last 37 included)
     fj.trim()
 
 
