@@ -16,6 +16,7 @@ from .structens import st_eigen, st_eigen_device, st_recon, st_recon_device, st_
 from .tract import Tract  # noqa: F401
 from .stream import (StreamBuffers, StreamWorkspace, angles_to_vectors, angles_to_vectors_device, make_sublist, stream,  # noqa: F401
                      stream_device, stream_device_run, stream_device_run_enqueue, stream_field_device)
+from .mgh import load_mgh, save_mgh  # noqa: F401
 from .nifti import (dsi_write, dti_write, gqi_write, load_nifti, mri_read, mri_read_bfiles, mri_write, rumba_write,  # noqa: F401
                     read_struct)
 from .trk import str_add, stream_to_trk, tract_header, trk_read, trk_write  # noqa: F401
@@ -26,3 +27,4 @@ from .tractsel import (Connectome, str_connectome, str_connectome_device, str_ga
                        str_select_device, str_select_work_size, str_take)
 from .bundle import (Bundles, str_assign_device, str_bundles, str_centroids, str_centroids_device, str_profile, str_resample,  # noqa: F401
                      str_resample_device)
+from .volxform import mri_xform, vol_xform_device, vol_xform_matrix, xfm_header  # noqa: F401

@@ -10,6 +10,7 @@ FIB_OK = 0
 FIB_ERR_CAPACITY = -9
 FIB_DENSITY_ACCUMULATE = 0x100      # OR-ed into the mode of fib(d)_str_density: add to what the map holds
 DENSITY_MODES = {"points": 0, "lines": 1, "endpoints": 2}
+VOL_INTERP = {"nearest": 0, "trilinear": 1}   # FIB_VOL_NEAREST / FIB_VOL_TRILINEAR
 FIB_CONNECTOME_ACCUMULATE = 0x100   # flags of fib(d)_str_connectome: add to what C and W hold
 FIB_CENTROIDS_ACCUMULATE = 0x100    # flags of fib(d)_str_centroids: add to what sums and counts hold
 FIB_MASK_OUTPUTS_ZEROED = 0x100     # OR-ed into mask_dtype: the output arrays are freshly zero-allocated (include/fibers_hip.h)
@@ -112,6 +113,8 @@ _PROTOS = {
     "fibd_stream_pack_trk_xfm": (i32, [vp, C.POINTER(C.c_float * 16), C.POINTER(C.c_float * 3), vp, vp]),
     "fibd_xfm_apply": (i32, [C.POINTER(C.c_float * 16), vp, vp, i64, vp]),
     "fib_xfm_apply": (i32, [i32, C.POINTER(C.c_float * 16), vp, vp, i64]),
+    "fibd_vol_xform": (i32, [C.POINTER(C.c_float * 16), vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp]),
+    "fib_vol_xform": (i32, [i32, C.POINTER(C.c_float * 16), vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32]),
     "fibd_str_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
     "fibd_str_density": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, C.c_uint64, vp]),
     "fibd_str_sample": (i32, [vp, i64, vp, i32, i32, i32, i32, f32, vp, vp]),

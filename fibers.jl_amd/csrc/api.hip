@@ -633,6 +633,43 @@ extern "C" int fib_st_recon(int device, const float *vol, int nx, int ny, int nz
     return FIB_OK;
 } FIB_API_CATCH
 
+// vol_xform host form: chunks of whole frames (they are independent); per chunk upload, one launch, download.  Copies block on the NULL
+// stream, so the read-back comes behind the kernel.  The buffers are local: nothing is kept between calls.
+extern "C" int fib_vol_xform(int device, const float out2in[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp,
+                             int32_t outside_bits, void *out, int nxo, int nyo, int nzo) try {
+    FIB_CHECK(out2in && vol && out, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nxi > 0 && nyi > 0 && nzi > 0 && nxo > 0 && nyo > 0 && nzo > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
+    FIB_CHECK(interp == FIB_VOL_NEAREST || interp == FIB_VOL_TRILINEAR, FIB_ERR_INVALID, "unknown interpolation %d", interp);
+    const size_t nvi = (size_t)nxi * nyi * nzi, nvo = (size_t)nxo * nyo * nzo;
+    const uintptr_t ai = reinterpret_cast<uintptr_t>(vol), ao = reinterpret_cast<uintptr_t>(out);
+    FIB_CHECK(ai + 4 * nvi * nframes <= ao || ao + 4 * nvo * nframes <= ai, FIB_ERR_INVALID, "vol and out must not overlap");
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "vol_xform runs on one device (FIB_DEVICE_ALL is not supported)");
+    fib::DeviceGuard guard;
+    RC(fib::use_device(device));
+    int nfc = 0;
+    if (const char *e = fib::env("FIBERS_VOL_XFORM_FRAMES")) nfc = atoi(e);
+    if (nfc <= 0) {                     // half the free memory: 4 (in) + 4 (out) bytes per voxel of a frame pair
+        size_t fr = 0, tot = 0;
+        FIB_HIP(hipMemGetInfo(&fr, &tot));
+        const size_t fit = (fr / 2) / (4 * (nvi + nvo));
+        FIB_CHECK(fit >= 1, FIB_ERR_NOMEM, "vol_xform: one input and one output frame do not fit in device memory");
+        nfc = (int)std::min<size_t>(fit, (size_t)nframes);
+    }
+    if (nfc > nframes) nfc = nframes;
+    fib::DevBuf<uint32_t> d_in, d_out;
+    RC(d_in.alloc(nvi * nfc));
+    RC(d_out.alloc(nvo * nfc));
+    const uint32_t *src = static_cast<const uint32_t *>(vol);
+    uint32_t *dst = static_cast<uint32_t *>(out);
+    for (int f0 = 0; f0 < nframes; f0 += nfc) {
+        const int nf = std::min(nfc, nframes - f0);
+        RC(h2d(d_in.p, src + nvi * f0, sizeof(uint32_t) * nvi * nf));
+        RC(fibd_vol_xform(out2in, d_in.p, nxi, nyi, nzi, nf, interp, outside_bits, d_out.p, nxo, nyo, nzo, nullptr));
+        RC(d2h(dst + nvo * f0, d_out.p, sizeof(uint32_t) * nvo * nf));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // tract maps: host forms.  One device; the points travel in chunks cut at line boundaries, the volume stays on the device.
 // ------------------------------------------------------------------------------------------------------------------------------

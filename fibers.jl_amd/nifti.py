@@ -4,7 +4,8 @@
 `<base>_<field>[k].nii.gz` naming of `dti_write` / `gqi_write` / `dsi_write` (dti.jl:344-349,
 gqi.jl:210-225, dsi.jl:279-294) and the struct reload `mri_read(inbase, type)` (mri.jl:2276-2311).
 Pure host code (NumPy); `.gz` goes through Python's gzip instead of shelling out to zcat/gzip
-(mri.jl:1586-1591, 2160-2163).  MGH and Bruker inputs are not part of this back end."""
+(mri.jl:1586-1591, 2160-2163).  `.mgh` / `.mgz` go through mgh.py (mri.jl:621-641, 1730-1739); Bruker inputs are not part of this
+back end."""
 import glob
 import gzip
 import os
@@ -13,6 +14,7 @@ import struct
 
 import numpy as np
 
+from .mgh import load_mgh, save_mgh
 from .mri import MRI
 
 _NIFTI_DTYPES = {2: np.uint8, 4: np.int16, 8: np.int32, 16: np.float32, 64: np.float64,
@@ -204,10 +206,12 @@ def _normalise_bvec(g):
 
 
 def mri_read(infile, headeronly=False, mmap=False):
-    """mri_read for NIfTI inputs (mri.jl:611-733): volume + optional <stem>.bval[s]/.bvec[s] tables,
+    """mri_read for NIfTI and MGH (.mgh / .mgz) inputs (mri.jl:611-733): volume + optional <stem>.bval[s]/.bvec[s] tables,
     gradient vectors normalised.  `vol` keeps the file's element type (the fits need Float32).
     mmap=True: see load_nifti (the volume stays in the file until a fit streams it to the GPU)."""
     low = infile.lower()
+    if low.endswith((".mgh", ".mgz")):
+        return _mri_read_mgh(infile, headeronly)
     if not (low.endswith(".nii") or low.endswith(".nii.gz")):
         raise ValueError("File extension not supported by this back end (NIfTI only): " + infile)
     hdr, vol = load_nifti(infile, headeronly, mmap=mmap)
@@ -221,7 +225,11 @@ def mri_read(infile, headeronly=False, mmap=False):
               vox2ras=M.copy())
     mri.tr = float(hdr["pixdim"][4])
     mri.niftihdr = hdr
-    stem = infile[: -7] if low.endswith(".nii.gz") else infile[: -4]
+    return _read_btables(mri, infile[: -7] if low.endswith(".nii.gz") else infile[: -4])
+
+
+def _read_btables(mri, stem):
+    """<stem>.bval[s] / .bvec[s], where both exist and fit the frames (mri.jl:690-716)"""
     bfile = next((stem + e for e in (".bvals", ".bval") if os.path.isfile(stem + e)), "")
     gfile = next((stem + e for e in (".bvecs", ".bvec") if os.path.isfile(stem + e)), "")
     if bfile and gfile:
@@ -231,10 +239,27 @@ def mri_read(infile, headeronly=False, mmap=False):
     return mri
 
 
+def _mri_read_mgh(infile, headeronly):
+    """the MGH branch of mri_read (mri.jl:621-641): tr from mr_parms, volres the column norms of M, the element type kept"""
+    vol, M, mr_parms, volsz = load_mgh(infile, headeronly)
+    if headeronly:
+        vol = np.zeros(volsz, vol.dtype, order="F")
+    mri = MRI(vol, volres=tuple(float(v) for v in np.sqrt((M[:3, :3].astype(np.float64) ** 2).sum(axis=0))), vox2ras=M.copy())
+    if len(mr_parms):
+        mri.tr = float(mr_parms[0])
+    return _read_btables(mri, infile[: -4])
+
+
 def mri_write(mri, outfile, datatype=None):
-    """mri_write for NIfTI outputs (mri.jl:1695-1919 + save_nifti 2059-2166).  Returns True on error
+    """mri_write for NIfTI and MGH (.mgh / .mgz) outputs (mri.jl:1695-1919 + save_nifti 2059-2166, save_mgh).  Returns True on error
     (byte count mismatch), like the reference."""
     low = outfile.lower()
+    if low.endswith((".mgh", ".mgz")):                                            # mri.jl:1730-1739
+        vol = mri.vol if datatype is None else mri.vol.astype(datatype)
+        err = save_mgh(vol, outfile, mri.vox2ras, [float(getattr(mri, "tr", 0.0)), 0.0, 0.0, 0.0])
+        if err:
+            print("WARNING: Problem saving " + outfile)
+        return err
     if not (low.endswith(".nii") or low.endswith(".nii.gz")):
         raise ValueError("File extension not supported by this back end (NIfTI only): " + outfile)
     vol = mri.vol

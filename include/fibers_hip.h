@@ -603,6 +603,42 @@ int fibd_str_centroids(const float *lines, int64_t nlines, int K, const int32_t 
                        int flags, double *sums, uint32_t *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Volume resampling: a volume moved through an Xform (NOT in the reference)             */
+/* ------------------------------------------------------------------------------------ */
+/* Volumes are planar [nframes][nz][ny][nx], x fastest (MRI.vol in Fortran order), 32-bit elements.  Voxel coordinates are 0-BASED
+ * ARRAY INDICES, the convention of .lta and FSL vox2vox matrices; the tract code's 1-based point coordinates are not involved.  These
+ * definitions are this project's own; they are the contract.
+ *
+ * PULL-BACK.  For the output voxel o = (i, j, k), taken as float32 values, p = xfm_point(M, i, j, k): the arithmetic of fib_xfm_apply
+ * (float32, every multiply and add rounded on its own, IEEE division, the projective last row honoured).  M = out2in is the
+ * OUTPUT -> INPUT matrix, row-major float[16]; the Python layer makes it as float32(inv(float64(xfm.vox2vox))), rounded once.
+ *
+ * INSIDE.  A sample is inside iff for every component 0 <= rint(p_c) <= n_c - 1 (ties to even), tested on the float value before any
+ * conversion to an integer: NaN fails, -0.0 passes.  The same rule for both interpolations (the tract maps' "voxel of a point" moved
+ * to 0-based; what FreeSurfer's sampler does).  Otherwise the output word is `outside_bits`, in every frame.
+ *
+ * FIB_VOL_NEAREST.  The 32-bit word at voxel rint(p) is copied untouched: float32 (NaN payloads included), int32 and uint32 volumes
+ * go through the same kernel.  The fill is a 32-bit pattern (declared int32_t: the bit pattern of a float32 or uint32 fill).
+ *
+ * FIB_VOL_TRILINEAR, float32 only.  Per component i0 = floor(p_c), f = p_c - floor(p_c) (one rounded float32 subtraction: it may
+ * round to 1.0 for a tiny negative p_c), g = 1 - f, and the neighbour indices i0 and i0 + 1 are each CLAMPED into [0, n_c - 1].  Then,
+ * without fused multiply-add and in exactly this order,
+ *   c00 = gx*v000 + fx*v100,  c10 = gx*v010 + fx*v110,  c01 = gx*v001 + fx*v101,  c11 = gx*v011 + fx*v111   (v_xyz, x the first digit)
+ *   c0 = gy*c00 + fy*c10,  c1 = gy*c01 + fy*c11,  out = gz*c0 + fz*c1.
+ * f == 0 and the clamped shell are not special-cased (g*v + f*v is not v in float32).  Consequences, documented and not fixed: an Inf
+ * neighbour with weight 0 gives NaN; NaN voxels propagate.
+ * Every frame uses the same p, indices and weights.
+ *
+ * fibd_vol_xform: vol and out are device pointers (4-byte alignment suffices: views into a larger buffer); asynchronous on `stream`,
+ * no allocation and no synchronisation inside.  One thread per output voxel, 64-bit element offsets in and out.  FIB_ERR_INVALID:
+ * non-positive sizes, an unknown interp, NULL pointers, ANY overlap of vol and out (a gather has no in-place form); a dimension above
+ * 2^24 is FIB_ERR_UNSUPPORTED. */
+#define FIB_VOL_NEAREST 0
+#define FIB_VOL_TRILINEAR 1
+int fibd_vol_xform(const float out2in[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp, int32_t outside_bits,
+                   void *out, int nxo, int nyo, int nzo, void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Host-buffer drop-in entry points (what the Julia wrapper ccalls)                       */
 /* ------------------------------------------------------------------------------------ */
 
@@ -661,6 +697,13 @@ int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sig
  * aligned.  Host-buffer form: the points go through the host tier's chunk pipeline; FIB_DEVICE_ALL splits them over the device set.
  * npoints == 0 does nothing. */
 int fib_xfm_apply(int device, const float vox2vox[16], const float *in, float *out, int64_t npoints);
+/* host-buffer form of fibd_vol_xform (the "Volume resampling" section above): vol [nframes][nzi][nyi][nxi] and out
+ * [nframes][nzo][nyo][nxo] are host memory.  Frames are independent: the call walks chunks of whole frames (upload, one launch,
+ * download), sized so that the input and output frames of a chunk fit in half the free device memory (FIBERS_VOL_XFORM_FRAMES=<n>
+ * overrides); results do not depend on the chunking.  The chunk's device buffers are local to the call: nothing is kept between
+ * calls.  One device: FIB_DEVICE_ALL is FIB_ERR_UNSUPPORTED. */
+int fib_vol_xform(int device, const float out2in[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp,
+                  int32_t outside_bits, void *out, int nxo, int nyo, int nzo);
 int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, float *adc, float *s0);
 /* host-buffer forms of the tract maps (fibd_str_density / fibd_str_sample / fibd_str_stats above): every array is host memory.  The

@@ -387,6 +387,35 @@ function str_xform(xfm::Xform{Float32}, tr::Tract{Float32}; device::Integer=0)
   return trnew
 end
 
+# ---- volume resampling (NOT in the reference; the definitions are the "Volume resampling" section of include/fibers_hip.h) ---------
+const FIB_VOL_INTERP = Dict(:nearest => 0, :trilinear => 1)
+
+"the output -> input matrix of vol_xform, row-major for the C ABI: Float32(inv(Float64(vox2vox))), rounded once"
+vol_xform_matrix(xfm::Xform{Float32}) = Matrix{Float32}(permutedims(Float32.(inv(Float64.(xfm.vox2vox)))))
+
+function vol_xform_call(xfm::Xform{Float32}, vol::Array{T,4}, interp::Symbol, bits::Int32, device::Integer) where T<:Union{Float32,Int32}
+  haskey(FIB_VOL_INTERP, interp) || error("interp must be :nearest or :trilinear")
+  collect(size(vol)[1:3]) == collect(xfm.insize) || error("the volume is " * string(size(vol)[1:3]) * " but the transform's input space is " * string(xfm.insize))
+  nxi, nyi, nzi, nf = size(vol)
+  nxo, nyo, nzo = Int.(xfm.outsize)
+  out = Array{T,4}(undef, nxo, nyo, nzo, nf)
+  m = vol_xform_matrix(xfm)
+  GC.@preserve m vol out fib_check(ccall((:fib_vol_xform, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Int32, Ptr{Cvoid}, Cint, Cint, Cint),
+      device, m, vol, nxi, nyi, nzi, nf, FIB_VOL_INTERP[interp], bits, out, nxo, nyo, nzo))
+  return out
+end
+
+"vol_xform(xfm, vol) — a volume [nx, ny, nz, nframes] resampled onto the output grid of xfm (nearest voxel or trilinear; voxels whose
+nearest input voxel does not exist get `outside`).  Gradient tables are not reoriented: that is the caller's business."
+vol_xform(xfm::Xform{Float32}, vol::Array{Float32,4}; interp::Symbol=:trilinear, outside::Real=0f0, device::Integer=0) =
+  vol_xform_call(xfm, vol, interp, reinterpret(Int32, Float32(outside)), device)
+"vol_xform(xfm, labels) — Int32 volumes (label maps) go through nearest-voxel resampling only"
+function vol_xform(xfm::Xform{Float32}, vol::Array{Int32,4}; interp::Symbol=:nearest, outside::Integer=0, device::Integer=0)
+  interp == :nearest || error("Int32 volumes take interp=:nearest only")
+  return vol_xform_call(xfm, vol, interp, Int32(outside), device)
+end
+
 # ---- tract maps (NOT in the reference; the definitions are the "Tract maps" section of include/fibers_hip.h) ----------------------
 const FIB_DENSITY_MODES = Dict(:points => 0, :lines => 1, :endpoints => 2)
 const FIB_DENSITY_ACCUMULATE = 0x100
