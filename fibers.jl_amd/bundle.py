@@ -6,7 +6,6 @@ csrc/bundle.hip; there is no NumPy path here (the per-node mean of `str_profile`
 
 Host tier: `Tract` / `MRI` in, `Tract` / `Bundles` / arrays out, through fib_str_*.  Device tier: torch tensors in and out, through
 fibd_str_* on `stream`, taking the entries of stream_device / stream_device_run's dict as they are."""
-import ctypes as C
 from dataclasses import dataclass, replace
 from typing import Optional
 
@@ -14,8 +13,8 @@ import numpy as np
 
 from . import _lib
 from .tract import Tract
-from .tractmap import _counts, _on, _packed, _points, _work, str_sample
-from .tractsel import _tensor
+from ._dev import ArgError, Launch, float3 as _res, packed as _packed, tensor, work as _work
+from .tractmap import _lines, str_sample, str_work_size
 
 
 @dataclass
@@ -26,10 +25,6 @@ class Bundles:
     counts: np.ndarray                    # uint32 [nmodels]: lines per bundle
     npoints: int = 0                      # points per line the distances were computed on
     lines: Optional[np.ndarray] = None    # float32 [nstr, npoints, 3]: the resampled lines (as stored, not flipped)
-
-
-def _res(volres):
-    return (C.c_float * 3)(*[float(v) for v in volres])
 
 
 def _equal_length(tr: Tract, npoints, device):
@@ -127,33 +122,29 @@ def str_profile(tr: Tract, vols, models: Tract, thresh_mm: float, npoints: int =
 # ---- device tier ------------------------------------------------------------------------------------------------------------------
 def _rows(t, ref, what):
     import torch
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3 and (ref is None or t.device == ref.device)):
-        raise ValueError("%s must be a contiguous float32 CUDA tensor [n, K, 3]" % what)
+    tensor(t, torch.float32, what, ref=ref, shape=(None, None, 3))
     return int(t.shape[0]), int(t.shape[1])
+
+
+def _flip(flip, nl, ref):
+    import torch
+    return None if flip is None else tensor(flip, torch.uint8, "flip", ref=ref, n=nl, bool_ok=True)
 
 
 def str_resample_device(xyz, npts, volres, npoints: int = 20, flip=None, out=None, status=None, work=None, stream=None):
     """fibd_str_resample on device tensors: xyz float32 [npoints, 3], npts int32 [nlines], flip uint8 / bool [nlines] or None.  Returns
-    (out float32 [nlines, K, 3], status int64 [1]) -- device tensors, the call does not wait.  An invalid `npts` leaves `out` unwritten
-    and sets status to -1; otherwise status is the number of lines."""
+    (out float32 [nlines, K, 3], status int64 [1]) -- device tensors, the call does not wait (`stream`, and `work` = None under a raw
+    handle: _dev.Launch).  An invalid `npts` leaves `out` unwritten and sets status to -1; otherwise status is the number of lines."""
     import torch
-    from .dti import _stream_ptr
-    npnt, nl = _points(xyz), _counts(npts, xyz)
+    npnt, nl = _lines(xyz, npts)
     K = int(npoints)
-    if flip is not None:
-        if flip.dtype == torch.bool:
-            flip = flip.view(torch.uint8)
-        _tensor(flip, torch.uint8, nl, xyz, "flip")
-    with _on(xyz, stream):
-        if out is None:
-            out = torch.empty((nl, K, 3), dtype=torch.float32, device=xyz.device)
-        else:
-            _tensor(out, torch.float32, nl * K * 3, xyz, "out")
-        if status is None:
-            status = torch.empty(1, dtype=torch.int64, device=xyz.device)
-        work, wb = _work(work, nl, xyz)
+    flip = _flip(flip, nl, xyz)
+    with Launch(xyz, stream) as L:
+        out = L.empty((nl, K, 3), torch.float32) if out is None else tensor(out, torch.float32, "out", ref=xyz, n=nl * K * 3)
+        status = L.empty(1, torch.int64) if status is None else tensor(status, torch.int64, "status", ref=xyz, n=1)
+        work, wb = _work(L, work, str_work_size, "str_work_size(nlines)", nl)
         _lib.check(_lib.lib().fibd_str_resample(xyz.data_ptr(), npts.data_ptr(), nl, npnt, _res(volres), K, flip.data_ptr() if flip is not None else None,
-                                                out.data_ptr(), status.data_ptr(), work.data_ptr(), wb, _stream_ptr(stream)))
+                                                out.data_ptr(), status.data_ptr(), work.data_ptr(), wb, L.sp))
     return out, status
 
 
@@ -161,18 +152,15 @@ def str_assign_device(lines, models, volres, thresh_mm: float, dist_all: bool = 
     """fibd_str_assign: lines float32 [nlines, K, 3], models float32 [nmodels, K, 3].  Returns a dict of device tensors: `label` int32
     [nlines], `dist` float32 [nlines], `flip` uint8 [nlines] and `dist_all` float32 [nlines, nmodels] (None unless asked for)."""
     import torch
-    from .dti import _stream_ptr
     nl, K = _rows(lines, None, "lines")
     nm, Km = _rows(models, lines, "models")
     if Km != K or nm < 1:
-        raise ValueError("models must be [nmodels >= 1, %d, 3] like the lines" % K)
-    with _on(lines, stream):
-        r = dict(label=torch.empty(nl, dtype=torch.int32, device=lines.device), dist=torch.empty(nl, dtype=torch.float32, device=lines.device),
-                 flip=torch.empty(nl, dtype=torch.uint8, device=lines.device),
-                 dist_all=torch.empty((nl, nm), dtype=torch.float32, device=lines.device) if dist_all else None)
+        raise ArgError("models must be [nmodels >= 1, %d, 3] like the lines" % K)
+    with Launch(lines, stream) as L:
+        r = dict(label=L.empty(nl, torch.int32), dist=L.empty(nl, torch.float32), flip=L.empty(nl, torch.uint8),
+                 dist_all=L.empty((nl, nm), torch.float32) if dist_all else None)
         _lib.check(_lib.lib().fibd_str_assign(lines.data_ptr(), nl, K, models.data_ptr(), nm, _res(volres), float(thresh_mm), r["label"].data_ptr(),
-                                              r["dist"].data_ptr(), r["flip"].data_ptr(), r["dist_all"].data_ptr() if dist_all else None,
-                                              _stream_ptr(stream)))
+                                              r["dist"].data_ptr(), r["flip"].data_ptr(), r["dist_all"].data_ptr() if dist_all else None, L.sp))
     return r
 
 
@@ -181,24 +169,19 @@ def str_centroids_device(lines, label, flip, nmodels: int, out=None, stream=None
     pair of an earlier call to accumulate into (lines that arrive in batches).  sums / counts is the centroid; as float32 it is the
     `models` of the next str_assign_device."""
     import torch
-    from .dti import _stream_ptr
     nl, K = _rows(lines, None, "lines")
     nm = int(nmodels)
-    _tensor(label, torch.int32, nl, lines, "label")
-    if flip is not None:
-        if flip.dtype == torch.bool:
-            flip = flip.view(torch.uint8)
-        _tensor(flip, torch.uint8, nl, lines, "flip")
-    with _on(lines, stream):
+    tensor(label, torch.int32, "label", ref=lines, n=nl)
+    flip = _flip(flip, nl, lines)
+    with Launch(lines, stream) as L:
         flags = 0
         if out is None:
-            sums = torch.empty((nm, K, 3), dtype=torch.float64, device=lines.device)
-            counts = torch.empty(nm, dtype=torch.uint32, device=lines.device)
+            sums, counts = L.empty((nm, K, 3), torch.float64), L.empty(nm, torch.uint32)
         else:
             flags = _lib.FIB_CENTROIDS_ACCUMULATE
             sums, counts = out
-            _tensor(sums, torch.float64, nm * K * 3, lines, "out sums")
-            _tensor(counts, torch.uint32, nm, lines, "out counts")
+            tensor(sums, torch.float64, "out sums", ref=lines, n=nm * K * 3)
+            tensor(counts, torch.uint32, "out counts", ref=lines, n=nm)
         _lib.check(_lib.lib().fibd_str_centroids(lines.data_ptr(), nl, K, label.data_ptr(), flip.data_ptr() if flip is not None else None, nm, flags,
-                                                 sums.data_ptr(), counts.data_ptr(), _stream_ptr(stream)))
+                                                 sums.data_ptr(), counts.data_ptr(), L.sp))
     return sums, counts

@@ -16,6 +16,8 @@ import math
 
 import numpy as np
 
+from ._dev import torch_stream
+
 
 def slab_bounds(nz: int, world: int, rank: int, nxy: int = 0) -> Tuple[int, int]:
     """contiguous near-equal z-slabs, like Threads.@threads :static over 1:nz.
@@ -51,17 +53,6 @@ def shard_seeds(seeds, world: int, rank: int):
     import torch
     gi = torch.arange(rank, seeds.numel(), world, device=seeds.device)
     return seeds[gi], gi
-
-
-def _torch_stream(stream):
-    """None, a torch.cuda.Stream or a raw hipStream_t handle -> the torch stream object (None: torch's current stream)"""
-    import torch
-    if stream is None or isinstance(stream, torch.cuda.Stream):
-        return stream
-    handle = int(getattr(stream, "value", stream) or 0)        # ctypes.c_void_p (the package's own handle type) or a plain integer
-    if handle == 0:                                             # the null stream: torch's default stream
-        return torch.cuda.default_stream()
-    return torch.cuda.ExternalStream(handle)
 
 
 def allreduce_odfmax(odfmax, group=None, always=False, raw=True):
@@ -104,7 +95,7 @@ def allgather_slabs(local, counts: Sequence[int], group=None, always=False):
     assert local.shape[0] == counts[rank]
     full = local.new_empty((sum(counts),) + tuple(local.shape[1:]))
     offs = np.concatenate([[0], np.cumsum(counts)])
-    if local.is_cuda and dist.get_backend(group) != "nccl":
+    if local.device.type == "cuda" and dist.get_backend(group) != "nccl":
         for r in range(world):
             piece = full[offs[r]:offs[r + 1]]
             if r == rank:
@@ -179,7 +170,7 @@ def odf_rec_sharded(plan, dwi_local, mask_local, group=None, stream=None, out=No
                          out_prezeroed=out_prezeroed, raw_odfmax=True)
     # the collective runs on the stream the kernels run on: it follows the kernel that writes out["odfmax"] and precedes the
     # normalisation in stream order, whatever torch's current stream is
-    ts = _torch_stream(stream)
+    ts = torch_stream(stream)
     with (torch.cuda.stream(ts) if ts is not None else contextlib.nullcontext()):
         allreduce_odfmax(out["odfmax"], group, always=always)
     qa_normalize_device(out["qa"], out["odfmax"], stream=stream, raw=True)   # {max, flag} -> NaN divisor if any rank saw a NaN mean

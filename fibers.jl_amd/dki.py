@@ -8,7 +8,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .dti import DTI_FIELDS, _check_tables, _chk_dev, _dwi_arg, _mask_checked, _stream_ptr
+from ._dev import Launch, Plan, tensor
+from .dti import DTI_FIELDS, _check_tables, _dwi_arg, _fit_args, _mask_checked
 from .mri import MRI
 from .odf import ODF, sphere_642
 
@@ -86,14 +87,14 @@ def dki_fit(dwi: MRI, mask: MRI, odf_dirs: ODF = sphere_642, min_signal: float =
     return DKI(**outs)
 
 
-class DkiPlan:
+class DkiPlan(Plan):
     """The DKI tables (pseudo-inverse columns, direction table of `odf_dirs`, limits) resident on one GPU"""
+    _destroy = "fib_dki_plan_destroy"
 
     def __init__(self, bval, bvec, odf_dirs: ODF = sphere_642, min_signal: float = DEFAULTS["min_signal"],
                  min_diffusivity: float = DEFAULTS["min_diffusivity"], min_kurtosis: float = DEFAULTS["min_kurtosis"],
                  max_kurtosis: float = DEFAULTS["max_kurtosis"], device: int = 0):
-        self._h = C.c_void_p()
-        self.device = device
+        Plan.__init__(self, device)
         bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
         self.nvol = int(bval.shape[0])
         bv = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
@@ -113,36 +114,20 @@ class DkiPlan:
         _lib.check(_lib.lib().fib_dki_plan_tables(self._h, A.ctypes.data, pA.ctypes.data, dirs.ctypes.data))
         return A, pA, dirs
 
-    def close(self):
-        if self._h:
-            _lib.lib().fib_dki_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def dki_fit_device(plan: DkiPlan, dwi, mask, out=None, stream=None, kt=True):
     """dwi: float32 CUDA tensor [nvol, nvox] (planar), mask: uint8 CUDA tensor [nvox].  Returns a dict of tensors: scalars [nvox],
     eigenvectors [3, nvox], kt [15, nvox].  `out` without a "kt" entry (or kt=False when the outputs are allocated here) skips
     the kurtosis tensor."""
     import torch
-    _chk_dev(dwi, torch.float32, "dwi")
-    _chk_dev(mask, torch.uint8, "mask")
-    nvox = mask.numel()
-    if dwi.numel() != nvox * plan.nvol:
-        raise ValueError("dwi has %d elements, expected nvol*nvox = %d" % (dwi.numel(), nvox * plan.nvol))
-    if out is None:
-        out = {k: torch.empty((_nframes(k), nvox) if _nframes(k) > 1 else (nvox,), dtype=torch.float32, device=dwi.device)
-               for k in DKI_FIELDS if kt or k != "kt"}
-    for k in DKI_FIELDS:
-        if k in out:
-            _chk_dev(out[k], torch.float32, k)
-            if out[k].numel() != _nframes(k) * nvox:
-                raise ValueError("out[%r] has %d elements, expected %d" % (k, out[k].numel(), _nframes(k) * nvox))
-    o = _lib.DkiOut(*[out[k].data_ptr() if k in out else None for k in DKI_FIELDS])
-    _lib.check(_lib.lib().fibd_dki_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, C.byref(o), _stream_ptr(stream)))
+    nvox = _fit_args(plan, dwi, mask)
+    with Launch(dwi, stream) as L:
+        if out is None:
+            out = {k: L.empty((_nframes(k), nvox) if _nframes(k) > 1 else (nvox,), torch.float32) for k in DKI_FIELDS if kt or k != "kt"}
+        else:
+            for k in DKI_FIELDS:
+                if k in out:
+                    tensor(out[k], torch.float32, "out[%r]" % k, ref=plan, n=_nframes(k) * nvox)
+        o = _lib.DkiOut(*[out[k].data_ptr() if k in out else None for k in DKI_FIELDS])
+        _lib.check(_lib.lib().fibd_dki_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, C.byref(o), L.sp))
     return out

@@ -9,6 +9,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._dev import Launch, Plan, stream_ptr as _stream_ptr, tensor
 from .mri import MRI
 
 DTI_FIELDS = ("s0", "eigval1", "eigval2", "eigval3", "eigvec1", "eigvec2", "eigvec3", "rd", "md", "fa")
@@ -108,12 +109,12 @@ def adc_fit(dwi: MRI, mask: MRI, device: int = 0):
 # ---------------------------------------------------------------------------------------------
 # device-resident form (torch tensors are plumbing: device memory + streams)
 # ---------------------------------------------------------------------------------------------
-class DtiPlan:
+class DtiPlan(Plan):
     """DTIwork / ADCwork (dti.jl:39-155) resident on one GPU.  bvec=None builds the ADC plan."""
+    _destroy = "fib_dti_plan_destroy"
 
     def __init__(self, bval, bvec=None, device: int = 0):
-        self._h = C.c_void_p()
-        self.device = device
+        Plan.__init__(self, device)
         bval = np.ascontiguousarray(bval, np.float32)
         self.nvol = int(bval.shape[0])
         bv = None if bvec is None else np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
@@ -133,67 +134,35 @@ class DtiPlan:
         _lib.check(_lib.lib().fibd_dti_last_partial_count(self._h, _stream_ptr(stream), C.byref(c)))
         return int(c.value)
 
-    def close(self):
-        if self._h:
-            _lib.lib().fib_dti_plan_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _stream_ptr(stream):
-    if stream is None:
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    return C.c_void_p(getattr(stream, "cuda_stream", stream))
-
-
-def _sync(stream):
-    """wait for `stream` (a torch stream, a raw hipStream_t handle, or None = the current stream)"""
+def _fit_args(plan, dwi, mask):
+    """the inputs of a plan's fit: dwi float32 [plan.nvol, nvox], mask uint8 [nvox], both on the plan's device -> nvox"""
     import torch
-    if stream is None:
-        torch.cuda.current_stream().synchronize()
-    elif hasattr(stream, "synchronize"):
-        stream.synchronize()
-    else:                                               # a raw handle: wait for that stream, not for the current device
-        torch.cuda.ExternalStream(int(getattr(stream, "value", stream) or 0)).synchronize()
-
-
-def _chk_dev(t, dtype, what):
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise TypeError("%s must be a contiguous CUDA tensor of dtype %s" % (what, dtype))
-    return t
+    nvox = tensor(mask, torch.uint8, "mask", ref=plan).numel()
+    tensor(dwi, torch.float32, "dwi [nvol, nvox]", ref=plan, n=nvox * plan.nvol)
+    return nvox
 
 
 def dti_fit_device(plan: DtiPlan, dwi, mask, out=None, stream=None):
     """dwi: float32 CUDA tensor [nvol, nvox] (planar: frame slowest == MRI.vol memory order);
-    mask: uint8 CUDA tensor [nvox].  Returns dict of tensors: scalars [nvox], eigvecs [3, nvox]."""
+    mask: uint8 CUDA tensor [nvox].  Returns dict of tensors: scalars [nvox], eigvecs [3, nvox] (`out`: such a dict to write into)."""
     import torch
-    _chk_dev(dwi, torch.float32, "dwi")
-    _chk_dev(mask, torch.uint8, "mask")
-    nvox = mask.numel()
-    if dwi.numel() != nvox * plan.nvol:
-        raise ValueError("dwi has %d elements, expected nvol*nvox = %d" % (dwi.numel(), nvox * plan.nvol))
-    if out is None:
-        out = {k: torch.empty((3, nvox) if "vec" in k else (nvox,), dtype=torch.float32, device=dwi.device)
-               for k in DTI_FIELDS}
-    o = _lib.DtiOut(*[out[k].data_ptr() for k in DTI_FIELDS])
-    _lib.check(_lib.lib().fibd_dti_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, C.byref(o), _stream_ptr(stream)))
+    nvox = _fit_args(plan, dwi, mask)
+    with Launch(dwi, stream) as L:
+        if out is None:
+            out = {k: L.empty((3, nvox) if "vec" in k else (nvox,), torch.float32) for k in DTI_FIELDS}
+        else:
+            for k in DTI_FIELDS:
+                tensor(out[k], torch.float32, "out[%r]" % k, ref=plan, n=(3 if "vec" in k else 1) * nvox)
+        o = _lib.DtiOut(*[out[k].data_ptr() for k in DTI_FIELDS])
+        _lib.check(_lib.lib().fibd_dti_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, C.byref(o), L.sp))
     return out
 
 
 def adc_fit_device(plan: DtiPlan, dwi, mask, stream=None):
     import torch
-    _chk_dev(dwi, torch.float32, "dwi")
-    _chk_dev(mask, torch.uint8, "mask")
-    nvox = mask.numel()
-    adc = torch.empty(nvox, dtype=torch.float32, device=dwi.device)
-    s0 = torch.empty(nvox, dtype=torch.float32, device=dwi.device)
-    _lib.check(_lib.lib().fibd_adc_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, adc.data_ptr(), s0.data_ptr(),
-                                       _stream_ptr(stream)))
+    nvox = _fit_args(plan, dwi, mask)
+    with Launch(dwi, stream) as L:
+        adc, s0 = L.empty(nvox, torch.float32), L.empty(nvox, torch.float32)
+        _lib.check(_lib.lib().fibd_adc_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, adc.data_ptr(), s0.data_ptr(), L.sp))
     return adc, s0

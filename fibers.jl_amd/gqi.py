@@ -7,7 +7,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from .dti import _check_tables, _chk_dev, _dwi_arg, _mask_arg, _mask_checked, _stream_ptr
+from ._dev import ArgError, Launch, Plan, stream_ptr, tensor
+from .dti import _check_tables, _dwi_arg, _fit_args, _mask_arg, _mask_checked
 from .mri import MRI
 from .odf import ODF, sphere_642
 
@@ -121,18 +122,19 @@ def find_peaks_work(odf, odf_dirs: ODF = sphere_642, device: int = 0):
 ODF_FORMATS = {"default": 0, "fp16x2": 1, "bf16x3": 2, "f32": 3}      # FIB_ODF_FORMAT_* (include/fibers_hip.h)
 
 
-class OdfPlan:
+class OdfPlan(Plan):
     """GQIwork (gqi.jl:32-82) or DSIwork (dsi.jl:41-143) resident on one GPU.  `format`: the operand format of the contraction
     (include/fibers_hip.h FIB_ODF_FORMAT_*): "fp16x2" (two fp16 pieces per f32 operand, the default), "bf16x3" (three exact bf16
     pieces), "f32" (f32 MFMA chain) or "default" (the environment's choice); `plan.format` is what the kernels actually run."""
+    _destroy = "fib_odf_plan_destroy"
 
     def __init__(self, kind: str, bval, bvec, odf_dirs: ODF = sphere_642, sigma: float = 1.25,
                  hann_width: int = 32, device: int = 0, format: str = "default"):
         if format not in ODF_FORMATS:
             raise ValueError("format must be one of %s" % sorted(ODF_FORMATS))
         fmt = ODF_FORMATS[format]
-        self._h = C.c_void_p()
-        self.kind, self.device = kind, device
+        Plan.__init__(self, device)
+        self.kind = kind
         bval = np.ascontiguousarray(bval, np.float32)
         bvec = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
         v, f = _odf_args(odf_dirs)
@@ -158,7 +160,7 @@ class OdfPlan:
     def list_unit(self, stream=None) -> str:
         """diagnostic: the unit of the voxel list the next reconstruction call on this plan will use ("octets": aligned groups of 32
         voxels, the default; "quads": aligned groups of 4, chosen by the previous call for sparse masks).  Results do not depend on it."""
-        code = _lib.lib().fib_odf_plan_list_unit(self._h, _stream_ptr(stream))
+        code = _lib.lib().fib_odf_plan_list_unit(self._h, stream_ptr(stream))
         if code < 0:
             _lib.check(code)
         return "octets" if code else "quads"
@@ -171,17 +173,6 @@ class OdfPlan:
         _lib.check(L.fib_odf_plan_matrix(self._h, A.ctypes.data, None, None, None))
         return A
 
-    def close(self):
-        if self._h:
-            _lib.lib().fib_odf_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def odf_rec_device(plan: OdfPlan, dwi, mask, out: Optional[dict] = None, normalize: bool = True, stream=None,
                    out_prezeroed: bool = False, separate_peaks: bool = False, raw_odfmax: bool = False):
@@ -191,26 +182,27 @@ def odf_rec_device(plan: OdfPlan, dwi, mask, out: Optional[dict] = None, normali
     voxel count is not a multiple of 4 (such a piece cannot run the fused peak scan, and the two forms differ at rounding level).
     raw_odfmax = FIB_ODF_RAW_ODFMAX: odfmax = {maximum of the means that are not NaN, NaN flag}, the form a MAX all-reduce takes."""
     import torch
-    _chk_dev(dwi, torch.float32, "dwi")
-    _chk_dev(mask, torch.uint8, "mask")
-    nvox = mask.numel()
-    if dwi.numel() != nvox * plan.nvol:
-        raise ValueError("dwi has %d elements, expected nvol*nvox = %d" % (dwi.numel(), nvox * plan.nvol))
-    dev = dwi.device
-    if out is None:
-        out = dict(odf=torch.empty((plan.nvert, nvox), dtype=torch.float32, device=dev),
-                   peak=[torch.empty((3, nvox), dtype=torch.float32, device=dev) for _ in range(3)],
-                   qa=[torch.empty(nvox, dtype=torch.float32, device=dev) for _ in range(3)],
-                   odfmax=torch.empty(2, dtype=torch.float32, device=dev))
-        if plan.kind == "dsi":
-            out["pdf"] = torch.empty((plan.nvol, nvox), dtype=torch.float32, device=dev)
-    pdf_ptr = out["pdf"].data_ptr() if plan.kind == "dsi" else None
-    _lib.check(_lib.lib().fibd_odf_rec(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, pdf_ptr, out["odf"].data_ptr(),
-                                       _lib.P3(*[t.data_ptr() for t in out["peak"]]),
-                                       _lib.P3(*[t.data_ptr() for t in out["qa"]]),
-                                       out["odfmax"].data_ptr(),
-                                       (1 if normalize else 0) | (2 if out_prezeroed else 0) | (4 if separate_peaks else 0) | (8 if raw_odfmax else 0),
-                                       _stream_ptr(stream)))
+    nvox = _fit_args(plan, dwi, mask)
+    dsi = plan.kind == "dsi"
+    with Launch(dwi, stream) as L:
+        if out is None:
+            out = dict(odf=L.empty((plan.nvert, nvox), torch.float32), peak=[L.empty((3, nvox), torch.float32) for _ in range(3)],
+                       qa=[L.empty(nvox, torch.float32) for _ in range(3)], odfmax=L.empty(2, torch.float32))
+            if dsi:
+                out["pdf"] = L.empty((plan.nvol, nvox), torch.float32)
+        else:
+            for k, n in [("odf", plan.nvert * nvox), ("odfmax", 2)] + ([("pdf", plan.nvol * nvox)] if dsi else []):
+                tensor(out[k], torch.float32, "out['%s']" % k, ref=plan, n=n)
+            for k, n in (("peak", 3 * nvox), ("qa", nvox)):
+                if len(out[k]) != 3:
+                    raise ArgError("out['%s'] must be three tensors" % k)
+                for t in out[k]:
+                    tensor(t, torch.float32, "out['%s']" % k, ref=plan, n=n)
+        _lib.check(_lib.lib().fibd_odf_rec(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, out["pdf"].data_ptr() if dsi else None,
+                                           out["odf"].data_ptr(), _lib.P3(*[t.data_ptr() for t in out["peak"]]),
+                                           _lib.P3(*[t.data_ptr() for t in out["qa"]]), out["odfmax"].data_ptr(),
+                                           (1 if normalize else 0) | (2 if out_prezeroed else 0) | (4 if separate_peaks else 0) | (8 if raw_odfmax else 0),
+                                           L.sp))
     return out
 
 
@@ -218,22 +210,31 @@ def qa_normalize_device(qa, odfmax, stream=None, raw=False):
     """qa[k] ./= odfmax (gqi.jl:166-168).  odfmax: a float, or a float32 CUDA tensor whose first element is the divisor (e.g.
     the all-reduced `out["odfmax"]`: it never leaves the device).  raw: the tensor is the pair {maximum of the non-NaN means, NaN
     flag} (odf_rec_device(raw_odfmax=True), all-reduced): the divisor is NaN if the flag is set, and odfmax[0] becomes the divisor."""
-    nvox = qa[0].numel()
-    if raw:
-        _lib.check(_lib.lib().fibd_qa_normalize_pair(_lib.P3(*[t.data_ptr() for t in qa]), nvox, odfmax.data_ptr(), _stream_ptr(stream)))
-    elif hasattr(odfmax, "data_ptr"):
-        _lib.check(_lib.lib().fibd_qa_normalize_dev(_lib.P3(*[t.data_ptr() for t in qa]), nvox, odfmax.data_ptr(), _stream_ptr(stream)))
-    else:
-        _lib.check(_lib.lib().fibd_qa_normalize(_lib.P3(*[t.data_ptr() for t in qa]), nvox, float(odfmax), _stream_ptr(stream)))
+    import torch
+    if len(qa) != 3:
+        raise ArgError("qa must be three tensors")
+    nvox = tensor(qa[0], torch.float32, "qa[0]").numel()
+    for t in qa[1:]:
+        tensor(t, torch.float32, "qa", ref=qa[0], n=nvox)
+    on_device = raw or hasattr(odfmax, "data_ptr")
+    if on_device:
+        tensor(odfmax, torch.float32, "odfmax", ref=qa[0], unit=2 if raw else 1)
+    q = _lib.P3(*[t.data_ptr() for t in qa])
+    with Launch(qa[0], stream) as L:
+        if raw:
+            _lib.check(_lib.lib().fibd_qa_normalize_pair(q, nvox, odfmax.data_ptr(), L.sp))
+        elif on_device:
+            _lib.check(_lib.lib().fibd_qa_normalize_dev(q, nvox, odfmax.data_ptr(), L.sp))
+        else:
+            _lib.check(_lib.lib().fibd_qa_normalize(q, nvox, float(odfmax), L.sp))
 
 
 def find_peaks_device(plan: OdfPlan, odf, stream=None):
     """find_peaks!(W) (gqi.jl:180) over a planar ODF tensor [nvert, nvox] ->
     (isort_top int32 [3, nvox] 0-based, nvalid int32 [nvox])"""
     import torch
-    _chk_dev(odf, torch.float32, "odf")
-    nvox = odf.numel() // plan.nvert
-    top = torch.empty((3, nvox), dtype=torch.int32, device=odf.device)
-    nvalid = torch.empty(nvox, dtype=torch.int32, device=odf.device)
-    _lib.check(_lib.lib().fibd_find_peaks(plan._h, odf.data_ptr(), nvox, top.data_ptr(), nvalid.data_ptr(), _stream_ptr(stream)))
+    nvox = tensor(odf, torch.float32, "odf [nvert, nvox]", ref=plan, unit=plan.nvert).numel() // plan.nvert
+    with Launch(odf, stream) as L:
+        top, nvalid = L.empty((3, nvox), torch.int32), L.empty(nvox, torch.int32)
+        _lib.check(_lib.lib().fibd_find_peaks(plan._h, odf.data_ptr(), nvox, top.data_ptr(), nvalid.data_ptr(), L.sp))
     return top, nvalid

@@ -6,7 +6,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from .dti import _check_tables, _chk_dev, _dwi_arg, _mask_checked, _stream_ptr
+from ._dev import ArgError, Launch, Plan, tensor
+from .dti import _check_tables, _dwi_arg, _mask_checked
 from .mri import MRI
 from .odf import ODF, sphere_724
 
@@ -57,16 +58,17 @@ def rumba_rec(dwi: MRI, mask: MRI, odf_dirs: ODF = sphere_724, niter: int = 600,
     return RUMBASD(fodf, sc[0], sc[1], peak, sc[2], sc[3], float(sm.value), float(ss.value))
 
 
-class RumbaPlan:
+class RumbaPlan(Plan):
     """kernel + contraction plans of rumba_rec resident on one GPU"""
+    _destroy = "fib_rumba_plan_destroy"
 
     def __init__(self, bval, bvec, odf_dirs: ODF = sphere_724, lam_para=1.7e-3, lam_perp=0.2e-3, lam_csf=3.0e-3,
                  lam_gm=0.8e-4, device: int = 0):
-        self._h = C.c_void_p()
+        Plan.__init__(self, device)
         bval = np.ascontiguousarray(bval, np.float32)
         bvec = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
         v = np.asfortranarray(odf_dirs.vertices, dtype=np.float32)
-        self.nvert, self.nvol, self.device = odf_dirs.nvert, int(bval.shape[0]), device
+        self.nvert, self.nvol = odf_dirs.nvert, int(bval.shape[0])
         _lib.check(_lib.lib().fib_rumba_plan_create(device, bval.ctypes.data, bvec.ctypes.data, self.nvol, v.ctypes.data,
                                                     v.shape[0], float(lam_para), float(lam_perp), float(lam_csf),
                                                     float(lam_gm), C.byref(self._h)))
@@ -79,17 +81,6 @@ class RumbaPlan:
         _lib.check(L.fib_rumba_plan_kernel(self._h, K.ctypes.data, None, None))
         return K
 
-    def close(self):
-        if self._h:
-            _lib.lib().fib_rumba_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def rumba_rec_device(plan: RumbaPlan, dwi, mask, shape, niter=600, ncoils=1, coil_combine="SMF-SENSE", ipat_factor=1,
                      use_tv=True, stream=None, out=None):
@@ -97,30 +88,27 @@ def rumba_rec_device(plan: RumbaPlan, dwi, mask, shape, niter=600, ncoils=1, coi
     gfa, var [nvox], peak [5][3,nvox], snr_mean, snr_std).  out: such a dict of tensors to write into (every element is
     written: zeros outside the mask)."""
     import torch
-    _chk_dev(dwi, torch.float32, "dwi")
-    _chk_dev(mask, torch.uint8, "mask")
-    nx, ny, nz = shape
+    nx, ny, nz = (int(v) for v in shape)
     nvox = nx * ny * nz
-    if dwi.dim() != 2 or dwi.shape[1] != nvox or dwi.shape[0] != plan.nvol or mask.numel() != nvox:
-        raise ValueError("dwi must be [%d, %d] and mask [%d] for shape %s" % (plan.nvol, nvox, nvox, tuple(shape)))
-    dev = dwi.device
-    if out is None:
-        out = dict(fodf=torch.empty((plan.nvert, nvox), dtype=torch.float32, device=dev),
-                   fgm=torch.empty(nvox, dtype=torch.float32, device=dev), fcsf=torch.empty(nvox, dtype=torch.float32, device=dev),
-                   gfa=torch.empty(nvox, dtype=torch.float32, device=dev), var=torch.empty(nvox, dtype=torch.float32, device=dev),
-                   peak=[torch.empty((3, nvox), dtype=torch.float32, device=dev) for _ in range(5)])
-    else:
-        want = dict(fodf=(plan.nvert, nvox), fgm=(nvox,), fcsf=(nvox,), gfa=(nvox,), var=(nvox,))
-        for k, shp in want.items():
-            if tuple(_chk_dev(out[k], torch.float32, "out['%s']" % k).shape) != shp:
-                raise ValueError("out['%s'] must have shape %s" % (k, shp))
-        if len(out["peak"]) != 5 or any(tuple(_chk_dev(t, torch.float32, "out['peak']").shape) != (3, nvox) for t in out["peak"]):
-            raise ValueError("out['peak'] must be five [3, %d] tensors" % nvox)
-    ro = _lib.RumbaOut(out["fodf"].data_ptr(), out["fgm"].data_ptr(), out["fcsf"].data_ptr(), out["gfa"].data_ptr(),
-                       out["var"].data_ptr(), (C.c_void_p * 5)(*[t.data_ptr() for t in out["peak"]]))
-    sm, ss = C.c_float(0), C.c_float(0)
-    _lib.check(_lib.lib().fibd_rumba_rec(plan._h, dwi.data_ptr(), mask.data_ptr(), nx, ny, nz, int(niter), int(ncoils),
-                                         _coil_mode(coil_combine), int(ipat_factor), 1 if use_tv else 0, C.byref(ro),
-                                         C.byref(sm), C.byref(ss), _stream_ptr(stream)))
+    tensor(dwi, torch.float32, "dwi", ref=plan, shape=(plan.nvol, nvox))
+    tensor(mask, torch.uint8, "mask", ref=plan, n=nvox)
+    want = dict(fodf=(plan.nvert, nvox), fgm=(nvox,), fcsf=(nvox,), gfa=(nvox,), var=(nvox,))
+    with Launch(dwi, stream) as L:
+        if out is None:
+            out = {k: L.empty(shp, torch.float32) for k, shp in want.items()}
+            out["peak"] = [L.empty((3, nvox), torch.float32) for _ in range(5)]
+        else:
+            for k, shp in want.items():
+                tensor(out[k], torch.float32, "out['%s']" % k, ref=plan, shape=shp)
+            if len(out["peak"]) != 5:
+                raise ArgError("out['peak'] must be five [3, %d] tensors" % nvox)
+            for t in out["peak"]:
+                tensor(t, torch.float32, "out['peak']", ref=plan, shape=(3, nvox))
+        ro = _lib.RumbaOut(out["fodf"].data_ptr(), out["fgm"].data_ptr(), out["fcsf"].data_ptr(), out["gfa"].data_ptr(),
+                           out["var"].data_ptr(), (C.c_void_p * 5)(*[t.data_ptr() for t in out["peak"]]))
+        sm, ss = C.c_float(0), C.c_float(0)
+        _lib.check(_lib.lib().fibd_rumba_rec(plan._h, dwi.data_ptr(), mask.data_ptr(), nx, ny, nz, int(niter), int(ncoils),
+                                             _coil_mode(coil_combine), int(ipat_factor), 1 if use_tv else 0, C.byref(ro),
+                                             C.byref(sm), C.byref(ss), L.sp))
     out["snr_mean"], out["snr_std"] = float(sm.value), float(ss.value)
     return out

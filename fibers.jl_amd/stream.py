@@ -7,7 +7,8 @@ from typing import List, Optional, Sequence, Union
 import numpy as np
 
 from . import _lib
-from .dti import _chk_dev, _mask_arg, _stream_ptr, _sync
+from ._dev import ArgError, Launch, sync as _sync, tensor
+from .dti import _mask_arg
 from .mri import MRI
 from .tract import Tract
 
@@ -270,7 +271,7 @@ def angles_to_vectors_device(ang, volres=(1.0, 1.0, 1.0)):
     """angles_to_vectors for a device-resident angle volume (float32 CUDA tensor of nvox angles): planar [3, nvox] vectors by
     the same rules (stream.jl:147-172) -- radians if all values lie in [-pi/2, pi/2] (+- eps), degrees if in [-90, 90]."""
     import torch
-    _chk_dev(ang, torch.float32, "angles")
+    tensor(ang, torch.float32, "angles")
     a = ang.reshape(-1)
     thru = int(np.argmax(np.asarray(volres, np.float32)))
     sd = [c for c in range(3) if c != thru]
@@ -295,19 +296,21 @@ def stream_field_device(ovec: List, f: Optional[List] = None, f_thresh: float = 
     mask uint8 [nvox] (already `> 0`-tested) or None.  Returns (field float32 [nvox, nvec, 4], mask uint8 [nvox])."""
     import torch
     nvec = len(ovec)
-    nvox = ovec[0].numel() // 3
-    for t in ovec:
-        _chk_dev(t, torch.float32, "ovec")
-    dev = ovec[0].device
-    field = torch.empty((nvox, nvec, 4), dtype=torch.float32, device=dev)
-    mout = torch.empty(nvox, dtype=torch.uint8, device=dev)
+    nvox = tensor(ovec[0], torch.float32, "ovec[0] [3, nvox]", unit=3).numel() // 3
+    for t in ovec[1:]:
+        tensor(t, torch.float32, "ovec", ref=ovec[0], n=3 * nvox)
+    if f is not None and len(f) != nvec:
+        raise ArgError("need one amplitude volume per orientation volume")
+    for what, t, dt in [("f", x, torch.float32) for x in f or ()] + [("fa", fa, torch.float32), ("mask", mask, torch.uint8)]:
+        if t is not None:
+            tensor(t, dt, what, ref=ovec[0], n=nvox)
     ov = (C.c_void_p * nvec)(*[t.data_ptr() for t in ovec])
-    fv = None if f is None else (C.c_void_p * nvec)(*[_chk_dev(t, torch.float32, "f").data_ptr() for t in f])
-    _lib.check(_lib.lib().fibd_stream_field(nvec, nvox, ov, fv, float(np.float32(f_thresh)),
-                                            None if fa is None else _chk_dev(fa, torch.float32, "fa").data_ptr(),
-                                            float(np.float32(fa_thresh)),
-                                            None if mask is None else _chk_dev(mask, torch.uint8, "mask").data_ptr(),
-                                            field.data_ptr(), mout.data_ptr(), _stream_ptr(stream)))
+    fv = None if f is None else (C.c_void_p * nvec)(*[t.data_ptr() for t in f])
+    with Launch(ovec[0], stream) as L:
+        field, mout = L.empty((nvox, nvec, 4), torch.float32), L.empty(nvox, torch.uint8)
+        _lib.check(_lib.lib().fibd_stream_field(nvec, nvox, ov, fv, float(np.float32(f_thresh)), None if fa is None else fa.data_ptr(),
+                                                float(np.float32(fa_thresh)), None if mask is None else mask.data_ptr(),
+                                                field.data_ptr(), mout.data_ptr(), L.sp))
     return field, mout
 
 
@@ -316,9 +319,10 @@ def _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, an
     """the preamble of the device-resident tracer calls: checks field / seeds / sublist, resolves `workspace` ("default": the host
     mirror's arena for the field's device) and returns the fib_stream_params"""
     import torch
-    _chk_dev(field, torch.float32, "field")
-    _chk_dev(seeds, torch.int64, "seeds")
-    _chk_dev(sublist, torch.float32, "sublist")
+    nx, ny, nz = (int(v) for v in shape)
+    tensor(field, torch.float32, "field", shape=(nx * ny * nz, None, 4))
+    tensor(seeds, torch.int64, "seeds", ref=field)
+    tensor(sublist, torch.float32, "sublist", ref=field, shape=(None, 3))
     ws = default_workspace(field.device.index or 0) if isinstance(workspace, str) else workspace
     return _params(shape, field.shape[1], len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist, search_ang, ws, interp,
                    integrator=integrator)
@@ -340,36 +344,40 @@ def stream_device(field, shape, seeds, sublist, len_min=3, len_max=None, ang_thr
     import torch
     prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
                          search_dist, search_ang, integrator=integrator)
+    if lcms is not None:
+        tensor(lcms, torch.float32, "lcms [10, nvox]", ref=field, n=10 * field.shape[0])
     job = C.c_void_p()
     nl, npnt = C.c_int64(0), C.c_int64(0)
-    L = _lib.lib()
-    sp = _stream_ptr(stream)
-    if lcms is None:
-        _lib.check(L.fibd_stream_trace(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(),
-                                       sublist.data_ptr(), sublist.shape[0], sp, C.byref(job), C.byref(nl), C.byref(npnt)))
-    else:
-        _chk_dev(lcms, torch.float32, "lcms")
-        _lib.check(L.fibd_stream_trace_lcm(C.byref(prm), field.data_ptr(), lcms.data_ptr(), float(np.float32(lcm_thresh)),
-                                           int(strdims[0]), int(strdims[1]), int(rng_seed), seeds.data_ptr(), seeds.numel(),
-                                           sublist.data_ptr(), sublist.shape[0], sp, C.byref(job), C.byref(nl), C.byref(npnt)))
-    try:
-        dev = field.device
-        out = dict(npts=torch.empty(nl.value, dtype=torch.int32, device=dev),
-                   seed_index=torch.empty(nl.value, dtype=torch.int64, device=dev),
-                   xyz=torch.empty((npnt.value, 3), dtype=torch.float32, device=dev) if xyz_out is None
-                   else xyz_out(npnt.value)[:3 * npnt.value].view(npnt.value, 3))
+    lib = _lib.lib()
+    with Launch(field, stream) as L:
         if lcms is None:
-            _lib.check(L.fibd_stream_pack(job, out["npts"].data_ptr(), out["seed_index"].data_ptr(), out["xyz"].data_ptr(), sp))
+            _lib.check(lib.fibd_stream_trace(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(),
+                                             sublist.data_ptr(), sublist.shape[0], L.sp, C.byref(job), C.byref(nl), C.byref(npnt)))
         else:
-            out["flags"] = torch.empty(npnt.value, dtype=torch.uint8, device=dev)
-            _lib.check(L.fibd_stream_pack_flags(job, out["npts"].data_ptr(), out["seed_index"].data_ptr(),
-                                                out["xyz"].data_ptr(), out["flags"].data_ptr(), sp))
-        if want_all_npts:
-            out["all_npts"] = torch.empty(seeds.numel() * sublist.shape[0], dtype=torch.int32, device=dev)
-            _lib.check(L.fibd_stream_all_npts(job, out["all_npts"].data_ptr(), sp))
-        _sync(stream)
-    finally:
-        L.fib_stream_job_destroy(job)
+            _lib.check(lib.fibd_stream_trace_lcm(C.byref(prm), field.data_ptr(), lcms.data_ptr(), float(np.float32(lcm_thresh)),
+                                                 int(strdims[0]), int(strdims[1]), int(rng_seed), seeds.data_ptr(), seeds.numel(),
+                                                 sublist.data_ptr(), sublist.shape[0], L.sp, C.byref(job), C.byref(nl), C.byref(npnt)))
+        try:
+            if xyz_out is None:
+                xyz = L.empty((npnt.value, 3), torch.float32)
+            else:
+                xyz = tensor(xyz_out(npnt.value), torch.float32, "the tensor xyz_out returns", ref=field)
+                if xyz.numel() < 3 * npnt.value:
+                    raise ArgError("xyz_out returned %d elements for %d points" % (xyz.numel(), npnt.value))
+                xyz = xyz.view(-1)[:3 * npnt.value].view(npnt.value, 3)
+            out = dict(npts=L.empty(nl.value, torch.int32), seed_index=L.empty(nl.value, torch.int64), xyz=xyz)
+            if lcms is None:
+                _lib.check(lib.fibd_stream_pack(job, out["npts"].data_ptr(), out["seed_index"].data_ptr(), xyz.data_ptr(), L.sp))
+            else:
+                out["flags"] = L.empty(npnt.value, torch.uint8)
+                _lib.check(lib.fibd_stream_pack_flags(job, out["npts"].data_ptr(), out["seed_index"].data_ptr(),
+                                                      xyz.data_ptr(), out["flags"].data_ptr(), L.sp))
+            if want_all_npts:
+                out["all_npts"] = L.empty(seeds.numel() * sublist.shape[0], torch.int32)
+                _lib.check(lib.fibd_stream_all_npts(job, out["all_npts"].data_ptr(), L.sp))
+            _sync(stream)
+        finally:
+            lib.fib_stream_job_destroy(job)
     return out
 
 
@@ -391,6 +399,12 @@ class StreamBuffers:
             self.xyz = torch.empty((int(points), 3), dtype=torch.float32, device=self.device)
 
 
+def _buffers_on(buffers, field):
+    """a caller's StreamBuffers live on the field's device (they are made by `reserve`, which sizes the three alike)"""
+    if buffers.npts is not None and buffers.npts.device != field.device:
+        raise ArgError("buffers are on %s, the field on %s" % (buffers.npts.device, field.device))
+
+
 def stream_device_run(field, shape, seeds, sublist, buffers: StreamBuffers = None, len_min=3, len_max=None, ang_thresh=45, step_size=0.5,
                       smooth_coeff=0.2, stream=None, workspace="default", interp="nearest", integrator="euler"):
     """stream_device in ONE library call (fibd_stream_run): trace, scan and pack without a host round trip in between -- from 2^21
@@ -401,22 +415,22 @@ def stream_device_run(field, shape, seeds, sublist, buffers: StreamBuffers = Non
     prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
                          integrator=integrator)
     nl_max = int(seeds.numel()) * int(sublist.shape[0])
-    if buffers is None:
-        buffers = StreamBuffers(field.device)
-    if buffers.npts is None or buffers.npts.numel() == 0:
-        buffers.reserve(nl_max, 32 * nl_max)                    # a first guess; the call below says what is needed
-    L = _lib.lib()
-    sp = _stream_ptr(stream)
     nl, npnt = C.c_int64(0), C.c_int64(0)
-    for attempt in range(2):
-        rc = L.fibd_stream_run(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sublist.data_ptr(), sublist.shape[0],
-                               buffers.npts.data_ptr(), buffers.seed_index.data_ptr(), buffers.npts.numel(),
-                               buffers.xyz.data_ptr(), buffers.xyz.shape[0], C.byref(nl), C.byref(npnt), sp)
-        if rc == _lib.FIB_ERR_CAPACITY and attempt == 0:
-            buffers.reserve(int(nl.value * 1.02) + 16, int(npnt.value * 1.02) + 1024)
-            continue
-        _lib.check(rc)
-        break
+    with Launch(field, stream) as L:
+        if buffers is None:
+            buffers = StreamBuffers(field.device)
+        _buffers_on(buffers, field)
+        if buffers.npts is None or buffers.npts.numel() == 0:
+            buffers.reserve(nl_max, 32 * nl_max)                    # a first guess; the call below says what is needed
+        for attempt in range(2):
+            rc = _lib.lib().fibd_stream_run(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sublist.data_ptr(), sublist.shape[0],
+                                            buffers.npts.data_ptr(), buffers.seed_index.data_ptr(), buffers.npts.numel(),
+                                            buffers.xyz.data_ptr(), buffers.xyz.shape[0], C.byref(nl), C.byref(npnt), L.sp)
+            if rc == _lib.FIB_ERR_CAPACITY and attempt == 0:
+                buffers.reserve(int(nl.value * 1.02) + 16, int(npnt.value * 1.02) + 1024)
+                continue
+            _lib.check(rc)
+            break
     return dict(npts=buffers.npts[: nl.value], seed_index=buffers.seed_index[: nl.value], xyz=buffers.xyz[: npnt.value], buffers=buffers)
 
 
@@ -431,10 +445,10 @@ def stream_device_run_enqueue(field, shape, seeds, sublist, buffers: StreamBuffe
                          integrator=integrator)
     if buffers is None or buffers.npts is None or buffers.npts.numel() == 0:
         raise ValueError("stream_device_run_enqueue needs sized buffers (call stream_device_run once)")
-    if counts is None:
-        counts = torch.zeros(2, dtype=torch.int64, device=field.device)
-    _chk_dev(counts, torch.int64, "counts")
-    _lib.check(_lib.lib().fibd_stream_run_enqueue(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sublist.data_ptr(),
-                                                  sublist.shape[0], buffers.npts.data_ptr(), buffers.seed_index.data_ptr(), buffers.npts.numel(),
-                                                  buffers.xyz.data_ptr(), buffers.xyz.shape[0], counts.data_ptr(), _stream_ptr(stream)))
+    _buffers_on(buffers, field)
+    with Launch(field, stream) as L:
+        counts = torch.zeros(2, dtype=torch.int64, device=field.device) if counts is None else tensor(counts, torch.int64, "counts", ref=field, n=2)
+        _lib.check(_lib.lib().fibd_stream_run_enqueue(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sublist.data_ptr(),
+                                                      sublist.shape[0], buffers.npts.data_ptr(), buffers.seed_index.data_ptr(), buffers.npts.numel(),
+                                                      buffers.xyz.data_ptr(), buffers.xyz.shape[0], counts.data_ptr(), L.sp))
     return buffers, counts

@@ -4,13 +4,12 @@
 of the tensor fit (csrc/sym3_eigen.inc).  `st_recon` builds those six volumes from a scalar volume -- Gaussian smoothing,
 Scharr gradients, their products, Gaussian smoothing of the products, all imfilter(..., "reflect") -- and decomposes them, in
 two HIP kernels (csrc/structens.hip)."""
-import contextlib
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from .dti import _stream_ptr, _sync
+from ._dev import ArgError, Launch, tensor, work as _work
 
 
 def st_eigen(Sxx, Sxy, Sxz, Syy, Syz, Szz, device=0):
@@ -29,21 +28,18 @@ def st_eigen(Sxx, Sxy, Sxz, Syy, Syz, Szz, device=0):
 
 
 def st_eigen_device(S, stream=None):
-    """Device tier: S = six float32 CUDA tensors [nvox]; returns (eigvec [9, nvox], eigval [3, nvox]) with
-    eigvec[i + 3 j] = component i of eigenvector j."""
+    """Device tier: S = six float32 CUDA tensors [nvox] on one device; returns (eigvec [9, nvox], eigval [3, nvox]) with
+    eigvec[i + 3 j] = component i of eigenvector j.  `stream`: _dev.Launch."""
     import torch
     if len(S) != 6:
-        raise ValueError("six volumes expected")
-    for t in S:
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise ValueError("contiguous float32 CUDA tensors expected")
-    nvox = S[0].numel()
-    eigvec = torch.empty((9, nvox), dtype=torch.float32, device=S[0].device)
-    eigval = torch.empty((3, nvox), dtype=torch.float32, device=S[0].device)
+        raise ArgError("six volumes expected")
+    nvox = tensor(S[0], torch.float32, "S[0]").numel()
+    for c in range(1, 6):
+        tensor(S[c], torch.float32, "S[%d]" % c, ref=S[0], n=nvox)
     ptrs = (C.c_void_p * 6)(*[t.data_ptr() for t in S])
-    sp = None if stream is None else C.c_void_p(stream.cuda_stream)
-    with torch.cuda.device(S[0].device):
-        _lib.check(_lib.lib().fibd_st_eigen(ptrs, nvox, eigvec.data_ptr(), eigval.data_ptr(), sp))
+    with Launch(S[0], stream) as L:
+        eigvec, eigval = L.empty((9, nvox), torch.float32), L.empty((3, nvox), torch.float32)
+        _lib.check(_lib.lib().fibd_st_eigen(ptrs, nvox, eigvec.data_ptr(), eigval.data_ptr(), L.sp))
     return eigvec, eigval
 
 
@@ -74,36 +70,34 @@ def st_recon_halo(sigma, rho):
     return h.value
 
 
+def st_recon_work_size(nx, ny, nz, sigma, rho):
+    """bytes of device scratch st_recon_device needs for nz output planes (fibd_st_recon_work_size)"""
+    b = C.c_uint64()
+    _lib.check(_lib.lib().fibd_st_recon_work_size(int(nx), int(ny), int(nz), float(sigma), float(rho), C.byref(b)))
+    return int(b.value)
+
+
 def st_recon_device(vol, shape, sigma, rho, stream=None, S_out=False, zin0=0, z0=0, z1=None):
     """Device tier of st_recon: vol = a contiguous float32 CUDA tensor holding planes [zin0, zin0 + vol.numel() / (nx*ny)) of
     the nx*ny*nz volume `shape` (x fastest).  Returns (eigvec [9, n], eigval [3, n]) for output planes [z0, z1) (default: all),
     st_eigen_device's layout, plus S [6, n] (Sxx Sxy Sxz Syy Syz Szz, the smoothed tensor) when S_out.  vol must hold the
     planes st_recon_halo(sigma, rho) beyond [z0, z1) on each side (as far as the volume goes).
     `stream`: a torch stream, a raw hipStream_t handle, or None (the current stream).  The kernels are enqueued on it and vol must
-    be ready there.  With a torch stream the outputs and the gradient workspace are allocated on that stream, so the caching
-    allocator hands the workspace out again only to work ordered after these kernels; with a raw handle the call waits for the
-    stream before it lets the workspace go."""
+    be ready there.  The outputs and the gradient workspace are allocated by _dev.Launch: on a torch stream the caching allocator
+    hands the workspace out again only to work ordered after these kernels; with a raw handle the call waits for the stream before
+    it lets the workspace go."""
     import torch
     nx, ny, nz = (int(n) for n in shape)
-    if not (vol.is_cuda and vol.dtype == torch.float32 and vol.is_contiguous()):
-        raise ValueError("a contiguous float32 CUDA tensor expected")
-    if nx <= 0 or ny <= 0 or vol.numel() % (nx * ny):
-        raise ValueError("vol does not hold whole %d x %d planes" % (nx, ny))
+    if nx <= 0 or ny <= 0:
+        raise ArgError("shape %s: nx and ny must be positive" % (tuple(shape),))
+    tensor(vol, torch.float32, "vol (whole %d x %d planes)" % (nx, ny), unit=nx * ny)
     z1 = nz if z1 is None else int(z1)
-    nzin, n = vol.numel() // (nx * ny), nx * ny * (z1 - int(z0))
-    dev = vol.device
-    L = _lib.lib()
-    nbytes = C.c_uint64()
-    _lib.check(L.fibd_st_recon_work_size(nx, ny, max(z1 - int(z0), 1), float(sigma), float(rho), C.byref(nbytes)))
-    on_torch_stream = isinstance(stream, torch.cuda.Stream)
-    with torch.cuda.device(dev), (torch.cuda.stream(stream) if on_torch_stream else contextlib.nullcontext()):
-        eigvec = torch.empty((9, max(n, 0)), dtype=torch.float32, device=dev)
-        eigval = torch.empty((3, max(n, 0)), dtype=torch.float32, device=dev)
-        S = torch.empty((6, max(n, 0)), dtype=torch.float32, device=dev) if S_out else None
-        work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    nzin, n = vol.numel() // (nx * ny), max(nx * ny * (z1 - int(z0)), 0)
+    with Launch(vol, stream) as L:
+        eigvec, eigval = L.empty((9, n), torch.float32), L.empty((3, n), torch.float32)
+        S = L.empty((6, n), torch.float32) if S_out else None
+        work, wb = _work(L, None, st_recon_work_size, "st_recon_work_size", nx, ny, max(z1 - int(z0), 1), sigma, rho)
         sp = (C.c_void_p * 6)(*[S[c].data_ptr() for c in range(6)]) if S_out else None
-        _lib.check(L.fibd_st_recon(vol.data_ptr(), nx, ny, nz, int(zin0), nzin, int(z0), z1, float(sigma), float(rho),
-                                   eigvec.data_ptr(), eigval.data_ptr(), sp, work.data_ptr(), nbytes.value, _stream_ptr(stream)))
-    if stream is not None and not on_torch_stream:     # a raw handle: the allocator cannot order the workspace's reuse after it
-        _sync(stream)
+        _lib.check(_lib.lib().fibd_st_recon(vol.data_ptr(), nx, ny, nz, int(zin0), nzin, int(z0), z1, float(sigma), float(rho),
+                                            eigvec.data_ptr(), eigval.data_ptr(), sp, work.data_ptr(), wb, L.sp))
     return (eigvec, eigval, S) if S_out else (eigvec, eigval)

@@ -5,7 +5,6 @@ section of include/fibers_hip.h.  All compute is in csrc/tractmap.hip; there is 
 
 Host tier: `Tract` / `MRI` in, `MRI` / `Tract` out, through fib_str_*.  Device tier: torch tensors in and out, through fibd_str_* on
 `stream`, taking the entries of stream_device / stream_device_run's dict as they are (no copy, no host round trip)."""
-import contextlib
 import ctypes as C
 from dataclasses import replace
 from typing import Sequence, Union
@@ -13,6 +12,7 @@ from typing import Sequence, Union
 import numpy as np
 
 from . import _lib
+from ._dev import ArgError, Launch, float3, packed as _packed, tensor, work as _work
 from .mri import MRI
 from .tract import Tract
 
@@ -21,12 +21,6 @@ def _mode(mode, accumulate=False):
     if mode not in _lib.DENSITY_MODES:
         raise ValueError("mode must be 'points', 'lines' or 'endpoints', not %r" % (mode,))
     return _lib.DENSITY_MODES[mode] | (_lib.FIB_DENSITY_ACCUMULATE if accumulate else 0)
-
-
-def _packed(tr: Tract):
-    xyz = np.ascontiguousarray(np.asarray(tr.xyz, np.float32).reshape(-1, 3))
-    npts = np.ascontiguousarray(tr.npts, dtype=np.int32)
-    return xyz, npts
 
 
 def _columns(a, n):
@@ -101,8 +95,7 @@ def str_stats(tr: Tract, device: int = 0) -> Tract:
     sc = _columns(tr.scalars, xyz.shape[0])
     ns = sc.shape[1]
     p = np.empty((npts.size, 1 + ns), np.float32)
-    res = (C.c_float * 3)(*[float(v) for v in tr.volres])
-    _lib.check(_lib.lib().fib_str_stats(int(device), xyz.ctypes.data, npts.ctypes.data, npts.size, xyz.shape[0], res,
+    _lib.check(_lib.lib().fib_str_stats(int(device), xyz.ctypes.data, npts.ctypes.data, npts.size, xyz.shape[0], float3(tr.volres),
                                         sc.ctypes.data if ns else None, ns, p.ctypes.data))
     return replace(tr, properties=np.concatenate([_columns(tr.properties, npts.size), p], axis=1))
 
@@ -115,84 +108,49 @@ def str_work_size(nlines: int) -> int:
     return int(b.value)
 
 
-def _on(ref, stream):
-    """allocation context: the tensor's device, and `stream` when it is a torch stream (the allocator then orders reuse after the kernel)"""
+def _points(xyz, what="xyz", ref=None):
+    """float32 [npoints, 3] (on the device of `ref`) -> npoints"""
     import torch
-    st = contextlib.ExitStack()
-    st.enter_context(torch.cuda.device(ref.device))
-    if isinstance(stream, torch.cuda.Stream):
-        st.enter_context(torch.cuda.stream(stream))
-    return st
-
-
-def _points(xyz):
-    import torch
-    if not (xyz.is_cuda and xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.numel() % 3 == 0):
-        raise ValueError("xyz must be a contiguous float32 CUDA tensor [npoints, 3]")
+    if tensor(xyz, torch.float32, what, ref=ref).numel() % 3:
+        raise ArgError("%s must hold whole points [npoints, 3], not %d coordinates" % (what, xyz.numel()))
     return xyz.numel() // 3
 
 
-def _counts(npts, xyz):
+def _lines(xyz, npts):
+    """the checks every tract tool starts with: xyz float32 [npoints, 3], npts int32 [nlines] on its device -> (npoints, nlines)"""
     import torch
-    if not (npts.is_cuda and npts.device == xyz.device and npts.dtype == torch.int32 and npts.is_contiguous()):
-        raise ValueError("npts must be a contiguous int32 CUDA tensor on the points' device")
-    return npts.numel()
-
-
-def _work(work, nlines, ref):
-    import torch
-    need = str_work_size(nlines)
-    if work is None:
-        return torch.empty((need + 7) // 8, dtype=torch.int64, device=ref.device), need
-    if not (work.is_cuda and work.is_contiguous() and work.numel() * work.element_size() >= need and work.data_ptr() % 8 == 0):
-        raise ValueError("work must be an 8-byte aligned CUDA tensor of at least str_work_size(nlines) = %d bytes" % need)
-    return work, work.numel() * work.element_size()
+    return _points(xyz), tensor(npts, torch.int32, "npts", ref=xyz).numel()
 
 
 def str_density_device(xyz, npts, shape, mode: str = "lines", out=None, n_outside=None, work=None, stream=None):
     """fibd_str_density on device tensors: xyz float32 [npoints, 3], npts int32 [nlines] (e.g. the `xyz` and `npts` entries of
     stream_device_run's dict).  Returns (density, n_outside): density uint32 [nx*ny*nz] (x fastest), n_outside int64 [1] -- both
-    device tensors, the call does not wait for the kernels.  `out`: an earlier density to accumulate into.  An invalid `npts`
-    (negative count, sum != npoints) adds nothing and sets n_outside to -1."""
+    device tensors, the call does not wait for the kernels (but see `work`).  `out`: an earlier density to accumulate into.  An
+    invalid `npts` (negative count, sum != npoints) adds nothing and sets n_outside to -1.  `stream`, and `work` = None under a raw
+    handle: _dev.Launch."""
     import torch
-    from .dti import _stream_ptr
-    npnt, nl = _points(xyz), _counts(npts, xyz)
+    npnt, nl = _lines(xyz, npts)
     nx, ny, nz = (int(v) for v in shape)
     if mode == "points" and npnt >= 2 ** 32:
         raise ValueError("counts are uint32: mode 'points' takes fewer than 2^32 points per call")
-    with _on(xyz, stream):
-        if out is None:
-            dens = torch.empty(nx * ny * nz, dtype=torch.uint32, device=xyz.device)
-        else:
-            dens = out
-            if not (dens.is_cuda and dens.dtype == torch.uint32 and dens.is_contiguous() and dens.numel() == nx * ny * nz):
-                raise ValueError("out must be a contiguous uint32 CUDA tensor of nx*ny*nz elements")
-        if n_outside is None:
-            n_outside = torch.empty(1, dtype=torch.int64, device=xyz.device)
-        work, wb = _work(work, nl, xyz)
+    with Launch(xyz, stream) as L:
+        dens = L.empty(nx * ny * nz, torch.uint32) if out is None else tensor(out, torch.uint32, "out", ref=xyz, n=nx * ny * nz)
+        n_outside = L.empty(1, torch.int64) if n_outside is None else tensor(n_outside, torch.int64, "n_outside", ref=xyz, n=1)
+        work, wb = _work(L, work, str_work_size, "str_work_size(nlines)", nl)
         _lib.check(_lib.lib().fibd_str_density(xyz.data_ptr(), npts.data_ptr(), nl, npnt, nx, ny, nz, _mode(mode, out is not None),
-                                               dens.data_ptr(), n_outside.data_ptr(), work.data_ptr(), wb, _stream_ptr(stream)))
+                                               dens.data_ptr(), n_outside.data_ptr(), work.data_ptr(), wb, L.sp))
     return dens, n_outside
 
 
 def str_sample_device(xyz, vol, shape, outside: float = 0.0, out=None, stream=None):
     """fibd_str_sample: vol float32 planar [nframes, nx*ny*nz] (or [nx*ny*nz] for one frame) -> scalars float32 [npoints, nframes]"""
     import torch
-    from .dti import _stream_ptr
     npnt = _points(xyz)
     nx, ny, nz = (int(v) for v in shape)
-    nvox = nx * ny * nz
-    if not (vol.is_cuda and vol.device == xyz.device and vol.dtype == torch.float32 and vol.is_contiguous() and vol.numel() % nvox == 0
-            and vol.numel() >= nvox):
-        raise ValueError("vol must be a contiguous float32 CUDA tensor [nframes, nx*ny*nz] on the points' device")
-    nf = vol.numel() // nvox
-    with _on(xyz, stream):
-        if out is None:
-            out = torch.empty((npnt, nf), dtype=torch.float32, device=xyz.device)
-        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == npnt * nf):
-            raise ValueError("out must be a contiguous float32 CUDA tensor [npoints, nframes]")
-        _lib.check(_lib.lib().fibd_str_sample(xyz.data_ptr(), npnt, vol.data_ptr(), nx, ny, nz, nf, float(outside), out.data_ptr(),
-                                              _stream_ptr(stream)))
+    nf = tensor(vol, torch.float32, "vol", ref=xyz, unit=nx * ny * nz).numel() // (nx * ny * nz)
+    with Launch(xyz, stream) as L:
+        out = L.empty((npnt, nf), torch.float32) if out is None else tensor(out, torch.float32, "out", ref=xyz, n=npnt * nf)
+        _lib.check(_lib.lib().fibd_str_sample(xyz.data_ptr(), npnt, vol.data_ptr(), nx, ny, nz, nf, float(outside), out.data_ptr(), L.sp))
     return out
 
 
@@ -200,21 +158,15 @@ def str_stats_device(xyz, npts, volres, scalars=None, out=None, work=None, strea
     """fibd_str_stats: properties float32 [nlines, 1 + n] -- length in mm, then the mean of each of the n columns of `scalars`
     (float32 [npoints, n] or [npoints]; None: lengths only).  Rows are left unwritten when `npts` is invalid."""
     import torch
-    from .dti import _stream_ptr
-    npnt, nl = _points(xyz), _counts(npts, xyz)
+    npnt, nl = _lines(xyz, npts)
     ns = 0
     if scalars is not None:
-        if not (scalars.is_cuda and scalars.device == xyz.device and scalars.dtype == torch.float32 and scalars.is_contiguous()
-                and (scalars.numel() % npnt == 0 if npnt else scalars.numel() == 0)):
-            raise ValueError("scalars must be a contiguous float32 CUDA tensor [npoints, n] on the points' device")
+        if tensor(scalars, torch.float32, "scalars", ref=xyz).numel():          # (no elements: no columns)
+            tensor(scalars, torch.float32, "scalars", ref=xyz, unit=npnt)
         ns = scalars.numel() // npnt if npnt else (scalars.shape[1] if scalars.dim() == 2 else 0)
-    res = (C.c_float * 3)(*[float(v) for v in volres])
-    with _on(xyz, stream):
-        if out is None:
-            out = torch.empty((nl, 1 + ns), dtype=torch.float32, device=xyz.device)
-        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == nl * (1 + ns)):
-            raise ValueError("out must be a contiguous float32 CUDA tensor [nlines, 1 + n]")
-        work, wb = _work(work, nl, xyz)
-        _lib.check(_lib.lib().fibd_str_stats(xyz.data_ptr(), npts.data_ptr(), nl, npnt, res, scalars.data_ptr() if ns else None, ns,
-                                             out.data_ptr(), work.data_ptr(), wb, _stream_ptr(stream)))
+    with Launch(xyz, stream) as L:
+        out = L.empty((nl, 1 + ns), torch.float32) if out is None else tensor(out, torch.float32, "out", ref=xyz, n=nl * (1 + ns))
+        work, wb = _work(L, work, str_work_size, "str_work_size(nlines)", nl)
+        _lib.check(_lib.lib().fibd_str_stats(xyz.data_ptr(), npts.data_ptr(), nl, npnt, float3(volres), scalars.data_ptr() if ns else None, ns,
+                                             out.data_ptr(), work.data_ptr(), wb, L.sp))
     return out

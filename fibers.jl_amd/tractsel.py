@@ -15,7 +15,8 @@ import numpy as np
 from . import _lib
 from .mri import MRI
 from .tract import Tract
-from .tractmap import _counts, _on, _packed, _points
+from ._dev import ArgError, Launch, float3, packed as _packed, tensor, work as _work
+from .tractmap import _lines, _points
 
 
 def _volume(v, shape, dtype, what):
@@ -123,9 +124,8 @@ def str_connectome(tr: Tract, labels, ids=None, lengths: bool = True, device: in
     wmat = np.zeros((L + 1, L + 1), np.float64) if lengths else None
     assign = np.zeros((npts.size, 2), np.int32)
     n = C.c_int64(0)
-    res = (C.c_float * 3)(*[float(v) for v in tr.volres])
     _lib.check(_lib.lib().fib_str_connectome(int(device), xyz.ctypes.data, npts.ctypes.data, npts.size, xyz.shape[0], shape[0], shape[1], shape[2],
-                                             res, lab.ctypes.data, remap.ctypes.data, remap.size, L, 0, cmat.ctypes.data,
+                                             float3(tr.volres), lab.ctypes.data, remap.ctypes.data, remap.size, L, 0, cmat.ctypes.data,
                                              wmat.ctypes.data if lengths else None, assign.ctypes.data, C.byref(n)))
     mean = None
     if lengths:
@@ -142,60 +142,41 @@ def str_select_work_size(nlines: int) -> int:
     return int(b.value)
 
 
-def _work(work, nlines, ref):
-    import torch
-    need = str_select_work_size(nlines)
-    if work is None:
-        return torch.empty((need + 7) // 8, dtype=torch.int64, device=ref.device), need
-    if not (work.is_cuda and work.is_contiguous() and work.numel() * work.element_size() >= need and work.data_ptr() % 8 == 0):
-        raise ValueError("work must be an 8-byte aligned CUDA tensor of at least str_select_work_size(nlines) = %d bytes" % need)
-    return work, work.numel() * work.element_size()
-
-
-def _tensor(t, dtype, n, ref, what):
-    if not (t.is_cuda and t.device == ref.device and t.dtype == dtype and t.is_contiguous() and (n is None or t.numel() == n)):
-        raise ValueError("%s must be a contiguous %s CUDA tensor%s on the points' device" % (what, dtype, "" if n is None else " of %d elements" % n))
-    return t
+_WORK = "str_select_work_size(nlines)"
 
 
 def str_roi_pack_device(rois, out=None, stream=None):
     """fibd_str_roi_pack: rois uint8 (or bool) [nroi, nvox] -> roibits uint32 [nvox], bit r = (rois[r] != 0)"""
     import torch
-    from .dti import _stream_ptr
-    if rois.dtype == torch.bool:
-        rois = rois.view(torch.uint8)
-    if not (rois.is_cuda and rois.dtype == torch.uint8 and rois.is_contiguous() and rois.dim() == 2 and rois.shape[0] <= 32):
-        raise ValueError("rois must be a contiguous uint8 CUDA tensor [nroi <= 32, nvox]")
+    rois = tensor(rois, torch.uint8, "rois", shape=(None, None), bool_ok=True)
     nroi, nvox = int(rois.shape[0]), int(rois.shape[1])
-    with _on(rois, stream):
-        if out is None:
-            out = torch.empty(nvox, dtype=torch.uint32, device=rois.device)
-        else:
-            _tensor(out, torch.uint32, nvox, rois, "out")
-        _lib.check(_lib.lib().fibd_str_roi_pack(rois.data_ptr(), nroi, nvox, out.data_ptr(), _stream_ptr(stream)))
+    if nroi > 32:
+        raise ArgError("rois must be [nroi <= 32, nvox], not %d regions" % nroi)
+    with Launch(rois, stream) as L:
+        out = L.empty(nvox, torch.uint32) if out is None else tensor(out, torch.uint32, "out", ref=rois, n=nvox)
+        _lib.check(_lib.lib().fibd_str_roi_pack(rois.data_ptr(), nroi, nvox, out.data_ptr(), L.sp))
     return out
 
 
 def str_select_device(xyz, npts, shape, roibits=None, visit_all: int = 0, visit_none: int = 0, end_any: int = 0, end_both: int = 0,
                       min_npts: int = 0, max_npts: int = 0, hits: bool = True, work=None, stream=None):
     """fibd_str_select on device tensors: xyz float32 [npoints, 3], npts int32 [nlines], roibits uint32 [nx*ny*nz].  Returns (keep uint8
-    [nlines], hits uint32 [nlines, 3] or None, counts int64 [2] = kept lines, kept points) -- device tensors, the call does not wait.
-    An invalid `npts` gives keep = 0, counts = (-1, -1) and leaves hits unwritten."""
+    [nlines], hits uint32 [nlines, 3] or None, counts int64 [2] = kept lines, kept points) -- device tensors, the call does not wait
+    (`stream`, and `work` = None under a raw handle: _dev.Launch).  An invalid `npts` gives keep = 0, counts = (-1, -1) and leaves
+    hits unwritten."""
     import torch
-    from .dti import _stream_ptr
-    npnt, nl = _points(xyz), _counts(npts, xyz)
+    npnt, nl = _lines(xyz, npts)
     nx, ny, nz = (int(v) for v in shape)
     if roibits is not None:
-        _tensor(roibits, torch.uint32, nx * ny * nz, xyz, "roibits")
-    with _on(xyz, stream):
-        keep = torch.empty(nl, dtype=torch.uint8, device=xyz.device)
-        h = torch.empty((nl, 3), dtype=torch.uint32, device=xyz.device) if hits else None
-        counts = torch.empty(2, dtype=torch.int64, device=xyz.device)
-        work, wb = _work(work, nl, xyz)
+        tensor(roibits, torch.uint32, "roibits", ref=xyz, n=nx * ny * nz)
+    with Launch(xyz, stream) as L:
+        keep = L.empty(nl, torch.uint8)
+        h = L.empty((nl, 3), torch.uint32) if hits else None
+        counts = L.empty(2, torch.int64)
+        work, wb = _work(L, work, str_select_work_size, _WORK, nl)
         _lib.check(_lib.lib().fibd_str_select(xyz.data_ptr(), npts.data_ptr(), nl, npnt, nx, ny, nz, roibits.data_ptr() if roibits is not None else None,
                                               int(visit_all), int(visit_none), int(end_any), int(end_both), int(min_npts), int(max_npts),
-                                              keep.data_ptr(), h.data_ptr() if hits else None, counts.data_ptr(), work.data_ptr(), wb,
-                                              _stream_ptr(stream)))
+                                              keep.data_ptr(), h.data_ptr() if hits else None, counts.data_ptr(), work.data_ptr(), wb, L.sp))
     return keep, h, counts
 
 
@@ -206,39 +187,29 @@ def str_gather_device(xyz, npts, keep, scalars=None, cap_lines=None, cap_points=
     suffice; the first counts[0] lines and counts[1] points of the outputs are the result.  If a capacity is exceeded (status -1) or
     `npts` is invalid (counts -1, -1) nothing is written.  `out`: a dict of an earlier call whose tensors are written again."""
     import torch
-    from .dti import _stream_ptr
-    npnt, nl = _points(xyz), _counts(npts, xyz)
-    if keep.dtype == torch.bool:
-        keep = keep.view(torch.uint8)
-    _tensor(keep, torch.uint8, nl, xyz, "keep")
+    npnt, nl = _lines(xyz, npts)
+    keep = tensor(keep, torch.uint8, "keep", ref=xyz, n=nl, bool_ok=True)
     ns = 0
     if scalars is not None:
-        _tensor(scalars, torch.float32, None, xyz, "scalars")
-        ns = scalars.numel() // npnt if npnt else 0
-        if ns * npnt != scalars.numel() or ns == 0:
-            raise ValueError("scalars must be [npoints, n] with n >= 1")
-    with _on(xyz, stream):
+        ns = tensor(scalars, torch.float32, "scalars [npoints, n >= 1]", ref=xyz, unit=npnt).numel() // npnt
+    with Launch(xyz, stream) as L:
         if out is None:
             cl = nl if cap_lines is None else int(cap_lines)
             cp = npnt if cap_points is None else int(cap_points)
-            out = dict(xyz=torch.empty((cp, 3), dtype=torch.float32, device=xyz.device), npts=torch.empty(cl, dtype=torch.int32, device=xyz.device),
-                       index=torch.empty(cl, dtype=torch.int64, device=xyz.device) if index else None,
-                       scalars=torch.empty((cp, ns), dtype=torch.float32, device=xyz.device) if ns else None,
-                       counts=torch.empty(3, dtype=torch.int64, device=xyz.device))
-        cl, cp = out["npts"].numel(), out["xyz"].numel() // 3
-        _tensor(out["xyz"], torch.float32, None, xyz, "out xyz")
-        _tensor(out["npts"], torch.int32, None, xyz, "out npts")
-        _tensor(out["counts"], torch.int64, 3, xyz, "out counts")
+            out = dict(xyz=L.empty((cp, 3), torch.float32), npts=L.empty(cl, torch.int32), index=L.empty(cl, torch.int64) if index else None,
+                       scalars=L.empty((cp, ns), torch.float32) if ns else None, counts=L.empty(3, torch.int64))
+        cl = tensor(out["npts"], torch.int32, "out npts", ref=xyz).numel()
+        cp = _points(out["xyz"], "out xyz", xyz)
+        tensor(out["counts"], torch.int64, "out counts", ref=xyz, n=3)
         if out.get("index") is not None:
-            _tensor(out["index"], torch.int64, cl, xyz, "out index")
+            tensor(out["index"], torch.int64, "out index", ref=xyz, n=cl)
         if ns:
-            _tensor(out["scalars"], torch.float32, cp * ns, xyz, "out scalars")
-        work, wb = _work(work, nl, xyz)
+            tensor(out.get("scalars"), torch.float32, "out scalars", ref=xyz, n=cp * ns)
+        work, wb = _work(L, work, str_select_work_size, _WORK, nl)
         _lib.check(_lib.lib().fibd_str_gather(xyz.data_ptr(), npts.data_ptr(), nl, npnt, keep.data_ptr(), scalars.data_ptr() if ns else None, ns, cl, cp,
                                               out["xyz"].data_ptr(), out["npts"].data_ptr(),
                                               out["index"].data_ptr() if out.get("index") is not None else None,
-                                              out["scalars"].data_ptr() if ns else None, out["counts"].data_ptr(), work.data_ptr(), wb,
-                                              _stream_ptr(stream)))
+                                              out["scalars"].data_ptr() if ns else None, out["counts"].data_ptr(), work.data_ptr(), wb, L.sp))
     return out
 
 
@@ -248,33 +219,29 @@ def str_connectome_device(xyz, npts, shape, labels, nnodes: int, remap=None, vol
     [nlines, 2] (None with assign=False) and `n_lines` int64 [1] (-1 for an invalid `npts`, and then nothing was added).  `out`: the
     dict of an earlier call to accumulate into (tractograms that arrive in batches; the counts do not depend on the order)."""
     import torch
-    from .dti import _stream_ptr
-    npnt, nl = _points(xyz), _counts(npts, xyz)
+    npnt, nl = _lines(xyz, npts)
     nx, ny, nz = (int(v) for v in shape)
-    L = int(nnodes)
-    _tensor(labels, torch.int32, nx * ny * nz, xyz, "labels")
+    nn = int(nnodes)
+    tensor(labels, torch.int32, "labels", ref=xyz, n=nx * ny * nz)
     if remap is not None:
-        _tensor(remap, torch.int32, None, xyz, "remap")
-    res = None if volres is None else (C.c_float * 3)(*[float(v) for v in volres])
-    with _on(xyz, stream):
+        tensor(remap, torch.int32, "remap", ref=xyz)
+    res = None if volres is None else float3(volres)
+    with Launch(xyz, stream) as L:
         flags = 0
         if out is None:
-            out = dict(counts=torch.empty((L + 1, L + 1), dtype=torch.uint32, device=xyz.device),
-                       lengths=torch.empty((L + 1, L + 1), dtype=torch.float64, device=xyz.device) if volres is not None else None)
+            out = dict(counts=L.empty((nn + 1, nn + 1), torch.uint32), lengths=L.empty((nn + 1, nn + 1), torch.float64) if volres is not None else None)
         else:
             flags = _lib.FIB_CONNECTOME_ACCUMULATE
-            out = dict(counts=out["counts"], lengths=out.get("lengths"))
-            _tensor(out["counts"], torch.uint32, (L + 1) ** 2, xyz, "out counts")
+            out = dict(counts=tensor(out["counts"], torch.uint32, "out counts", ref=xyz, n=(nn + 1) ** 2), lengths=out.get("lengths"))
             if (out["lengths"] is None) != (volres is None):
                 raise ValueError("lengths are accumulated iff volres is given and the earlier call had them")
             if volres is not None:
-                _tensor(out["lengths"], torch.float64, (L + 1) ** 2, xyz, "out lengths")
-        out["assign"] = torch.empty((nl, 2), dtype=torch.int32, device=xyz.device) if assign else None
-        out["n_lines"] = torch.empty(1, dtype=torch.int64, device=xyz.device)
-        work, wb = _work(work, nl, xyz)
+                tensor(out["lengths"], torch.float64, "out lengths", ref=xyz, n=(nn + 1) ** 2)
+        out["assign"] = L.empty((nl, 2), torch.int32) if assign else None
+        out["n_lines"] = L.empty(1, torch.int64)
+        work, wb = _work(L, work, str_select_work_size, _WORK, nl)
         _lib.check(_lib.lib().fibd_str_connectome(xyz.data_ptr(), npts.data_ptr(), nl, npnt, nx, ny, nz, res, labels.data_ptr(),
-                                                  remap.data_ptr() if remap is not None else None, remap.numel() if remap is not None else 0, L, flags,
+                                                  remap.data_ptr() if remap is not None else None, remap.numel() if remap is not None else 0, nn, flags,
                                                   out["counts"].data_ptr(), out["lengths"].data_ptr() if volres is not None else None,
-                                                  out["assign"].data_ptr() if assign else None, out["n_lines"].data_ptr(), work.data_ptr(), wb,
-                                                  _stream_ptr(stream)))
+                                                  out["assign"].data_ptr() if assign else None, out["n_lines"].data_ptr(), work.data_ptr(), wb, L.sp))
     return out

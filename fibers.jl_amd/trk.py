@@ -14,8 +14,11 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _lib
+from ._dev import Launch, float3, sync
 from .mri import MRI
+from .stream import _device_params
 from .tract import Tract
+from .xform import _row_major
 
 _HDR = struct.Struct("<6s3h3f3fh200sh200s16f444s4s4s6f2s6B3i")      # 1000 bytes, trk.jl:13-35
 assert _HDR.size == 1000
@@ -188,35 +191,30 @@ def stream_to_trk(outfile, field, shape, seeds, sublist, ref: MRI, stream=None, 
     on its way out (fibd_stream_pack_trk_xfm) and the header carries the output space (outsize, outres, outvox2ras)."""
     import time
     import torch
-    from .stream import _params, default_workspace
-    from .dti import _stream_ptr, _sync
-    nvec = field.shape[1]
-    prm = _params(shape, nvec, kw.get("len_min", 3), kw.get("len_max"), kw.get("ang_thresh", 45),
-                  kw.get("step_size", 0.5), kw.get("smooth_coeff", 0.2), ws=default_workspace(field.device.index or 0),
-                  interp=kw.get("interp", "nearest"), integrator=kw.get("integrator", "euler"))
+    prm = _device_params(field, shape, seeds, sublist, "default", kw.get("len_min", 3), kw.get("len_max"), kw.get("ang_thresh", 45),
+                         kw.get("step_size", 0.5), kw.get("smooth_coeff", 0.2), kw.get("interp", "nearest"), integrator=kw.get("integrator", "euler"))
     job = C.c_void_p()
     nl, npnt = C.c_int64(0), C.c_int64(0)
-    L = _lib.lib()
-    sp = _stream_ptr(stream)
-    _lib.check(L.fibd_stream_trace(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(),
-                                   sublist.data_ptr(), sublist.shape[0], sp, C.byref(job), C.byref(nl), C.byref(npnt)))
-    try:
-        body = torch.empty(nl.value + 3 * npnt.value, dtype=torch.float32, device=field.device)
-        if xfm is None:
-            vs = (C.c_float * 3)(*[float(np.float32(v)) for v in ref.volres[:3]])
-            _lib.check(L.fibd_stream_pack_trk(job, C.byref(vs), body.data_ptr(), sp))
-        else:
-            from .xform import _row_major
-            vs = (C.c_float * 3)(*[float(v) for v in xfm.outres])
-            _lib.check(L.fibd_stream_pack_trk_xfm(job, _row_major(xfm), C.byref(vs), body.data_ptr(), sp))
-            ref = SimpleNamespace(volsize=tuple(int(v) for v in xfm.outsize), volres=tuple(float(v) for v in xfm.outres),
-                                  vox2ras=xfm.outvox2ras)
-        _sync(stream)                                   # the pack ran on `stream`: a copy only orders against the current one
-        if timings is not None:
-            timings["device_done"] = time.perf_counter()
-        _download_and_write(outfile, tract_header(ref, n_count=nl.value), body)
-    finally:
-        L.fib_stream_job_destroy(job)
+    lib = _lib.lib()
+    with Launch(field, stream) as L:
+        _lib.check(lib.fibd_stream_trace(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(),
+                                         sublist.data_ptr(), sublist.shape[0], L.sp, C.byref(job), C.byref(nl), C.byref(npnt)))
+        try:
+            body = L.empty(nl.value + 3 * npnt.value, torch.float32)
+            if xfm is None:
+                vs = float3(np.float32(v) for v in ref.volres[:3])
+                _lib.check(lib.fibd_stream_pack_trk(job, C.byref(vs), body.data_ptr(), L.sp))
+            else:
+                vs = float3(xfm.outres)
+                _lib.check(lib.fibd_stream_pack_trk_xfm(job, _row_major(xfm), C.byref(vs), body.data_ptr(), L.sp))
+                ref = SimpleNamespace(volsize=tuple(int(v) for v in xfm.outsize), volres=tuple(float(v) for v in xfm.outres),
+                                      vox2ras=xfm.outvox2ras)
+            sync(stream)                                    # the pack ran on `stream`: a copy only orders against the current one
+            if timings is not None:
+                timings["device_done"] = time.perf_counter()
+            _download_and_write(outfile, tract_header(ref, n_count=nl.value), body)
+        finally:
+            lib.fib_stream_job_destroy(job)
     if timings is not None:
         timings["file_done"] = time.perf_counter()
     return dict(nlines=nl.value, npoints=npnt.value)

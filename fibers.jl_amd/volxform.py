@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._dev import ArgError, Launch, tensor
 from .mri import MRI
 from .xform import Xform, _f32, _voxrot
 
@@ -103,24 +104,19 @@ def vol_xform_device(out2in, vol, inshape, outshape, interp: str = "trilinear", 
     volume [nframes, nxo*nyo*nzo] (or [nvox]) in the input's type; `out` may be given (a view at any 4-byte boundary is fine; it
     must not overlap vol).  The call does not wait for the kernel."""
     import torch
-    from .dti import _stream_ptr
-    from .tractmap import _on
     code = _interp(interp)
     nxi, nyi, nzi = (int(v) for v in inshape)
     nxo, nyo, nzo = (int(v) for v in outshape)
     nvi, nvo = nxi * nyi * nzi, nxo * nyo * nzo
-    if not (vol.is_cuda and vol.dtype in (torch.float32, torch.int32) and vol.is_contiguous() and nvi > 0 and vol.numel() >= nvi
-            and vol.numel() % nvi == 0):
-        raise ValueError("vol must be a contiguous float32 or int32 CUDA tensor [nframes, nxi*nyi*nzi]")
+    tensor(vol, (torch.float32, torch.int32), "vol [nframes, nxi*nyi*nzi]", unit=nvi)
     if vol.dtype != torch.float32 and code != _lib.VOL_INTERP["nearest"]:
-        raise ValueError("'trilinear' takes float32 volumes, not %s" % vol.dtype)
+        raise ArgError("'trilinear' takes float32 volumes, not %s" % vol.dtype)
     nf = vol.numel() // nvi
     bits = _bits(outside, np.float32 if vol.dtype == torch.float32 else np.int32)
-    with _on(vol, stream):
+    with Launch(vol, stream) as L:
         if out is None:
-            out = torch.empty((nf, nvo) if vol.dim() > 1 else (nvo,), dtype=vol.dtype, device=vol.device)
-        elif not (out.is_cuda and out.device == vol.device and out.dtype == vol.dtype and out.is_contiguous() and out.numel() == nf * nvo):
-            raise ValueError("out must be a contiguous CUDA tensor of the input's type and device with nframes * nxo*nyo*nzo elements")
-        _lib.check(_lib.lib().fibd_vol_xform(_row_major(out2in), vol.data_ptr(), nxi, nyi, nzi, nf, code, bits, out.data_ptr(), nxo, nyo, nzo,
-                                             _stream_ptr(stream)))
+            out = L.empty((nf, nvo) if vol.dim() > 1 else (nvo,), vol.dtype)
+        else:
+            tensor(out, vol.dtype, "out [nframes, nxo*nyo*nzo]", ref=vol, n=nf * nvo)
+        _lib.check(_lib.lib().fibd_vol_xform(_row_major(out2in), vol.data_ptr(), nxi, nyi, nzi, nf, code, bits, out.data_ptr(), nxo, nyo, nzo, L.sp))
     return out

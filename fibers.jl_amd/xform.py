@@ -6,13 +6,13 @@ inverses, products, the SVD behind `voxrot` -- are computed in float64 from the 
 reference does them in Float32 through LAPACK/BLAS, whose operation order is not reproduced).  The per-point apply,
 the hot path, is HIP (csrc/xform.hip): a NumPy array goes through the host-buffer entry fib_xfm_apply, a CUDA tensor through
 fibd_xfm_apply on the caller's stream.  Only the integer-output form of `xfm_apply!` (round, ties to even) is evaluated here."""
-import contextlib
 import ctypes as C
 from dataclasses import dataclass, field, replace
 
 import numpy as np
 
 from . import _lib
+from ._dev import ArgError, Launch, tensor
 from .mri import MRI
 from .tract import Tract
 
@@ -241,18 +241,11 @@ def xfm_apply(xfm: Xform, points, out=None, device=0, stream=None):
 
 def _apply_device(xfm, points, out, stream):
     import torch
-    from .dti import _stream_ptr
-    if not (points.dtype == torch.float32 and points.is_contiguous()):
-        raise ValueError("a contiguous float32 CUDA tensor expected")
-    if points.numel() % 3:
-        raise ValueError("points must be [N, 3] or a flat vector of 3N coordinates")
-    if out is None:                                  # (allocated on the launch stream: the allocator orders its reuse after the kernel)
-        with torch.cuda.device(points.device), (torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else contextlib.nullcontext()):
-            out = torch.empty_like(points)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == points.numel()):
-        raise ValueError("out must be a contiguous float32 CUDA tensor of the input's size")
-    with torch.cuda.device(points.device):
-        _lib.check(_lib.lib().fibd_xfm_apply(_row_major(xfm), points.data_ptr(), out.data_ptr(), points.numel() // 3, _stream_ptr(stream)))
+    if tensor(points, torch.float32, "points").numel() % 3:
+        raise ArgError("points must be [N, 3] or a flat vector of 3N coordinates")
+    with Launch(points, stream) as L:
+        out = L.empty(points.shape, torch.float32) if out is None else tensor(out, torch.float32, "out", ref=points, n=points.numel())
+        _lib.check(_lib.lib().fibd_xfm_apply(_row_major(xfm), points.data_ptr(), out.data_ptr(), points.numel() // 3, L.sp))
     return out
 
 
