@@ -166,6 +166,15 @@ _PROTOS = {
                          C.POINTER(TractOut)]),
     "fib_stream_lcm": (i32, [i32, C.POINTER(StreamParams), vp, vp, f32, vp, f32, vp, i32, vp, i32, vp, i32,
                              vp, f32, C.c_uint64, C.POINTER(TractOut)]),
+    "fib_prob_row_pitch": (i32, [i32]),
+    "fibd_prob_table": (i32, [vp, vp, i64, i32, i32, f32, vp, vp]),
+    "fib_prob_plan_create": (i32, [i32, vp, i32, f32, C.POINTER(vp)]),
+    "fib_prob_plan_destroy": (None, [vp]),
+    "fibd_prob_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
+    "fibd_prob_run": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, vp, i64, vp, i32, C.c_uint64, vp, vp, i64, vp, i64,
+                            C.POINTER(i64), C.POINTER(i64), vp, C.c_uint64, vp]),
+    "fib_prob_stream": (i32, [i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, i32, C.c_uint64,
+                              C.POINTER(TractOut)]),
     "fib_tract_free": (None, [C.POINTER(TractOut)]),
 }
 

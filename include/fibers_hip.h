@@ -603,6 +603,70 @@ int fibd_str_centroids(const float *lines, int64_t nlines, int K, const int32_t 
                        int flags, double *sums, uint32_t *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Probabilistic tracking: ODF-sampled streamlines (NOT in the reference)                */
+/* ------------------------------------------------------------------------------------ */
+/* Streamlines whose direction at every step is DRAWN from the ODF of the voxel ahead, restricted to a cone around the direction of
+ * travel.  These definitions are this project's own; they are the contract.  Wherever a sum is formed it is an integer sum, and every
+ * float32 operation is rounded on its own (no fused multiply-add): the output is BIT-IDENTICAL to a NumPy restatement.
+ *
+ * DIRECTIONS.  U[i], i < nvert: the first half of an ODF sphere's vertices (the vertices gqi_rec reports peaks on), float32 [nvert][3].
+ * 1 <= nvert <= 512, else FIB_ERR_UNSUPPORTED.
+ *
+ * WEIGHT TABLE, uint16 [nvox][pitch], pitch = fib_prob_row_pitch(nvert) = 64 * ceil(nvert / 64), padding zero, 16-byte aligned.  Built
+ * from an ODF float32 [nvert][nvox] planar (what fibd_odf_rec writes and MRI.vol[nx,ny,nz,nvert] is).  Per voxel, o_i its amplitudes:
+ *   m = the minimum of the o_i that are not NaN if subtract_min, else 0;   w_i = o_i - m if that is > 0, else 0 (a NaN fails the test);
+ *   wmax = max_i w_i.  If wmax is 0 or not finite, or the voxel's mask byte is 0 (mask uint8 [nvox] or NULL), the row is all zero.
+ *   Otherwise t_i = w_i / wmax (one IEEE float32 division), q_i = 0 where t_i < pmf_thresh, else (uint16) floorf(t_i * 65535.0f).
+ * The table carries the mask: a zero row ends a line.
+ *
+ * CONE.  c(j,i) = (U[j].x*U[i].x + U[j].y*U[i].y) + U[j].z*U[i].z, every product and sum rounded to float32 on its own.
+ *   allow(j,i) = |c(j,i)| >= cosang_thresh,   same(j,i) = c(j,i) > 0.   cosang_thresh must be > 0 (an angle below 90 degrees), else
+ *   FIB_ERR_INVALID: the cone is the only bend limit.
+ *
+ * RANDOM NUMBERS.  The generator of fibd_stream_trace_lcm, h(line, k) = splitmix64(rng_seed ^ splitmix64(line * 0xD1342543DE82EF95 + k)),
+ * here its top 32 bits: u = h >> 32.  A draw from weights q with Q = sum q_i > 0 is r = (u * Q) >> 32 in 64-bit integers, and the pick
+ * is the first i whose running integer sum exceeds r.  Q < 2^25: nothing overflows, and a unit of weight owns at least 128 values of u.
+ * Known answers for h >> 32: (rng_seed 0, line 0, k 0) 2802244911; (1234, 5, 2) 1460108722; (2^63 + 1, 10^6, 141) 2790284181.
+ *
+ * A LINE.  line = i * nsub + sub for the i-th seed of the list (seeds: 0-based column-major voxel indices; one outside the volume has no
+ * points); k counts the line's draws from 0.  pos0 = the seed voxel (1-based, as float32) + sublist[sub].  If the seed voxel's row has
+ * Q = 0 the line has no points.  Otherwise j0 is drawn from the whole row (no cone), and then for s0 in (+1, -1), each pass starting from
+ * pos = pos0, j = j0, s = s0:
+ *   1. vec = s * U[j] (exact); nxt = pos + vec * step_size: multiply, then add, each rounded.
+ *   2. vox = rint(nxt), ties to even.  nxt not finite or vox outside 1..n: the pass ends.
+ *   3. q'_i = allow(j,i) ? table[vox][i] : 0.  Q' = sum q'_i = 0: the pass ends and NO DRAW IS CONSUMED.
+ *   4. i* is drawn from q'; s = same(j,i*) ? s : -s; j = i*.
+ *   5. pos is emitted and npts incremented; npts > len_max: the pass ends; otherwise pos = nxt.
+ * (the shape of stream.jl:625-690: a point is saved only if its successor step is valid, the seed is emitted once per direction, npts is
+ * shared by both directions.)  Output order [fwd_N .. fwd_1, bwd_1 .. bwd_M], at most len_max + 2 points; a line is kept iff
+ * npts >= len_min.  No smoothing and no separate bend test: a direction is always a vertex and the cone is the bend limit.
+ * Results depend on the arguments and rng_seed only -- not on scheduling, the launch shape or how often the call is made. */
+typedef struct fib_prob_plan fib_prob_plan;
+/* the row pitch of the weight table in elements; 0 for an unsupported nvert */
+int fib_prob_row_pitch(int nvert);
+/* odf, mask (or NULL) and table are device pointers; asynchronous on `stream`, no allocation and no synchronisation inside.  A transpose
+ * through LDS: 4 * nvert bytes read and 2 * pitch written per voxel. */
+int fibd_prob_table(const float *odf, const uint8_t *mask, int64_t nvox, int nvert, int subtract_min, float pmf_thresh, uint16_t *table,
+                    void *stream);
+/* the plan holds U and the bit rows of allow and same (nvert x pitch bits each) on `device`; vertices is host memory [nvert][3] */
+int fib_prob_plan_create(int device, const float *vertices, int nvert, float cosang_thresh, fib_prob_plan **plan);
+void fib_prob_plan_destroy(fib_prob_plan *plan);
+/* bytes of device scratch fibd_prob_run needs for nlines = nseed * nsub lines (24 per line and the scan's block totals); 8-byte aligned.
+ * After a call, also one that returned FIB_ERR_CAPACITY, work begins with int32 [nlines][2] = {nfwd, nbwd} of EVERY line in (seed, sub)
+ * order, those dropped by len_min included (their sum is the line's npts). */
+int fibd_prob_work_size(int64_t nlines, size_t *bytes);
+/* Trace and pack into caller-provided device buffers, the layout of fibd_stream_run: npts int32 [lines_cap], seed_index int64
+ * [lines_cap] (= seed * nsub + sub), xyz float32 [3 * points_cap], kept lines in (seed, sub) order, one after the other.  No row of
+ * len_max + 2 points is reserved per line: a first pass traces and counts, a scan applies len_min and places every kept line, a second
+ * pass replays the kept lines (the generator is counter-based) and stores every point at its final place.  *nlines / *npoints receive the
+ * totals (host); when they exceed the capacities the call returns FIB_ERR_CAPACITY after the first pass and has written NOTHING to the
+ * three buffers.  plan's device must be current; table, seeds, sublist and work are device pointers; synchronises `stream`. */
+int fibd_prob_run(const fib_prob_plan *plan, int nx, int ny, int nz, int32_t len_min, int32_t len_max, float step_size, const uint16_t *table,
+                  const int64_t *seeds, int64_t nseed, const float *sublist, int32_t nsub, uint64_t rng_seed, int32_t *npts,
+                  int64_t *seed_index, int64_t lines_cap, float *xyz, int64_t points_cap, int64_t *nlines, int64_t *npoints, void *work,
+                  size_t work_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Volume resampling: a volume moved through an Xform (NOT in the reference)             */
 /* ------------------------------------------------------------------------------------ */
 /* Volumes are planar [nframes][nz][ny][nx], x fastest (MRI.vol in Fortran order), 32-bit elements.  Voxel coordinates are 0-BASED
@@ -793,6 +857,14 @@ int fib_stream_lcm(int device, const fib_stream_params *prm, const float *const 
                    float f_thresh, const float *fa, float fa_thresh, const void *mask, int mask_dtype,
                    const void *seed, int seed_dtype, const float *sublist, int32_t nsub,
                    const float *lcms, float lcm_thresh, uint64_t rng_seed, fib_tract_out *out);
+/* prob_stream: the host-buffer form of the "Probabilistic tracking" section.  odf [nx,ny,nz,nvert] column-major (planar [nvert][nvox]),
+ * vertices [nvert][3]; mask and seed uint8 [nvox] (non-zero = inside) or NULL (mask NULL: no mask; seed NULL: the mask's voxels, or all).
+ * The weight table is built from voxel chunks of the host ODF, so the float ODF is never whole on the device (the table, 2 * pitch bytes
+ * per voxel, is).  Fills a library-allocated fib_tract_out like fib_stream (release with fib_tract_free); flags stays NULL.  The same
+ * bytes as fibd_prob_table + fibd_prob_run.  One device: FIB_DEVICE_ALL is FIB_ERR_UNSUPPORTED. */
+int fib_prob_stream(int device, int nx, int ny, int nz, const float *odf, int nvert, const float *vertices, const uint8_t *mask,
+                    const uint8_t *seed, const float *sublist, int32_t nsub, int32_t len_min, int32_t len_max, float cosang_thresh,
+                    float step_size, float pmf_thresh, int32_t subtract_min, uint64_t rng_seed, fib_tract_out *out);
 void fib_tract_free(fib_tract_out *out);
 
 #ifdef __cplusplus

@@ -604,3 +604,73 @@ fibd_str_connectome(xyz::Ptr{Cvoid}, npts::Ptr{Cvoid}, nlines::Integer, npoints:
        Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt64, Ptr{Cvoid}),
       xyz, npts, nlines, npoints, dims[1], dims[2], dims[3], volres, labels, remap, nremap, nnodes, flags, cmat, wmat, assign, n_lines, work,
       work_bytes, stream))
+
+# ---- probabilistic tracking (NOT in the reference; "Probabilistic tracking" in include/fibers_hip.h) -----------------------------
+"""prob_stream(odf, odf_dirs; mask, seed, nsub, len_min, len_max, ang_thresh, step_size, pmf_thresh, subtract_min, rng_seed) -> Tract —
+probabilistic tractography from an ODF volume [nx,ny,nz,nvert] (e.g. `gqi_rec(...).odf`): at every step the direction is drawn from the
+ODF of the voxel ahead inside a cone of `ang_thresh` degrees (below 90) around the direction of travel.  Seeds, `nsub` and the line
+layout follow `stream`; the draws come from the library's counter-based generator (`rng_seed`), the sub-voxel offsets from Julia's RNG."""
+function prob_stream(odf::MRI, odf_dirs::ODF=sphere_642; mask::Union{MRI,Nothing}=nothing, seed::Union{MRI,Nothing}=nothing,
+                     nsub::Integer=3, len_min::Integer=3, len_max::Integer=maximum(odf.volsize), ang_thresh::Real=45,
+                     step_size::Real=.5, pmf_thresh::Real=.1, subtract_min::Bool=true, rng_seed::Integer=rand(UInt64),
+                     device::Integer=0)
+  vol = odf.vol::Array{Float32,4}
+  nx, ny, nz, nvert = size(vol)
+  nvert == size(odf_dirs.vertices, 1) ÷ 2 || error("odf must have one frame per direction of the half sphere")
+  U = Matrix{Float32}(permutedims(odf_dirs.vertices[1:nvert, :]))            # [3 x nvert] = [nvert][3] on the C side
+  m8 = isnothing(mask) ? UInt8[] : UInt8.(view(mask.vol, :, :, :, 1) .> 0)
+  s8 = isnothing(seed) ? UInt8[] : UInt8.(view(seed.vol, :, :, :, 1) .> 0)
+  sublist = nsub > 0 ? hcat([Float32.(rand(Uniform(-.5+eps(), .5-eps()), 3)) for _ in 1:nsub]...) : zeros(Float32, 3, 1)
+  out = FibTractOut()
+  GC.@preserve vol U m8 s8 sublist fib_check(ccall((:fib_prob_stream, libfibers), Cint,
+      (Cint, Cint, Cint, Cint, Ptr{Float32}, Cint, Ptr{Float32}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float32}, Int32, Int32, Int32, Cfloat, Cfloat,
+       Cfloat, Int32, UInt64, Ref{FibTractOut}),
+      device, nx, ny, nz, vol, nvert, U, isnothing(mask) ? Ptr{UInt8}(C_NULL) : pointer(m8), isnothing(seed) ? Ptr{UInt8}(C_NULL) : pointer(s8),
+      sublist, size(sublist, 2), len_min, len_max, cosd(Float32(ang_thresh)), Float32(step_size), Float32(pmf_thresh), Int32(subtract_min),
+      UInt64(rng_seed), out))
+  npts = unsafe_wrap(Array, out.npts, out.nlines)
+  xyz  = unsafe_wrap(Array, out.xyz, (3, Int(out.npoints)))
+  off  = cumsum(vcat(0, Int.(npts)))
+  str  = [xyz[:, off[i]+1:off[i+1]] for i in 1:length(npts)]
+  ccall((:fib_tract_free, libfibers), Cvoid, (Ref{FibTractOut},), out)
+  tr = Tract{Float32}(isnothing(mask) ? odf : mask)
+  str_add!(tr, str)
+  return tr
+end
+
+# device tier
+fib_prob_row_pitch(nvert::Integer) = Int(ccall((:fib_prob_row_pitch, libfibers), Cint, (Cint,), nvert))
+
+fibd_prob_table(odf::Ptr{Cvoid}, mask::Ptr{Cvoid}, nvox::Integer, nvert::Integer, subtract_min::Bool, pmf_thresh::Real, table::Ptr{Cvoid},
+                stream::Ptr{Cvoid}=C_NULL) =
+  fib_check(ccall((:fibd_prob_table, libfibers), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Cint, Cfloat, Ptr{Cvoid}, Ptr{Cvoid}),
+      odf, mask, nvox, nvert, Int32(subtract_min), Float32(pmf_thresh), table, stream))
+
+function fib_prob_plan_create(device::Integer, U::Matrix{Float32}, cosang_thresh::Real)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve U fib_check(ccall((:fib_prob_plan_create, libfibers), Cint, (Cint, Ptr{Float32}, Cint, Cfloat, Ref{Ptr{Cvoid}}),
+      device, U, size(U, 2), Float32(cosang_thresh), h))
+  return h[]
+end
+fib_prob_plan_destroy(plan::Ptr{Cvoid}) = ccall((:fib_prob_plan_destroy, libfibers), Cvoid, (Ptr{Cvoid},), plan)
+
+function fibd_prob_work_size(nlines::Integer)
+  b = Ref{UInt64}(0)
+  fib_check(ccall((:fibd_prob_work_size, libfibers), Cint, (Int64, Ref{UInt64}), nlines, b))
+  return Int(b[])
+end
+
+"fibd_prob_run on device pointers -> (status, nlines, npoints); status FIB_ERR_CAPACITY (-9): the counts say what the buffers must hold"
+function fibd_prob_run(plan::Ptr{Cvoid}, dims, len_min::Integer, len_max::Integer, step_size::Real, table::Ptr{Cvoid}, seeds::Ptr{Cvoid},
+                       nseed::Integer, sublist::Ptr{Cvoid}, nsub::Integer, rng_seed::Integer, npts::Ptr{Cvoid}, seed_index::Ptr{Cvoid},
+                       lines_cap::Integer, xyz::Ptr{Cvoid}, points_cap::Integer, work::Ptr{Cvoid}, work_bytes::Integer,
+                       stream::Ptr{Cvoid}=C_NULL)
+  nl, np = Ref{Int64}(0), Ref{Int64}(0)
+  rc = ccall((:fibd_prob_run, libfibers), Cint,
+      (Ptr{Cvoid}, Cint, Cint, Cint, Int32, Int32, Cfloat, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int32, UInt64, Ptr{Cvoid}, Ptr{Cvoid},
+       Int64, Ptr{Cvoid}, Int64, Ref{Int64}, Ref{Int64}, Ptr{Cvoid}, UInt64, Ptr{Cvoid}),
+      plan, dims[1], dims[2], dims[3], len_min, len_max, Float32(step_size), table, seeds, nseed, sublist, nsub, UInt64(rng_seed), npts,
+      seed_index, lines_cap, xyz, points_cap, nl, np, work, work_bytes, stream)
+  rc == 0 || rc == -9 || fib_check(rc)
+  return rc, nl[], np[]
+end
