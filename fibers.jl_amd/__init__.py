@@ -31,3 +31,6 @@ from .volxform import mri_xform, vol_xform_device, vol_xform_matrix, xfm_header 
 # (the device tier of prob_stream is reached through the module: probtrack.prob_table_device, probtrack.prob_stream_device)
 from . import probtrack  # noqa: F401
 from .probtrack import ProbPlan, prob_row_pitch, prob_stream, prob_work_size  # noqa: F401
+# (the device tier of the warps likewise: warp.warp_pack_device, warp.warp_points_device, warp.warp_volume_device, warp.warp_invert_device)
+from . import warp  # noqa: F401
+from .warp import Warp, mri_warp, str_warp, warp_invert, warp_read, warp_write  # noqa: F401

@@ -61,6 +61,7 @@ class TractOut(C.Structure):
 _lib = None
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
 P3 = C.c_void_p * 3
+M16 = C.POINTER(C.c_float * 16)     # a row-major float[16] matrix
 
 _PROTOS = {
     "fib_last_error": (C.c_char_p, []),
@@ -115,6 +116,13 @@ _PROTOS = {
     "fib_xfm_apply": (i32, [i32, C.POINTER(C.c_float * 16), vp, vp, i64]),
     "fibd_vol_xform": (i32, [C.POINTER(C.c_float * 16), vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp]),
     "fib_vol_xform": (i32, [i32, C.POINTER(C.c_float * 16), vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32]),
+    "fibd_warp_pack": (i32, [vp, i32, i32, i32, vp, vp]),
+    "fibd_warp_points": (i32, [vp, i32, i32, i32, M16, M16, M16, vp, vp, i64, vp]),
+    "fibd_warp_volume": (i32, [vp, i32, i32, i32, M16, M16, M16, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp]),
+    "fibd_warp_invert": (i32, [vp, i32, i32, i32, M16, M16, i32, vp, vp, i32, i32, i32, vp]),
+    "fib_warp_points": (i32, [i32, vp, i32, i32, i32, M16, M16, M16, vp, vp, i64]),
+    "fib_warp_volume": (i32, [i32, vp, i32, i32, i32, M16, M16, M16, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32]),
+    "fib_warp_invert": (i32, [i32, vp, i32, i32, i32, M16, M16, i32, vp, vp, i32, i32, i32]),
     "fibd_str_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
     "fibd_str_density": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, C.c_uint64, vp]),
     "fibd_str_sample": (i32, [vp, i64, vp, i32, i32, i32, i32, f32, vp, vp]),

@@ -671,6 +671,109 @@ extern "C" int fib_vol_xform(int device, const float out2in[16], const void *vol
 } FIB_API_CATCH
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// non-linear warps: host forms.  One device; the planar field is uploaded and packed once and stays resident for the call, the points
+// or the frames travel in chunks.  Copies block on the NULL stream, so a read-back comes behind its kernel.  The buffers are local.
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+// the field of a host call on the current device: upload, pack, and the planar copy goes back to the driver
+int warp_field_upload(const float *disp, int nx, int ny, int nz, fib::DevBuf<float> &packed) {
+    FIB_CHECK(disp, FIB_ERR_INVALID, "NULL field");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "the field's dimensions must be positive");
+    const size_t nvox = (size_t)nx * ny * nz;
+    fib::DevBuf<float> planar;
+    RC(planar.alloc(3 * nvox));
+    RC(packed.alloc(4 * nvox));
+    RC(h2d(planar.p, disp, sizeof(float) * 3 * nvox));
+    RC(fibd_warp_pack(planar.p, nx, ny, nz, packed.p, nullptr));
+    FIB_HIP(hipDeviceSynchronize());
+    return FIB_OK;
+}
+}  // namespace
+
+extern "C" int fib_warp_points(int device, const float *disp, int nx, int ny, int nz, const float to_ras[16], const float to_field[16],
+                               const float from_ras[16], const float *xyz, float *out, int64_t npoints) try {
+    FIB_CHECK(disp && to_ras && to_field && from_ras, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "the field's dimensions must be positive");
+    FIB_CHECK(npoints >= 0, FIB_ERR_INVALID, "npoints must not be negative");
+    FIB_CHECK(npoints == 0 || (xyz && out), FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(xyz == out || xyz + 3 * npoints <= out || out + 3 * npoints <= xyz, FIB_ERR_INVALID, "xyz and out must be the same array or not overlap");
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "warp_points runs on one device (FIB_DEVICE_ALL is not supported)");
+    fib::DeviceGuard guard;
+    RC(fib::use_device(device));
+    if (npoints == 0) return FIB_OK;
+    int64_t chunk = (int64_t)1 << 22;                       // 48 MB of points per chunk
+    if (const char *e = fib::env("FIBERS_WARP_POINTS")) { const long long v = atoll(e); if (v > 0) chunk = v; }
+    fib::DevBuf<float> d_field, d_xyz;
+    RC(warp_field_upload(disp, nx, ny, nz, d_field));
+    RC(d_xyz.alloc((size_t)3 * std::min(chunk, npoints)));
+    for (int64_t p0 = 0; p0 < npoints; p0 += chunk) {
+        const int64_t np = std::min(chunk, npoints - p0);
+        RC(h2d(d_xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(fibd_warp_points(d_field.p, nx, ny, nz, to_ras, to_field, from_ras, d_xyz.p, d_xyz.p, np, nullptr));
+        RC(d2h(out + 3 * p0, d_xyz.p, sizeof(float) * 3 * (size_t)np));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_warp_volume(int device, const float *disp, int nx, int ny, int nz, const float to_ras[16], const float to_field[16],
+                               const float from_ras[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp, int32_t outside_bits,
+                               void *out, int nxo, int nyo, int nzo) try {
+    FIB_CHECK(disp && to_ras && to_field && from_ras && vol && out, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "the field's dimensions must be positive");
+    FIB_CHECK(nxi > 0 && nyi > 0 && nzi > 0 && nxo > 0 && nyo > 0 && nzo > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
+    FIB_CHECK(interp == FIB_VOL_NEAREST || interp == FIB_VOL_TRILINEAR, FIB_ERR_INVALID, "unknown interpolation %d", interp);
+    const size_t nvi = (size_t)nxi * nyi * nzi, nvo = (size_t)nxo * nyo * nzo, nvf = (size_t)nx * ny * nz;
+    const uintptr_t ai = reinterpret_cast<uintptr_t>(vol), ao = reinterpret_cast<uintptr_t>(out);
+    FIB_CHECK(ai + 4 * nvi * nframes <= ao || ao + 4 * nvo * nframes <= ai, FIB_ERR_INVALID, "vol and out must not overlap");
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "warp_volume runs on one device (FIB_DEVICE_ALL is not supported)");
+    fib::DeviceGuard guard;
+    RC(fib::use_device(device));
+    fib::DevBuf<float> d_field;
+    RC(warp_field_upload(disp, nx, ny, nz, d_field));
+    int nfc = 0;
+    if (const char *e = fib::env("FIBERS_WARP_FRAMES")) nfc = atoi(e);
+    if (nfc <= 0) {                     // half the free memory (the field is resident already): 4 (in) + 4 (out) bytes per voxel of a frame pair
+        size_t fr = 0, tot = 0;
+        FIB_HIP(hipMemGetInfo(&fr, &tot));
+        const size_t fit = (fr / 2) / (4 * (nvi + nvo));
+        FIB_CHECK(fit >= 1, FIB_ERR_NOMEM, "warp_volume: the field (%zu voxels), one input and one output frame do not fit in device memory", nvf);
+        nfc = (int)std::min<size_t>(fit, (size_t)nframes);
+    }
+    if (nfc > nframes) nfc = nframes;
+    fib::DevBuf<uint32_t> d_in, d_out;
+    RC(d_in.alloc(nvi * nfc));
+    RC(d_out.alloc(nvo * nfc));
+    const uint32_t *src = static_cast<const uint32_t *>(vol);
+    uint32_t *dst = static_cast<uint32_t *>(out);
+    for (int f0 = 0; f0 < nframes; f0 += nfc) {
+        const int nf = std::min(nfc, nframes - f0);
+        RC(h2d(d_in.p, src + nvi * f0, sizeof(uint32_t) * nvi * nf));
+        RC(fibd_warp_volume(d_field.p, nx, ny, nz, to_ras, to_field, from_ras, d_in.p, nxi, nyi, nzi, nf, interp, outside_bits, d_out.p, nxo, nyo,
+                            nzo, nullptr));
+        RC(d2h(dst + nvo * f0, d_out.p, sizeof(uint32_t) * nvo * nf));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_warp_invert(int device, const float *disp, int nx, int ny, int nz, const float out_to_ras[16], const float ras_to_field[16],
+                               int niter, float *inv, float *err, int nxo, int nyo, int nzo) try {
+    FIB_CHECK(disp && out_to_ras && ras_to_field && inv, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0 && nxo > 0 && nyo > 0 && nzo > 0, FIB_ERR_INVALID, "the field's and the output's dimensions must be positive");
+    FIB_CHECK(niter >= 0, FIB_ERR_INVALID, "niter must not be negative");
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "warp_invert runs on one device (FIB_DEVICE_ALL is not supported)");
+    fib::DeviceGuard guard;
+    RC(fib::use_device(device));
+    const size_t nvo = (size_t)nxo * nyo * nzo;
+    fib::DevBuf<float> d_field, d_out;
+    RC(warp_field_upload(disp, nx, ny, nz, d_field));
+    RC(d_out.alloc(4 * nvo));
+    RC(fibd_warp_invert(d_field.p, nx, ny, nz, out_to_ras, ras_to_field, niter, d_out.p, err ? d_out.p + 3 * nvo : nullptr, nxo, nyo, nzo, nullptr));
+    RC(d2h(inv, d_out.p, sizeof(float) * 3 * nvo));
+    if (err) RC(d2h(err, d_out.p + 3 * nvo, sizeof(float) * nvo));
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // tract maps: host forms.  One device; the points travel in chunks cut at line boundaries, the volume stays on the device.
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {

@@ -1,0 +1,246 @@
+// warp.hip — non-linear warps on gfx950: a displacement field (mm, RAS) on a grid of its own applied to points (fibd_warp_points) and
+// to volumes (fibd_warp_volume), and inverted by fixed-point iteration (fibd_warp_invert).  Not in the reference: the definitions are
+// the "Non-linear warps" section of include/fibers_hip.h.  The non-linear sibling of xform.hip and volxform.hip: the matrices are
+// applied by xfm_point (xfm_apply.inc) and a warped volume is sampled by vx_sample (vol_sample.inc).
+//
+// The field's device form is float4 [nvox] = (dx, dy, dz, 0), made once by fibd_warp_pack (the tracer's precedent, stream.hip): the
+// sample S(q) is 8 aligned 16-byte gathers instead of 24 scalar ones.  All three users are gather kernels with one thread per point or
+// output voxel; the field is the large operand (182 x 218 x 182 packed: 115 MB) and lives in L2 / the Infinity Cache, so what bounds them
+// is the gather rate, not arithmetic (profiles/warp/README.md).  Offsets are 64-bit; points and volumes may start at any 4-byte
+// boundary (single-word loads and stores), the packed field at any 16-byte boundary.
+#include "common.h"
+
+#include <algorithm>
+
+// the matrices, the sample and the iteration are sequences of separately rounded float32 operations: nothing in this file may fuse a*b+c
+#pragma clang fp contract(off)
+
+namespace {
+
+#include "xfm_apply.inc"
+#include "vol_sample.inc"
+
+constexpr int WP_MAX_DIM = 1 << 24;                            // every size is exact in float32 (the clamp compares floats)
+constexpr int WP_BLOCK = 256;
+
+struct WarpField { const float4 *f; int nx, ny, nz; };
+
+// one component of q: the clamp (the edge displacement continues beyond the grid: +-Inf clamp, -0.0 passes), then floor and fraction
+__device__ __forceinline__ void wp_axis(float q, int n, int &i0, int &i1, float &f, float &g) {
+    const float hi = (float)(n - 1);
+    const float qc = q < 0.f ? 0.f : (q > hi ? hi : q);
+    const float fl = floorf(qc);
+    i0 = (int)fl;
+    f = qc - fl;
+    g = 1.f - f;
+    i1 = min(i0 + 1, n - 1);
+}
+
+__device__ __forceinline__ float wp_lerp3(float gx, float fx, float gy, float fy, float gz, float fz, float v000, float v100, float v010, float v110,
+                                          float v001, float v101, float v011, float v111) {
+    const float c00 = gx * v000 + fx * v100, c10 = gx * v010 + fx * v110;
+    const float c01 = gx * v001 + fx * v101, c11 = gx * v011 + fx * v111;
+    const float c0 = gy * c00 + fy * c10;
+    const float c1 = gy * c01 + fy * c11;
+    return gz * c0 + fz * c1;
+}
+
+// S(q): q in field-voxel coordinates (0-based).  A NaN in any component gives three NaNs (nothing is converted to an integer then).
+__device__ __forceinline__ float3 wp_sample(const WarpField &W, const float3 q) {
+    if (q.x != q.x || q.y != q.y || q.z != q.z) {
+        const float n = __builtin_nanf("");
+        return make_float3(n, n, n);
+    }
+    int x0, x1, y0, y1, z0, z1;
+    float fx, gx, fy, gy, fz, gz;
+    wp_axis(q.x, W.nx, x0, x1, fx, gx);
+    wp_axis(q.y, W.ny, y0, y1, fy, gy);
+    wp_axis(q.z, W.nz, z0, z1, fz, gz);
+    const int64_t r0 = (int64_t)W.nx * y0, r1 = (int64_t)W.nx * y1;
+    const int64_t s0 = (int64_t)W.nx * W.ny * z0, s1 = (int64_t)W.nx * W.ny * z1;
+    const float4 v000 = W.f[x0 + r0 + s0], v100 = W.f[x1 + r0 + s0], v010 = W.f[x0 + r1 + s0], v110 = W.f[x1 + r1 + s0];
+    const float4 v001 = W.f[x0 + r0 + s1], v101 = W.f[x1 + r0 + s1], v011 = W.f[x0 + r1 + s1], v111 = W.f[x1 + r1 + s1];
+    return make_float3(wp_lerp3(gx, fx, gy, fy, gz, fz, v000.x, v100.x, v010.x, v110.x, v001.x, v101.x, v011.x, v111.x),
+                       wp_lerp3(gx, fx, gy, fy, gz, fz, v000.y, v100.y, v010.y, v110.y, v001.y, v101.y, v011.y, v111.y),
+                       wp_lerp3(gx, fx, gy, fy, gz, fz, v000.z, v100.z, v010.z, v110.z, v001.z, v101.z, v011.z, v111.z));
+}
+
+// the warp of a point of caller coordinates: to RAS and to field voxels, the sample, the sum, back to caller coordinates
+__device__ __forceinline__ float3 wp_point(const WarpField &W, const XfmMat &to_ras, const XfmMat &to_field, const XfmMat &from_ras, float px,
+                                           float py, float pz) {
+    const float3 x = xfm_point(to_ras, px, py, pz);
+    const float3 d = wp_sample(W, xfm_point(to_field, px, py, pz));
+    return xfm_point(from_ras, x.x + d.x, x.y + d.y, x.z + d.z);
+}
+
+__global__ __launch_bounds__(WP_BLOCK) void wp_pack_kernel(const float *__restrict__ disp, int64_t nvox, float4 *__restrict__ packed) {
+    const int64_t v = (int64_t)blockIdx.x * WP_BLOCK + threadIdx.x;
+    if (v < nvox) packed[v] = make_float4(disp[v], disp[nvox + v], disp[2 * nvox + v], 0.f);
+}
+
+// (no __restrict__ on the points: out may be xyz itself; a thread reads its point before it writes it)
+__global__ __launch_bounds__(WP_BLOCK) void wp_points_kernel(const WarpField W, const XfmMat to_ras, const XfmMat to_field, const XfmMat from_ras,
+                                                             const float *xyz, float *out, int64_t npoints) {
+    const int64_t p = (int64_t)blockIdx.x * WP_BLOCK + threadIdx.x;
+    if (p >= npoints) return;
+    const float3 r = wp_point(W, to_ras, to_field, from_ras, xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2]);
+    out[3 * p] = r.x; out[3 * p + 1] = r.y; out[3 * p + 2] = r.z;
+}
+
+// the tile of vx_kernel<64, 4, .> (volxform.hip): four neighbouring x-row segments, a wave each
+template <int BX, int BY, int UNROLL>
+__global__ __launch_bounds__(BX * BY) void wp_volume_kernel(const WarpField W, const XfmMat to_ras, const XfmMat to_field, const XfmMat from_ras,
+                                                            const uint32_t *__restrict__ vol, int nxi, int nyi, int nzi, int nframes, int interp,
+                                                            uint32_t fill, uint32_t *__restrict__ out, int nxo, int nyo, int nzo, unsigned nsx,
+                                                            unsigned nsy) {
+    const unsigned b = blockIdx.x, bx = b % nsx, r = b / nsx, by = r % nsy, k = r / nsy;
+    const int i = (int)(bx * BX) + (int)(threadIdx.x % BX), j = (int)(by * BY) + (int)(threadIdx.x / BX);
+    if (i >= nxo || j >= nyo) return;
+    const int64_t nvo = (int64_t)nxo * nyo * nzo;
+    uint32_t *dst = out + ((int64_t)i + (int64_t)nxo * ((int64_t)j + (int64_t)nyo * k));
+    vx_sample<UNROLL>(wp_point(W, to_ras, to_field, from_ras, (float)i, (float)j, (float)k), vol, nxi, nyi, nzi, nframes, interp, fill, dst, nvo);
+}
+
+__device__ __forceinline__ bool wp_same_bits(const float3 a, const float3 b) {
+    return __float_as_uint(a.x) == __float_as_uint(b.x) && __float_as_uint(a.y) == __float_as_uint(b.y) && __float_as_uint(a.z) == __float_as_uint(b.z);
+}
+
+// x <- y - S(x), niter times from x = y.  The loop is left when an iterate repeats bit for bit: every later one is the same.
+template <int BX, int BY>
+__global__ __launch_bounds__(BX * BY) void wp_invert_kernel(const WarpField W, const XfmMat out_to_ras, const XfmMat ras_to_field, int niter,
+                                                            float *__restrict__ inv, float *__restrict__ err, int nxo, int nyo, int nzo, unsigned nsx,
+                                                            unsigned nsy) {
+    const unsigned b = blockIdx.x, bx = b % nsx, r = b / nsx, by = r % nsy, k = r / nsy;
+    const int i = (int)(bx * BX) + (int)(threadIdx.x % BX), j = (int)(by * BY) + (int)(threadIdx.x / BX);
+    if (i >= nxo || j >= nyo) return;
+    const int64_t nvo = (int64_t)nxo * nyo * nzo, o = (int64_t)i + (int64_t)nxo * ((int64_t)j + (int64_t)nyo * k);
+    const float3 y = xfm_point(out_to_ras, (float)i, (float)j, (float)k);
+    float3 x = y;
+    for (int it = 0; it < niter; it++) {
+        const float3 d = wp_sample(W, xfm_point(ras_to_field, x.x, x.y, x.z));
+        const float3 xn = make_float3(y.x - d.x, y.y - d.y, y.z - d.z);
+        const bool same = wp_same_bits(xn, x);
+        x = xn;
+        if (same) break;
+    }
+    inv[o] = x.x - y.x; inv[nvo + o] = x.y - y.y; inv[2 * nvo + o] = x.z - y.z;
+    if (err) {
+        const float3 d = wp_sample(W, xfm_point(ras_to_field, x.x, x.y, x.z));
+        const float rx = (x.x + d.x) - y.x, ry = (x.y + d.y) - y.y, rz = (x.z + d.z) - y.z;
+        float e = fmaxf(fmaxf(fabsf(rx), fabsf(ry)), fabsf(rz));           // (fmaxf drops a NaN operand: it is put back)
+        if (rx != rx || ry != ry || rz != rz) e = __builtin_nanf("");
+        err[o] = e;
+    }
+}
+
+int wp_field_check(const void *packed, int nx, int ny, int nz) {
+    FIB_CHECK(packed, FIB_ERR_INVALID, "NULL field");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "the field's dimensions must be positive");
+    FIB_CHECK(std::max({nx, ny, nz}) <= WP_MAX_DIM, FIB_ERR_UNSUPPORTED, "a field dimension above 2^24");
+    FIB_CHECK((reinterpret_cast<uintptr_t>(packed) & 15) == 0, FIB_ERR_INVALID, "the packed field must be 16-byte aligned");
+    return FIB_OK;
+}
+
+bool wp_disjoint(const void *a, uint64_t na, const void *b, uint64_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa + na <= pb || pb + nb <= pa;
+}
+
+XfmMat wp_mat(const float m[16]) {
+    XfmMat X;
+    memcpy(X.m, m, sizeof X.m);
+    return X;
+}
+
+}  // namespace
+
+#define WP_RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
+
+extern "C" int fibd_warp_pack(const float *disp, int nx, int ny, int nz, void *packed, void *stream) try {
+    FIB_CHECK(disp, FIB_ERR_INVALID, "NULL argument");
+    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_CHECK((reinterpret_cast<uintptr_t>(disp) & 3) == 0, FIB_ERR_INVALID, "the field must be 4-byte aligned");
+    const int64_t nvox = (int64_t)nx * ny * nz;
+    FIB_CHECK(wp_disjoint(disp, 12ull * (uint64_t)nvox, packed, 16ull * (uint64_t)nvox), FIB_ERR_INVALID, "disp and packed must not overlap");
+    FIB_CHECK(fib::cdiv(nvox, WP_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "the field needs 2^31 workgroups or more");
+    fib::ProfScope prof("warp_pack", (hipStream_t)stream);
+    hipLaunchKernelGGL(wp_pack_kernel, dim3((unsigned)fib::cdiv(nvox, WP_BLOCK)), dim3(WP_BLOCK), 0, (hipStream_t)stream, disp, nvox,
+                       static_cast<float4 *>(packed));
+    FIB_HIP(hipGetLastError());
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fibd_warp_points(const void *packed, int nx, int ny, int nz, const float to_ras[16], const float to_field[16], const float from_ras[16],
+                                const float *xyz, float *out, int64_t npoints, void *stream) try {
+    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_CHECK(to_ras && to_field && from_ras, FIB_ERR_INVALID, "NULL matrix");
+    FIB_CHECK(npoints >= 0, FIB_ERR_INVALID, "npoints must not be negative");
+    if (npoints == 0) return FIB_OK;
+    FIB_CHECK(xyz && out, FIB_ERR_INVALID, "NULL argument");
+    const uintptr_t ai = reinterpret_cast<uintptr_t>(xyz), ao = reinterpret_cast<uintptr_t>(out);
+    FIB_CHECK((ai & 3) == 0 && (ao & 3) == 0, FIB_ERR_INVALID, "points must be 4-byte aligned");
+    // in place or not at all: a partial overlap would let one thread's stores reach another thread's loads
+    FIB_CHECK(ai == ao || wp_disjoint(xyz, 12ull * (uint64_t)npoints, out, 12ull * (uint64_t)npoints), FIB_ERR_INVALID,
+              "xyz and out must be the same array or not overlap");
+    FIB_CHECK(wp_disjoint(packed, 16ull * (uint64_t)nx * ny * nz, out, 12ull * (uint64_t)npoints), FIB_ERR_INVALID, "out must not overlap the field");
+    FIB_CHECK(fib::cdiv(npoints, WP_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "the points need 2^31 workgroups or more");
+    const WarpField W{static_cast<const float4 *>(packed), nx, ny, nz};
+    fib::ProfScope prof("warp_points", (hipStream_t)stream);
+    hipLaunchKernelGGL(wp_points_kernel, dim3((unsigned)fib::cdiv(npoints, WP_BLOCK)), dim3(WP_BLOCK), 0, (hipStream_t)stream, W, wp_mat(to_ras),
+                       wp_mat(to_field), wp_mat(from_ras), xyz, out, npoints);
+    FIB_HIP(hipGetLastError());
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fibd_warp_volume(const void *packed, int nx, int ny, int nz, const float to_ras[16], const float to_field[16], const float from_ras[16],
+                                const void *vol, int nxi, int nyi, int nzi, int nframes, int interp, int32_t outside_bits, void *out, int nxo, int nyo,
+                                int nzo, void *stream) try {
+    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_CHECK(to_ras && to_field && from_ras && vol && out, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nxi > 0 && nyi > 0 && nzi > 0 && nxo > 0 && nyo > 0 && nzo > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
+    FIB_CHECK(interp == FIB_VOL_NEAREST || interp == FIB_VOL_TRILINEAR, FIB_ERR_INVALID, "unknown interpolation %d", interp);
+    FIB_CHECK(std::max({nxi, nyi, nzi, nxo, nyo, nzo}) <= WP_MAX_DIM, FIB_ERR_UNSUPPORTED, "a volume dimension above 2^24");
+    FIB_CHECK(((reinterpret_cast<uintptr_t>(vol) | reinterpret_cast<uintptr_t>(out)) & 3) == 0, FIB_ERR_INVALID, "volumes must be 4-byte aligned");
+    const uint64_t bi = 4ull * (uint64_t)nxi * nyi * nzi * nframes, bo = 4ull * (uint64_t)nxo * nyo * nzo * nframes;
+    // a gather: any output word may be read as another thread's input, so there is no in-place form
+    FIB_CHECK(wp_disjoint(vol, bi, out, bo), FIB_ERR_INVALID, "vol and out must not overlap");
+    FIB_CHECK(wp_disjoint(packed, 16ull * (uint64_t)nx * ny * nz, out, bo), FIB_ERR_INVALID, "out must not overlap the field");
+    constexpr int BX = 64, BY = 4;
+    const unsigned nsx = (unsigned)fib::cdiv(nxo, BX), nsy = (unsigned)fib::cdiv(nyo, BY);
+    FIB_CHECK(fib::cdiv(nxo, BX) * fib::cdiv(nyo, BY) * nzo < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "the output volume needs 2^31 workgroups or more");
+    const WarpField W{static_cast<const float4 *>(packed), nx, ny, nz};
+    const dim3 grid(nsx * nsy * (unsigned)nzo), block(BX * BY);        // a flat grid over (x segment, y tile, z): no 65535 limit on ny or nz
+    const uint32_t *src = static_cast<const uint32_t *>(vol);
+    uint32_t *dst = static_cast<uint32_t *>(out);
+    fib::ProfScope prof("warp_volume", (hipStream_t)stream);
+    if (nframes >= 4)
+        hipLaunchKernelGGL((wp_volume_kernel<BX, BY, 4>), grid, block, 0, (hipStream_t)stream, W, wp_mat(to_ras), wp_mat(to_field), wp_mat(from_ras), src,
+                           nxi, nyi, nzi, nframes, interp, (uint32_t)outside_bits, dst, nxo, nyo, nzo, nsx, nsy);
+    else
+        hipLaunchKernelGGL((wp_volume_kernel<BX, BY, 1>), grid, block, 0, (hipStream_t)stream, W, wp_mat(to_ras), wp_mat(to_field), wp_mat(from_ras), src,
+                           nxi, nyi, nzi, nframes, interp, (uint32_t)outside_bits, dst, nxo, nyo, nzo, nsx, nsy);
+    FIB_HIP(hipGetLastError());
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fibd_warp_invert(const void *packed, int nx, int ny, int nz, const float out_to_ras[16], const float ras_to_field[16], int niter,
+                                float *inv, float *err, int nxo, int nyo, int nzo, void *stream) try {
+    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_CHECK(out_to_ras && ras_to_field && inv, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(niter >= 0, FIB_ERR_INVALID, "niter must not be negative");
+    FIB_CHECK(nxo > 0 && nyo > 0 && nzo > 0, FIB_ERR_INVALID, "the output dimensions must be positive");
+    FIB_CHECK(std::max({nxo, nyo, nzo}) <= WP_MAX_DIM, FIB_ERR_UNSUPPORTED, "an output dimension above 2^24");
+    FIB_CHECK(((reinterpret_cast<uintptr_t>(inv) | reinterpret_cast<uintptr_t>(err)) & 3) == 0, FIB_ERR_INVALID, "inv and err must be 4-byte aligned");
+    const uint64_t nvo = (uint64_t)nxo * nyo * nzo, bf = 16ull * (uint64_t)nx * ny * nz;
+    FIB_CHECK(wp_disjoint(packed, bf, inv, 12 * nvo) && (!err || (wp_disjoint(packed, bf, err, 4 * nvo) && wp_disjoint(inv, 12 * nvo, err, 4 * nvo))),
+              FIB_ERR_INVALID, "the field, inv and err must not overlap");
+    constexpr int BX = 64, BY = 4;
+    const unsigned nsx = (unsigned)fib::cdiv(nxo, BX), nsy = (unsigned)fib::cdiv(nyo, BY);
+    FIB_CHECK(fib::cdiv(nxo, BX) * fib::cdiv(nyo, BY) * nzo < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "the output volume needs 2^31 workgroups or more");
+    const WarpField W{static_cast<const float4 *>(packed), nx, ny, nz};
+    fib::ProfScope prof("warp_invert", (hipStream_t)stream);
+    hipLaunchKernelGGL((wp_invert_kernel<BX, BY>), dim3(nsx * nsy * (unsigned)nzo), dim3(BX * BY), 0, (hipStream_t)stream, W, wp_mat(out_to_ras),
+                       wp_mat(ras_to_field), niter, inv, err, nxo, nyo, nzo, nsx, nsy);
+    FIB_HIP(hipGetLastError());
+    return FIB_OK;
+} FIB_API_CATCH

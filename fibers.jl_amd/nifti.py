@@ -250,10 +250,14 @@ def _mri_read_mgh(infile, headeronly):
     return _read_btables(mri, infile[: -4])
 
 
-def mri_write(mri, outfile, datatype=None):
+def mri_write(mri, outfile, datatype=None, vector=False):
     """mri_write for NIfTI and MGH (.mgh / .mgz) outputs (mri.jl:1695-1919 + save_nifti 2059-2166, save_mgh).  Returns True on error
-    (byte count mismatch), like the reference."""
+    (byte count mismatch), like the reference.  vector=True (NIfTI only; not in the reference) writes the frames as the components of
+    a vector image, the form ITK / ANTs give a displacement field: dim = [5, nx, ny, nz, 1, nframes], intent code 1007; the data
+    bytes are the same."""
     low = outfile.lower()
+    if vector and low.endswith((".mgh", ".mgz")):
+        raise ValueError("a vector image is a NIfTI file, not " + outfile)
     if low.endswith((".mgh", ".mgz")):                                            # mri.jl:1730-1739
         vol = mri.vol if datatype is None else mri.vol.astype(datatype)
         err = save_mgh(vol, outfile, mri.vox2ras, [float(getattr(mri, "tr", 0.0)), 0.0, 0.0, 0.0])
@@ -269,6 +273,8 @@ def mri_write(mri, outfile, datatype=None):
     code, bitpix = _DTYPE_CODES[dt]
     nx, ny, nz, nf = vol.shape
     dim = [4 if nf > 1 else 3, nx, ny, nz, nf, 1, 1, 1]
+    if vector:
+        dim = [5, nx, ny, nz, 1, nf, 1, 1]
     glmin = 0
     if dim[1] > 2 ** 15:
         glmin, dim[1] = dim[1], -1
@@ -276,7 +282,7 @@ def mri_write(mri, outfile, datatype=None):
     b, c, d, x, y, z, qfac = vox2ras_to_qform(M)
     pixdim = [qfac] + [float(v) for v in mri.volres[:3]] + [float(getattr(mri, "tr", 0.0)), 0.0, 0.0, 0.0]
     nh = getattr(mri, "niftihdr", None) or {}
-    hdr = _HDR.pack(348, b"\0" * 10, b"\0" * 18, 0, 0, 0, 0, *dim, 0.0, 0.0, 0.0, 0, code, bitpix, 0, *pixdim,
+    hdr = _HDR.pack(348, b"\0" * 10, b"\0" * 18, 0, 0, 0, 0, *dim, 0.0, 0.0, 0.0, 1007 if vector else 0, code, bitpix, 0, *pixdim,
                     352.0, float(nh.get("scl_slope", 0.0)), float(nh.get("scl_inter", 0.0)), 0, 0, 2 | 16,
                     float(vol.max()) if vol.size else 0.0, float(vol.min()) if vol.size else 0.0, 0.0, 0.0, 0, glmin,
                     ("%-80s" % "FreeSurfer julia").encode(), b"\0" * 24, 1, 1, b, c, d, x, y, z,

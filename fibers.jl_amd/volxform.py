@@ -50,6 +50,18 @@ def _bits(outside, dtype, narrow=None):
         return int(v.astype(dtype).view(np.int32)[0])
 
 
+def _words(mri, interp, who):
+    """mri.vol as the 32-bit words the sampler takes: float32 (either interpolation), int32 / uint32 as they are and 8- / 16-bit
+    integers widened, with "nearest"; anything else is a ValueError in the name of `who`"""
+    dt, nearest = mri.vol.dtype, _interp(interp) == _lib.VOL_INTERP["nearest"]
+    if dt in _WIDEN and nearest:
+        return np.asfortranarray(mri.vol.astype(_WIDEN[dt]))
+    if dt in _WORDS and (dt == np.float32 or nearest):
+        return np.asfortranarray(mri.vol)
+    raise ValueError("%s takes float32 volumes (either interpolation) or 8- / 16- / 32-bit integer volumes with 'nearest', not %s with %r"
+                     % (who, dt, interp))
+
+
 def xfm_header(inref: MRI, outref: MRI) -> Xform:
     """The header-only transform from `inref`'s voxels to `outref`'s, for volumes that are already in register (FreeSurfer's
     --regheader): ras2ras = I, vox2vox = float32(inv(outref.vox2ras) @ inref.vox2ras) computed in float64; sizes, resolutions and
@@ -77,13 +89,7 @@ def mri_xform(xfm: Xform, mri: MRI, interp: str = "trilinear", outside=0, device
     if tuple(int(v) for v in xfm.insize) != tuple(mri.volsize):
         raise ValueError("the volume is %s but the transform's input space is %s" % (tuple(mri.volsize), tuple(int(v) for v in xfm.insize)))
     dt = mri.vol.dtype
-    if dt in _WIDEN and code == _lib.VOL_INTERP["nearest"]:
-        work = np.asfortranarray(mri.vol.astype(_WIDEN[dt]))
-    elif dt in _WORDS and (dt == np.float32 or code == _lib.VOL_INTERP["nearest"]):
-        work = np.asfortranarray(mri.vol)
-    else:
-        raise ValueError("mri_xform takes float32 volumes (either interpolation) or 8- / 16- / 32-bit integer volumes with 'nearest', not %s with %r"
-                         % (dt, interp))
+    work = _words(mri, interp, "mri_xform")
     M = vol_xform_matrix(xfm)
     nxi, nyi, nzi = (int(v) for v in mri.volsize)
     nxo, nyo, nzo = (int(v) for v in xfm.outsize)

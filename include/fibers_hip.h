@@ -703,6 +703,57 @@ int fibd_vol_xform(const float out2in[16], const void *vol, int nxi, int nyi, in
                    void *out, int nxo, int nyo, int nzo, void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Non-linear warps: a displacement field applied to points and volumes, and inverted    */
+/* (NOT in the reference)                                                                 */
+/* ------------------------------------------------------------------------------------ */
+/* The non-linear sibling of fib_xfm_apply and of the volume resampling above, with their conventions: float32, every multiply and add
+ * rounded on its own (no fused multiply-add), planar volumes [nframes][nz][ny][nx], 0-based voxel indices for volumes.  These
+ * definitions are this project's own; they are the contract.
+ *
+ * FIELD.  A displacement field is a float32 volume of 3 frames on a grid of its own (nx, ny, nz and the vox2ras of that grid, RAS mm):
+ * frame c at voxel (i, j, k) is component c of the displacement IN MM, RAS.  It defines phi(x) = x + d(x) for a RAS point x of the
+ * field's space A; phi(x) is a RAS point of the other space B.  Points travel A -> B; a volume is pulled back, so a volume of B lands on
+ * a grid of A.  Device form: float4 [nvox] = (dx, dy, dz, 0), 16-byte aligned, made once by fibd_warp_pack from the planar field (one
+ * aligned 16-byte gather per neighbour).  The host forms take the planar field and pack it themselves.
+ *
+ * SAMPLE S(q), q in float32 field-voxel coordinates (0-based).  If any q_c is NaN all three results are NaN.  Otherwise per component,
+ * with n_c the field's size: qc = q_c < 0 ? 0 : (q_c > n_c - 1 ? n_c - 1 : q_c) -- beyond the grid the EDGE displacement continues
+ * (+-Inf clamp, -0.0 passes; no zero outside and no inside test: a jump to zero at the border makes the inversion below oscillate in
+ * the border voxels, the clamped rule converges) -- then i0 = (int)floor(qc), f = qc - floor(qc) (one rounding), g = 1 - f,
+ * i1 = min(i0 + 1, n_c - 1).  Each displacement component is then interpolated between the 8 neighbours in the order and with the
+ * roundings of FIB_VOL_TRILINEAR above (x pairs, then y, then z); f == 0 is not special-cased.
+ *
+ * WARP OF A POINT p (any 3-vector of caller coordinates) with three row-major float[16] matrices, each applied with fib_xfm_apply's
+ * arithmetic (xfm_point: the projective row and the IEEE division included):
+ *   x = xfm_point(to_ras, p),  q = xfm_point(to_field, p),  d = S(q),  y_c = x_c + d_c (one rounding each),  p' = xfm_point(from_ras, y).
+ * to_ras takes caller coordinates to RAS of space A, to_field to the field's voxels, from_ras takes RAS of space B to the caller's
+ * output coordinates.
+ *
+ * WARP OF A VOLUME.  For the output voxel (i, j, k), taken as floats, p' is the warp of that point; `vol` is then sampled at p' exactly
+ * as fibd_vol_xform samples at its p: the INSIDE rule, FIB_VOL_NEAREST / FIB_VOL_TRILINEAR, outside_bits, every frame with the same p'.
+ *
+ * INVERSE.  For the output voxel (i, j, k) of a grid in space B: y = xfm_point(out_to_ras, i, j, k), x = y; niter times
+ * q = xfm_point(ras_to_field, x), d = S(q), x_c = y_c - d_c; then inv_c = x_c - y_c (three planar frames on the output grid: the field
+ * of phi^-1, mm RAS) and, once more, d = S(xfm_point(ras_to_field, x)), r_c = (x_c + d_c) - y_c, err = max_c |r_c| (a NaN in any r_c
+ * gives NaN).  niter = 0 gives inv = 0 and err = the displacement at y.  The kernel leaves the loop when an iterate repeats bit for bit
+ * (every later one is the same) and uses no other stopping rule.  The iteration converges where the field's Jacobian norm is below 1;
+ * err is the caller's check where the field folds.
+ *
+ * The four device entries are asynchronous on `stream`, allocate nothing and do not synchronise; element offsets are 64-bit.
+ * FIB_ERR_INVALID: NULL pointers (err of fibd_warp_invert may be NULL), non-positive sizes (npoints == 0 does nothing), niter < 0, an
+ * unknown interp, a packed field that is not 16-byte aligned, ANY overlap of vol and out; a dimension above 2^24 is
+ * FIB_ERR_UNSUPPORTED.  fibd_warp_points: out == xyz is allowed (other overlaps are not) and points need only be 4-byte aligned, as
+ * for fibd_xfm_apply; volumes, inv and err need only be 4-byte aligned. */
+int fibd_warp_pack(const float *disp, int nx, int ny, int nz, void *packed, void *stream);
+int fibd_warp_points(const void *packed, int nx, int ny, int nz, const float to_ras[16], const float to_field[16], const float from_ras[16],
+                     const float *xyz, float *out, int64_t npoints, void *stream);
+int fibd_warp_volume(const void *packed, int nx, int ny, int nz, const float to_ras[16], const float to_field[16], const float from_ras[16],
+                     const void *vol, int nxi, int nyi, int nzi, int nframes, int interp, int32_t outside_bits, void *out, int nxo, int nyo,
+                     int nzo, void *stream);
+int fibd_warp_invert(const void *packed, int nx, int ny, int nz, const float out_to_ras[16], const float ras_to_field[16], int niter,
+                     float *inv, float *err, int nxo, int nyo, int nzo, void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Host-buffer drop-in entry points (what the Julia wrapper ccalls)                       */
 /* ------------------------------------------------------------------------------------ */
 
@@ -768,6 +819,19 @@ int fib_xfm_apply(int device, const float vox2vox[16], const float *in, float *o
  * calls.  One device: FIB_DEVICE_ALL is FIB_ERR_UNSUPPORTED. */
 int fib_vol_xform(int device, const float out2in[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp,
                   int32_t outside_bits, void *out, int nxo, int nyo, int nzo);
+/* host-buffer forms of the non-linear warps (the "Non-linear warps" section above): every array is host memory and `disp` is the PLANAR
+ * field [3][nz][ny][nx]; the call uploads it, packs it on the device and keeps it resident until it returns.  One device
+ * (FIB_DEVICE_ALL is FIB_ERR_UNSUPPORTED); the device buffers are local to the call.  Results do not depend on the chunking.
+ * fib_warp_points: the points go in chunks of 2^22 (FIBERS_WARP_POINTS=<n> overrides); out == xyz is allowed, other overlaps are
+ * FIB_ERR_INVALID; npoints == 0 does nothing.  fib_warp_volume: chunks of whole frames sized to half the free device memory, as
+ * fib_vol_xform walks them (FIBERS_WARP_FRAMES=<n> overrides).  fib_warp_invert: inv [3][nzo][nyo][nxo], err [nzo][nyo][nxo] or NULL. */
+int fib_warp_points(int device, const float *disp, int nx, int ny, int nz, const float to_ras[16], const float to_field[16],
+                    const float from_ras[16], const float *xyz, float *out, int64_t npoints);
+int fib_warp_volume(int device, const float *disp, int nx, int ny, int nz, const float to_ras[16], const float to_field[16],
+                    const float from_ras[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp, int32_t outside_bits,
+                    void *out, int nxo, int nyo, int nzo);
+int fib_warp_invert(int device, const float *disp, int nx, int ny, int nz, const float out_to_ras[16], const float ras_to_field[16], int niter,
+                    float *inv, float *err, int nxo, int nyo, int nzo);
 int fib_adc_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, float *adc, float *s0);
 /* host-buffer forms of the tract maps (fibd_str_density / fibd_str_sample / fibd_str_stats above): every array is host memory.  The

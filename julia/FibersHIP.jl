@@ -416,6 +416,74 @@ function vol_xform(xfm::Xform{Float32}, vol::Array{Int32,4}; interp::Symbol=:nea
   return vol_xform_call(xfm, vol, interp, Int32(outside), device)
 end
 
+# ---- non-linear warps (NOT in the reference; the definitions are the "Non-linear warps" section of include/fibers_hip.h) -----------
+# A field is a Float32 array [nx, ny, nz, 3] (the displacement in mm, RAS) with the vox2ras of its grid.  Matrices are made in Float64
+# from the Float32 fields, rounded once, and go to the C ABI row-major.
+warp_rowmajor(m) = Matrix{Float32}(permutedims(Float32.(m)))
+warp_shift(v) = [1.0 0 0 v; 0 1 0 v; 0 0 1 v; 0 0 0 1]
+
+"str_warp(field, field_vox2ras, tr, out_vox2ras) — the lines of tr through phi(x) = x + d(x): tract volume -> (pre_ras2ras) -> the
+field's space -> phi -> (post_ras2ras) -> the volume of out_vox2ras.  `origin` is the index of the first voxel's centre in the tract's
+coordinates (1 for what `stream` makes).  Returns the moved lines; the header of the new Tract is the caller's to fill from the output
+volume, as str_xform does."
+function str_warp(field::Array{Float32,4}, field_vox2ras::Matrix{Float32}, tr::Tract{Float32}, out_vox2ras::Matrix{Float32};
+                  pre_ras2ras=Matrix{Float64}(I, 4, 4), post_ras2ras=Matrix{Float64}(I, 4, 4), origin::Real=1, device::Integer=0)
+  size(field, 4) == 3 || error("a displacement field has 3 frames")
+  to_ras   = Float64.(pre_ras2ras) * Float64.(tr.vox_to_ras) * warp_shift(-Float64(origin))
+  to_field = inv(Float64.(field_vox2ras)) * to_ras
+  from_ras = warp_shift(Float64(origin)) * inv(Float64.(out_vox2ras)) * Float64.(post_ras2ras)
+  a, q, b = warp_rowmajor(to_ras), warp_rowmajor(to_field), warp_rowmajor(from_ras)
+  n   = [size(x, 2) for x in tr.xyz]
+  off = cumsum(vcat(0, n))
+  packed = isempty(n) ? Matrix{Float32}(undef, 3, 0) : reduce(hcat, tr.xyz)
+  moved  = similar(packed)
+  nx, ny, nz = size(field)[1:3]
+  GC.@preserve field a q b packed moved fib_check(ccall((:fib_warp_points, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64),
+      device, field, nx, ny, nz, a, q, b, packed, moved, size(packed, 2)))
+  return [moved[:, off[i]+1:off[i+1]] for i in 1:length(n)]
+end
+
+"mri_warp(field, field_vox2ras, vol, vol_vox2ras, outsize, out_vox2ras) — vol [nx, ny, nz, nframes] pulled back through the field onto
+the grid (outsize, out_vox2ras): the sampling positions travel output voxel -> (pre) -> the field's space -> phi -> (post) -> vol's voxels"
+function mri_warp(field::Array{Float32,4}, field_vox2ras::Matrix{Float32}, vol::Array{T,4}, vol_vox2ras::Matrix{Float32}, outsize,
+                  out_vox2ras::Matrix{Float32}; interp::Symbol=(T == Float32 ? :trilinear : :nearest), outside::Real=0,
+                  pre_ras2ras=Matrix{Float64}(I, 4, 4), post_ras2ras=Matrix{Float64}(I, 4, 4), device::Integer=0) where T<:Union{Float32,Int32}
+  size(field, 4) == 3 || error("a displacement field has 3 frames")
+  haskey(FIB_VOL_INTERP, interp) || error("interp must be :nearest or :trilinear")
+  (T == Float32 || interp == :nearest) || error("Int32 volumes take interp=:nearest only")
+  to_ras   = Float64.(pre_ras2ras) * Float64.(out_vox2ras)
+  to_field = inv(Float64.(field_vox2ras)) * to_ras
+  from_ras = inv(Float64.(vol_vox2ras)) * Float64.(post_ras2ras)
+  a, q, b = warp_rowmajor(to_ras), warp_rowmajor(to_field), warp_rowmajor(from_ras)
+  nx, ny, nz = size(field)[1:3]
+  nxi, nyi, nzi, nf = size(vol)
+  nxo, nyo, nzo = Int.(outsize)
+  out  = Array{T,4}(undef, nxo, nyo, nzo, nf)
+  bits = T == Float32 ? reinterpret(Int32, Float32(outside)) : Int32(outside)
+  GC.@preserve field a q b vol out fib_check(ccall((:fib_warp_volume, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Int32,
+       Ptr{Cvoid}, Cint, Cint, Cint),
+      device, field, nx, ny, nz, a, q, b, vol, nxi, nyi, nzi, nf, FIB_VOL_INTERP[interp], bits, out, nxo, nyo, nzo))
+  return out
+end
+
+"warp_invert(field, field_vox2ras, outsize, out_vox2ras) — (inv [nxo, nyo, nzo, 3], err [nxo, nyo, nzo]): the field of phi^-1 on the
+output grid by niter fixed-point steps, and the residual max_c |x_c + d_c(x) - y_c| in mm at every voxel"
+function warp_invert(field::Array{Float32,4}, field_vox2ras::Matrix{Float32}, outsize, out_vox2ras::Matrix{Float32};
+                     niter::Integer=20, device::Integer=0)
+  size(field, 4) == 3 || error("a displacement field has 3 frames")
+  y, q = warp_rowmajor(out_vox2ras), warp_rowmajor(inv(Float64.(field_vox2ras)))
+  nx, ny, nz = size(field)[1:3]
+  nxo, nyo, nzo = Int.(outsize)
+  invf = Array{Float32,4}(undef, nxo, nyo, nzo, 3)
+  err  = Array{Float32,3}(undef, nxo, nyo, nzo)
+  GC.@preserve field y q invf err fib_check(ccall((:fib_warp_invert, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Float32}, Ptr{Float32}, Cint, Cint, Cint),
+      device, field, nx, ny, nz, y, q, niter, invf, err, nxo, nyo, nzo))
+  return invf, err
+end
+
 # ---- tract maps (NOT in the reference; the definitions are the "Tract maps" section of include/fibers_hip.h) ----------------------
 const FIB_DENSITY_MODES = Dict(:points => 0, :lines => 1, :endpoints => 2)
 const FIB_DENSITY_ACCUMULATE = 0x100
