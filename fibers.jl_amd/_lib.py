@@ -39,6 +39,15 @@ class DkiOut(C.Structure):
                 ("s0", "eigval1", "eigval2", "eigval3", "eigvec1", "eigvec2", "eigvec3", "rd", "md", "fa", "mk", "ak", "rk", "kt")]
 
 
+class CsdParams(C.Structure):
+    _fields_ = [("lmax", C.c_int), ("lambda_para", C.c_float), ("lambda_perp", C.c_float), ("s0", C.c_float), ("b0_thresh", C.c_float),
+                ("shell", C.c_float), ("b_tol", C.c_float), ("lam", C.c_float), ("tau", C.c_float), ("niter", C.c_int)]
+
+
+class CsdOut(C.Structure):
+    _fields_ = [("sh", C.c_void_p), ("odf", C.c_void_p), ("niter", C.c_void_p), ("peak", C.c_void_p * 3), ("f", C.c_void_p * 3)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("nvec", C.c_int32),
                 ("len_min", C.c_int32), ("len_max", C.c_int32),
@@ -79,6 +88,11 @@ _PROTOS = {
     "fib_dki_plan_destroy": (None, [vp]),
     "fib_dki_plan_tables": (i32, [vp, vp, vp, vp]),
     "fibd_dki_fit": (i32, [vp, vp, vp, i64, C.POINTER(DkiOut), vp]),
+    "fib_csd_design": (i32, [vp, vp, i32, vp, i32, C.POINTER(CsdParams), vp, C.POINTER(i32), vp, vp, vp, vp, C.POINTER(i32)]),
+    "fib_csd_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, C.POINTER(CsdParams), C.POINTER(vp)]),
+    "fib_csd_plan_destroy": (None, [vp]),
+    "fib_csd_plan_tables": (i32, [vp, vp, C.POINTER(i32), vp, vp, vp, vp]),
+    "fibd_csd_rec": (i32, [vp, vp, vp, i64, C.POINTER(CsdOut), vp]),
     "fib_gqi_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, f32, C.POINTER(vp)]),
     "fib_dsi_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, i32, C.POINTER(vp)]),
     "fib_gqi_plan_create_fmt": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, f32, i32, C.POINTER(vp)]),
@@ -158,6 +172,7 @@ _PROTOS = {
     "fib_dti_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, C.POINTER(DtiOut)]),
     "fib_adc_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
     "fib_dki_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, C.POINTER(DkiParams), C.POINTER(DkiOut)]),
+    "fib_csd_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(CsdParams), C.POINTER(CsdOut)]),
     "fib_gqi_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, P3, P3]),
     "fib_dsi_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, P3, P3]),
     "fib_rumba_plan_create": (i32, [i32, vp, vp, i32, vp, i32, f32, f32, f32, f32, C.POINTER(vp)]),

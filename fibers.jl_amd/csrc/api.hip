@@ -549,6 +549,44 @@ extern "C" int fib_dki_fit(int device, const float *dwi, int nx, int ny, int nz,
                                  });
 } FIB_API_CATCH
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// csd_rec
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_csd_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
+                           const void *mask, int mask_dtype, const float *bval, const float *bvec,
+                           const float *verts, int nverts, const int32_t *faces, int nfaces, const fib_csd_params *params, const fib_csd_out *out) try {
+    FitCall c;
+    RC(fit_call(c, device, bval, nvol, bvec != nullptr, dwi && mask && out && params, nx, ny, nz, mask_dtype,
+                out && out->sh && out->odf && out->niter && out->peak[0] && out->peak[1] && out->peak[2] && out->f[0] && out->f[1] && out->f[2],
+                "NULL output volume", verts && faces && nverts >= 2 && nverts % 2 == 0 && nfaces > 0));
+    // the refusals of the design come before any device is touched, and give the output rows their counts
+    int nshell = 0, rank = 0;
+    RC(fib_csd_design(bval, bvec, nvol, verts, nverts, params, nullptr, &nshell, nullptr, nullptr, nullptr, nullptr, &rank));
+    const int n = (params->lmax + 1) * (params->lmax + 2) / 2, nreg = nverts / 2;
+    const std::vector<Rows> ins = {{dwi, nullptr, nvol}};
+    const std::vector<Rows> outs = {{nullptr, out->sh, n}, {nullptr, out->odf, nreg}, {nullptr, out->niter, 1},
+                                    {nullptr, out->peak[0], 3}, {nullptr, out->peak[1], 3}, {nullptr, out->peak[2], 3},
+                                    {nullptr, out->f[0], 1}, {nullptr, out->f[1], 1}, {nullptr, out->f[2], 1}};
+    std::string key;
+    key_add(key, "csd", 3);
+    key_add(key, bval, sizeof(float) * nvol);
+    key_add(key, bvec, sizeof(float) * 3 * nvol);
+    key_add(key, verts, sizeof(float) * 3 * nverts);
+    key_add(key, faces, sizeof(int32_t) * 3 * nfaces);
+    key_add(key, params, sizeof *params);
+    return fit_run<fib_csd_plan>(c, ins, mask, outs,
+                                 [&](DevState &d, fib_csd_plan **p) {
+                                     return cached_plan<fib_csd_plan, fib_csd_plan_destroy>(d, key, [&](fib_csd_plan **q) {
+                                         return fib_csd_plan_create(d.device, bval, bvec, nvol, verts, nverts, faces, nfaces, params, q); }, p);
+                                 },
+                                 [&](const fib_csd_plan *plan, const float *din, const uint8_t *dm, int64_t nv, float *b, hipStream_t st) -> int {
+                                     float *pk = b + (int64_t)(n + nreg + 1) * nv;
+                                     fib_csd_out dev{b, b + (int64_t)n * nv, b + (int64_t)(n + nreg) * nv, {pk, pk + 3 * nv, pk + 6 * nv},
+                                                     {pk + 9 * nv, pk + 10 * nv, pk + 11 * nv}};
+                                     return fibd_csd_rec(plan, din, dm, nv, &dev, st);
+                                 });
+} FIB_API_CATCH
+
 extern "C" int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigvec, float *eigval) try {
     FIB_CHECK(S && eigvec && eigval, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nvox > 0, FIB_ERR_INVALID, "nvox must be positive");

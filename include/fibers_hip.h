@@ -200,6 +200,62 @@ int fib_dki_plan_tables(const fib_dki_plan *plan, float *A, float *pA, float *di
 int fibd_dki_fit(const fib_dki_plan *plan, const float *dwi, const uint8_t *mask, int64_t nvox,
                  const fib_dki_out *out, void *stream);
 
+/* ---- Constrained spherical deconvolution (not in the reference; this section and DESIGN.md §5 are the definition) ----
+ * Basis: real, even-order spherical harmonics up to lmax in {2, 4, 6, 8}: n = (lmax + 1)(lmax + 2) / 2 = 6, 15, 28, 45 columns, column
+ *   l (l + 1) / 2 + m.  Y_lm = N_l^|m| P_l^|m|(cos theta) {sqrt 2 cos(m phi), m > 0; 1, m = 0; sqrt 2 sin(|m| phi), m < 0},
+ *   N = sqrt((2l + 1) / (4 pi) (l - |m|)! / (l + |m|)!), P with the Condon-Shortley phase, theta from +z, phi = atan2(y, x).
+ * Shell: frames with b <= b0_thresh are b0 frames and are not read.  shell <= 0 means the largest b; the shell frames are those with
+ *   b > b0_thresh and |b - shell| <= b_tol shell, nshell of them in frame order.  nshell < n is FIB_ERR_INVALID, and so is a kernel matrix
+ *   X whose rank (fib_dki_design's rule: singular values > eps(Float32) min(m, n) sigma_max, on the float64 matrix) is below n.
+ * Response: a prolate tensor (lambda_para, lambda_perp) and s0.  R_l = sqrt(4 pi / (2l + 1)) 2 pi int_-1^1 s0 exp(-bbar (lambda_perp +
+ *   (lambda_para - lambda_perp) t^2)) Y_l0(t) dt by 64-point Gauss-Legendre quadrature in float64; bbar = the mean b of the shell frames.
+ * Tables, built in float64 and rounded once to float32:
+ *   X [nshell x n] = Y(shell bvecs) diag(R_l);  Y [nreg x n] = the basis at the first-half vertices (nreg = nverts / 2);
+ *   B [nreg x n] = Y lambda R_0 nshell / nreg (at 362 directions the scaling of Tournier 2007).
+ * Per voxel (skipped, all outputs 0, when the mask is 0 or no shell sample is > 0), with s the shell samples:
+ *   f = the least-squares solution on the first min(n, 15) columns of X, the other coefficients 0;  thr = tau B[0,0] f[0];
+ *   repeat up to niter times:  a = B f;  set = {i : a_i < thr};  from the second pass on, stop if the set equals the previous one;
+ *     solve (X'X + sum_{i in set} b_i b_i') f = X's by Cholesky  (b_i = row i of B; the first pass always solves).
+ *   sh = f;  odf = max(Y f, 0);  niter = the number of solves;  peak[k], f[k] = vertex and odf amplitude of the k-th peak of find_peaks!
+ *   on odf (fibd_find_peaks on the tessellation's faces), zeros beyond the number of peaks.
+ * Arithmetic: float64 from the float32 samples and tables on (X's, a, the matrix, its factor, the solves, Y f); outputs are rounded to
+ *   float32 once.  This is a matter of correctness: membership in the set is discontinuous, one direction changing sides changes the
+ *   matrix by a whole b b', and amplitudes come within 1e-5 of thr (relative) in a few hundred voxels -- float32 sums deviate by 3e-6. */
+typedef struct fib_csd_plan fib_csd_plan;
+typedef struct {
+    int lmax;                /* 2, 4, 6 or 8 */
+    float lambda_para;       /* the response: eigenvalues of the prolate tensor (mm^2/s) and its b = 0 signal */
+    float lambda_perp;
+    float s0;
+    float b0_thresh;         /* 50 */
+    float shell;             /* <= 0: the largest b */
+    float b_tol;             /* 0.05 */
+    float lambda;            /* weight of the constraint rows (1) */
+    float tau;               /* threshold as a fraction of the initial mean amplitude (0.1) */
+    int niter;               /* most solves per voxel (50) */
+} fib_csd_params;
+/* sh [n][nvox], odf [nreg][nvox], niter [nvox] (a count, stored as float32 like every volume), peak[k] [3][nvox], f[k] [nvox] */
+typedef struct {
+    float *sh, *odf, *niter;
+    float *peak[3];
+    float *f[3];
+} fib_csd_out;
+/* Host only (no device needed).  frames [nvol] receives the nshell shell frames (0-based), R [lmax / 2 + 1], X [nshell x n], B and Y
+ * [nreg x n] column-major; any of them may be NULL (size X for nvol rows when nshell is not known).  The frame list and *nshell are filled
+ * even when the scheme is refused, *rank and the tables whenever nshell >= n.  verts [nverts x 3] column-major. */
+int fib_csd_design(const float *bval, const float *bvec, int nvol, const float *verts, int nverts, const fib_csd_params *params,
+                   int32_t *frames, int *nshell, float *R, float *X, float *B, float *Y, int *rank);
+/* faces [nfaces x 3] column-major, 1-based: the peak finder's neighbour table.  Shells of more than 256 frames and tessellations of more
+ * than 384 directions are FIB_ERR_UNSUPPORTED. */
+int fib_csd_plan_create(int device, const float *bval, const float *bvec, int nvol, const float *verts, int nverts,
+                        const int32_t *faces, int nfaces, const fib_csd_params *params, fib_csd_plan **plan);
+void fib_csd_plan_destroy(fib_csd_plan *plan);
+/* host copies of the plan's tables, as fib_csd_design returns them; any pointer may be NULL */
+int fib_csd_plan_tables(const fib_csd_plan *plan, int32_t *frames, int *nshell, float *R, float *X, float *B, float *Y);
+/* dwi [nvol][nvox] planar (every frame of the scheme; the kernel reads the shell's), mask uint8 [nvox].  Every output is written in every
+ * voxel.  The plan holds the peak finder's scratch of the call: one call at a time per plan. */
+int fibd_csd_rec(const fib_csd_plan *plan, const float *dwi, const uint8_t *mask, int64_t nvox, const fib_csd_out *out, void *stream);
+
 /* gqi_rec / dsi_rec volume loop + find_peaks! + peak/qa extraction (gqi.jl:132-162,
  * dsi.jl:197-261).  odf [nvox*nvert] planar; pdf [nvox*nvol] (DSI plans only, else NULL);
  * peak[k] [nvox*3] planar, qa[k] [nvox].  `flags` is a bit set:
@@ -796,6 +852,11 @@ int fib_dti_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
 int fib_dki_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, const float *bvec,
                 const float *verts, int nverts, const fib_dki_params *params, const fib_dki_out *out);
+/* csd_rec: fibd_csd_rec on host arrays, sharded and chunked like fib_dki_fit (FIB_DEVICE_ALL: the device set); the same missing-table
+ * errors, the refusals of fib_csd_design. */
+int fib_csd_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
+                const void *mask, int mask_dtype, const float *bval, const float *bvec,
+                const float *verts, int nverts, const int32_t *faces, int nfaces, const fib_csd_params *params, const fib_csd_out *out);
 /* adc_fit(dwi::MRI, mask::MRI) (dti.jl:164) */
 /* host-buffer form of fibd_st_eigen (structens.jl:13-37) */
 int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigvec, float *eigval);

@@ -127,6 +127,49 @@ function dki_fit(dwi::MRI, mask::MRI, odf_dirs::ODF=sphere_642; min_signal::Real
   return DKI(S0, E1, E2, E3, V1, V2, V3, RD, MD, FA, MK, AK, RK, KT)
 end
 
+# layout: fib_csd_params sizeof 40: lmax@0 lambda_para@4 lambda_perp@8 s0@12 b0_thresh@16 shell@20 b_tol@24 lambda@28 tau@32 niter@36
+struct FibCsdParams
+  lmax::Cint; lambda_para::Cfloat; lambda_perp::Cfloat; s0::Cfloat; b0_thresh::Cfloat; shell::Cfloat; b_tol::Cfloat
+  lambda::Cfloat; tau::Cfloat; niter::Cint
+end
+
+# layout: fib_csd_out sizeof 72: sh@0 odf@8 niter@16 peak@24 f@48
+struct FibCsdOut
+  sh::Ptr{Float32}; odf::Ptr{Float32}; niter::Ptr{Float32}
+  peak::NTuple{3,Ptr{Float32}}; f::NTuple{3,Ptr{Float32}}
+end
+
+"Container for outputs of a CSD reconstruction: harmonic coefficients, fibre ODF, its three peaks with their amplitudes, solves per voxel"
+struct CSD
+  sh::MRI; odf::MRI; peak::Vector{MRI}; f::Vector{MRI}; niter::MRI
+end
+
+"csd_rec(dwi, mask, response, odf_dirs) — constrained spherical deconvolution of one shell (not in the reference; include/fibers_hip.h).
+ response = (lambda_para, lambda_perp, s0); shell <= 0: the largest b"
+function csd_rec(dwi::MRI, mask::MRI, response::NTuple{3,<:Real}, odf_dirs::ODF=sphere_724; lmax::Integer=8, b0_thresh::Real=50f0,
+                 shell::Real=0f0, b_tol::Real=0.05f0, lambda::Real=1f0, tau::Real=0.1f0, niter::Integer=50, device::Integer=0)
+  isempty(dwi.bval) && error("Missing b-value table from input DWI structure")
+  isempty(dwi.bvec) && error("Missing gradient table from input DWI structure")
+  nx, ny, nz, nvol = size(dwi.vol)
+  n = div((lmax + 1) * (lmax + 2), 2)
+  nreg = div(size(odf_dirs.vertices, 1), 2)
+  SH = MRI(mask, n, Float32); O = MRI(mask, nreg, Float32); NI = MRI(mask, 1, Float32)
+  peak = [MRI(mask, 3, Float32) for _ in 1:3]; f = [MRI(mask, 1, Float32) for _ in 1:3]
+  faces = Int32.(odf_dirs.faces); verts = odf_dirs.vertices; vol = dwi.vol::Array{Float32,4}; m = mask.vol
+  par = Ref(FibCsdParams(lmax, response[1], response[2], response[3], b0_thresh, shell, b_tol, lambda, tau, niter))
+  GC.@preserve vol m SH O NI peak f faces verts begin
+    out = Ref(FibCsdOut(pointer(SH.vol), pointer(O.vol), pointer(NI.vol),
+                        (pointer(peak[1].vol), pointer(peak[2].vol), pointer(peak[3].vol)),
+                        (pointer(f[1].vol), pointer(f[2].vol), pointer(f[3].vol))))
+    fib_check(ccall((:fib_csd_rec, libfibers), Cint,
+                    (Cint, Ptr{Float32}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32},
+                     Ptr{Float32}, Cint, Ptr{Int32}, Cint, Ref{FibCsdParams}, Ref{FibCsdOut}),
+                    device, vol, nx, ny, nz, nvol, m, FIB_DTYPE[eltype(m)] | FIB_MASK_OUTPUTS_ZEROED, dwi.bval, dwi.bvec,
+                    verts, size(verts, 1), faces, size(faces, 1), par, out))
+  end
+  return CSD(SH, O, peak, f, NI)
+end
+
 "find_peaks(odf, odf_dirs) — find_peaks!(W) (gqi.jl:180-201) for a whole ODF volume [nx,ny,nz,nvert]:
  returns (isort_top [nx,ny,nz,3] 1-based first-half vertex rows, 0 where absent; nvalid [nx,ny,nz])"
 function find_peaks(odf::MRI, odf_dirs::ODF=sphere_642; device::Integer=0)
