@@ -36,7 +36,7 @@ namespace {
 using fibh::bind_this_thread; using fibh::chunk_count; using fibh::CopyPool; using fibh::dtype_size; using fibh::LiveMap; using fibh::NBUF; using fibh::Rows;
 using fibh::slab;
 
-#define RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
+#define RC(x) FIB_RC(x)
 
 // (mask element types, the copy pool, live maps, the chunk schedule and the chunk pipeline itself: host_tier.h -- pure host code, also built
 // under the sanitizers by tests/test_host_sanitizers.py)

@@ -4,7 +4,7 @@
 // "Bundle tools" section of include/fibers_hip.h.  Resample reads packed lines as fibd_stream_run / fibd_stream_pack leave them.
 //
 // Kernels
-//   tm_scan_block / tm_scan_totals / tm_scan_apply   (tm_lines.inc) the offset scan and its verdict on npts; *status_dev starts at 0 / -1
+//   ls_block / ls_totals / ls_apply <TmItem>   (line_scan.inc, tm_lines.inc) the offset scan and its verdict on npts; *status_dev starts at 0 / -1
 //   bd_resample<G>    lines of at most BD_SHORT_MAX points, G lanes per line, G segments per round.  NO storage for the cumulative
 //                     lengths: in a round every lane computes the length of its segment, then the group runs the float64 running sum
 //                     through its G lanes in sequence (shuffles), so that lane g holds [c_i, c_{i+1}) of its segment -- the same
@@ -26,8 +26,6 @@
 
 // every distance is defined as float64 operations rounded one by one (include/fibers_hip.h): nothing in this file may fuse a*b+c
 #pragma clang fp contract(off)
-
-#define BD_RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
 
 namespace {
 
@@ -271,14 +269,14 @@ extern "C" int fibd_str_resample(const float *xyz, const int32_t *npts, int64_t 
                                  const uint8_t *flip, float *out, int64_t *status_dev, void *work, size_t work_bytes, void *stream) try {
     FIB_CHECK(K >= 2 && K <= BD_K_MAX, FIB_ERR_UNSUPPORTED, "fibd_str_resample gives 2 to %d points per line, not %d", BD_K_MAX, K);
     FIB_CHECK(volres && status_dev, FIB_ERR_INVALID, "NULL argument");
-    BD_RC(tm_check_lines(xyz, npts, nlines, npoints));
+    FIB_RC(tm_check_lines(xyz, npts, nlines, npoints));
     FIB_CHECK(nlines == 0 || out, FIB_ERR_INVALID, "NULL out");
     FIB_CHECK((reinterpret_cast<uintptr_t>(out) & 3) == 0, FIB_ERR_INVALID, "out must be 4-byte aligned");
     FIB_CHECK(fib::cdiv(nlines * BD_RESAMPLE_G, TM_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "too many lines");
     hipStream_t st = (hipStream_t)stream;
     fib::ProfScope prof("str_resample", st);
     TmWork w;
-    BD_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, status_dev, st, w));          // (*status_dev = 0, or -1 for a refused input)
+    FIB_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, status_dev, st, w));          // (*status_dev = 0, or -1 for a refused input)
     if (nlines == 0) return FIB_OK;
     hipLaunchKernelGGL(bd_resample<BD_RESAMPLE_G>, dim3((unsigned)fib::cdiv(nlines * BD_RESAMPLE_G, TM_BLOCK)), dim3(TM_BLOCK), 0, st, xyz, npts, w.off,
                        nlines, volres[0], volres[1], volres[2], K, flip, w.head, reinterpret_cast<uint32_t *>(out), status_dev);
@@ -290,7 +288,7 @@ extern "C" int fibd_str_resample(const float *xyz, const int32_t *npts, int64_t 
 
 extern "C" int fibd_str_assign(const float *lines, int64_t nlines, int K, const float *models, int nmodels, const float volres[3],
                                float thresh_mm, int32_t *label, float *dist, uint8_t *flip, float *dist_all, void *stream) try {
-    BD_RC(bd_check_rows(lines, nlines, K));
+    FIB_RC(bd_check_rows(lines, nlines, K));
     FIB_CHECK(nmodels >= 1 && nmodels < (1 << 24), FIB_ERR_INVALID, "the number of models must be between 1 and 2^24 - 1");
     FIB_CHECK(models && volres, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK((reinterpret_cast<uintptr_t>(models) & 3) == 0, FIB_ERR_INVALID, "models must be 4-byte aligned");
@@ -309,7 +307,7 @@ extern "C" int fibd_str_assign(const float *lines, int64_t nlines, int K, const 
 extern "C" int fibd_str_centroids(const float *lines, int64_t nlines, int K, const int32_t *label, const uint8_t *flip, int nmodels,
                                   int flags, double *sums, uint32_t *counts, void *stream) try {
     FIB_CHECK((flags & ~FIB_CENTROIDS_ACCUMULATE) == 0, FIB_ERR_INVALID, "unknown centroid flags 0x%x", flags);
-    BD_RC(bd_check_rows(lines, nlines, K));
+    FIB_RC(bd_check_rows(lines, nlines, K));
     FIB_CHECK(nmodels >= 1 && nmodels < (1 << 24), FIB_ERR_INVALID, "the number of models must be between 1 and 2^24 - 1");
     FIB_CHECK(sums && counts && (nlines == 0 || label), FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(fib::cdiv(nlines * 64, TM_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "too many lines");

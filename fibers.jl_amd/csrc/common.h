@@ -30,6 +30,9 @@ int fail(int code, const char *fmt, ...);
         if (!(cond)) return fib::fail((code), __VA_ARGS__); \
     } while (0)
 
+// pass a callee's error code (and its message) on
+#define FIB_RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
+
 // No C++ exception crosses the C ABI (include/fibers_hip.h): every extern "C" body is a function-try-block that ends in one of these.
 #define FIB_API_CATCH                                                                                                  \
     catch (const std::bad_alloc &) { return fib::fail(FIB_ERR_NOMEM, "out of host memory"); }                           \

@@ -16,7 +16,7 @@
 //                     is +-U[j] (LDS).  The loop runs until every line of the wave has ended; lines that have ended ride along masked.
 //                     EMIT = false counts (nfwd, nbwd per line), EMIT = true replays a kept line and stores its points at their final
 //                     place: the generator is counter-based, so the replay is exact and no scratch rows exist.
-//   pb_scan_block / pb_scan_totals / pb_scan_apply   len_min and the exclusive scan of (kept lines, their points) between the passes
+//   ls_block / ls_totals / ls_apply <PbItem>   (line_scan.inc) len_min and the exclusive scan of (kept lines, their points) between the passes
 #include "common.h"
 
 #include <algorithm>
@@ -27,8 +27,6 @@
 // the definition rounds every product and sum on its own (include/fibers_hip.h): nothing in this file, host or device, may fuse a*b+c
 #pragma clang fp contract(off)
 
-#define PB_RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
-
 struct fib_prob_plan {
     int device = 0, nvert = 0, nchunk = 0;                     // nchunk = pitch / 8: the 16-byte pieces (and cone bytes) of a row
     float cosang = 0.0f;
@@ -38,11 +36,11 @@ struct fib_prob_plan {
 
 namespace {
 
+#include "line_scan.inc"                                       // LsVec, ls_scan, ls_check_work
+
 constexpr int PB_BLOCK = 256;
 constexpr int PB_NVERT_MAX = 512;
 constexpr int PB_TV32_NVERT = 480;                            // 33 floats per vertex + the partials stay under 64 KB
-constexpr int PB_SCAN_ITEMS = 4;
-constexpr int PB_SCAN_TILE = PB_BLOCK * PB_SCAN_ITEMS;
 constexpr int PB_LEN_MAX = 1 << 24;
 constexpr size_t PB_HEAD_BYTES = 16;                           // {lines, points} as int64
 
@@ -278,82 +276,35 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_trace(const PbArgs a) {
 }
 
 // ---- len_min and the offsets -----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PB_BLOCK) void pb_scan_block(const int32_t *counts, int64_t nlines, int len_min, int64_t *totals) {
-    __shared__ int64_t s_l[PB_BLOCK / 64], s_p[PB_BLOCK / 64];
-    const int64_t base = (int64_t)blockIdx.x * PB_SCAN_TILE + (int64_t)threadIdx.x * PB_SCAN_ITEMS;
-    int64_t nl = 0, np = 0;
-    for (int i = 0; i < PB_SCAN_ITEMS; i++)
-        if (base + i < nlines) { const int n = counts[2 * (base + i)] + counts[2 * (base + i) + 1]; if (n >= len_min) { nl++; np += n; } }
-    for (int d = 32; d >= 1; d >>= 1) { nl += __shfl_xor(nl, d); np += __shfl_xor(np, d); }
-    if ((threadIdx.x & 63) == 0) { s_l[threadIdx.x >> 6] = nl; s_p[threadIdx.x >> 6] = np; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t tl = 0, tp = 0;
-        for (int w = 0; w < PB_BLOCK / 64; w++) { tl += s_l[w]; tp += s_p[w]; }
-        totals[2 * blockIdx.x] = tl; totals[2 * blockIdx.x + 1] = tp;
+// the scan of (kept lines, their points): a line is kept when it has at least len_min points.  lineoff is -1 for a dropped line; ptoff
+// is written for every line.  Nothing is refused; head = {lines, points}.
+struct PbItem {
+    static constexpr int N = 2;
+    const int32_t *counts;
+    int len_min;
+    int64_t *lineoff, *ptoff, *head;
+    __device__ LsVec<2> load(int64_t l, bool &) const {
+        const int n = counts[2 * l] + counts[2 * l + 1];
+        const bool kept = n >= len_min;
+        return {kept ? 1 : 0, kept ? n : 0};
     }
-}
-
-// one workgroup: the block totals -> their exclusive scan in place; head = {lines, points}
-__global__ __launch_bounds__(PB_BLOCK) void pb_scan_totals(int64_t *totals, int64_t nblocks, int64_t *head) {
-    __shared__ int64_t s_l[PB_BLOCK], s_p[PB_BLOCK];
-    const int64_t per = (nblocks + PB_BLOCK - 1) / PB_BLOCK, b0 = threadIdx.x * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
-    int64_t sl = 0, sp = 0;
-    for (int64_t b = b0; b < b1; b++) { sl += totals[2 * b]; sp += totals[2 * b + 1]; }
-    s_l[threadIdx.x] = sl; s_p[threadIdx.x] = sp;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t rl = 0, rp = 0;
-        for (int t = 0; t < PB_BLOCK; t++) { const int64_t l = s_l[t], p = s_p[t]; s_l[t] = rl; s_p[t] = rp; rl += l; rp += p; }
-        head[0] = rl; head[1] = rp;
+    __device__ void store(int64_t l, const LsVec<2> &run, const LsVec<2> &mine) const {
+        lineoff[l] = mine.v[0] ? run.v[0] : -1;
+        ptoff[l] = run.v[1];
     }
-    __syncthreads();
-    int64_t rl = s_l[threadIdx.x], rp = s_p[threadIdx.x];
-    for (int64_t b = b0; b < b1; b++) {
-        const int64_t l = totals[2 * b], p = totals[2 * b + 1];
-        totals[2 * b] = rl; totals[2 * b + 1] = rp;
-        rl += l; rp += p;
-    }
-}
-
-__global__ __launch_bounds__(PB_BLOCK) void pb_scan_apply(const int32_t *counts, int64_t nlines, int len_min, const int64_t *totals, int64_t *lineoff,
-                                                          int64_t *ptoff) {
-    __shared__ int64_t s_l[PB_BLOCK / 64], s_p[PB_BLOCK / 64];
-    const int64_t base = (int64_t)blockIdx.x * PB_SCAN_TILE + (int64_t)threadIdx.x * PB_SCAN_ITEMS;
-    int n[PB_SCAN_ITEMS];
-    int64_t ml = 0, mp = 0;
-    for (int i = 0; i < PB_SCAN_ITEMS; i++) {
-        n[i] = -1;
-        if (base + i < nlines) { const int c = counts[2 * (base + i)] + counts[2 * (base + i) + 1]; if (c >= len_min) { n[i] = c; ml++; mp += c; } }
-    }
-    int64_t il = ml, ip = mp;
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t ol = __shfl_up(il, d), op = __shfl_up(ip, d);
-        if (lane >= d) { il += ol; ip += op; }
-    }
-    if (lane == 63) { s_l[threadIdx.x >> 6] = il; s_p[threadIdx.x >> 6] = ip; }
-    __syncthreads();
-    int64_t rl = totals[2 * blockIdx.x], rp = totals[2 * blockIdx.x + 1];
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) { rl += s_l[w]; rp += s_p[w]; }
-    rl += il - ml; rp += ip - mp;
-    for (int i = 0; i < PB_SCAN_ITEMS; i++)
-        if (base + i < nlines) {
-            lineoff[base + i] = n[i] >= 0 ? rl : -1;
-            ptoff[base + i] = rp;
-            if (n[i] >= 0) { rl++; rp += n[i]; }
-        }
-}
+    __device__ void verdict(const LsVec<2> &grand, bool) const { head[0] = grand.v[0]; head[1] = grand.v[1]; }
+    __device__ bool go() const { return true; }
+};
 
 // the work area: counts int32 [nlines][2] | lineoff int64 [nlines] | ptoff int64 [nlines] | head int64 [2] | block totals int64 [nblocks][2]
 struct PbWork {
     int32_t *counts;
-    int64_t *lineoff, *ptoff, *head, *totals;
-    int64_t nblocks;
+    int64_t *lineoff, *ptoff, *head;
+    LsVec<2> *totals;
 };
 size_t pb_work_bytes(int64_t nlines) {
     const size_t n = (size_t)std::max<int64_t>(nlines, 1);
-    return 8 * n + 8 * n + 8 * n + PB_HEAD_BYTES + 16 * (size_t)std::max<int64_t>(1, fib::cdiv(nlines, PB_SCAN_TILE));
+    return 8 * n + 8 * n + 8 * n + PB_HEAD_BYTES + sizeof(LsVec<2>) * (size_t)ls_total_slots(nlines);
 }
 PbWork pb_work(void *work, int64_t nlines) {
     const size_t n = (size_t)std::max<int64_t>(nlines, 1);
@@ -363,8 +314,7 @@ PbWork pb_work(void *work, int64_t nlines) {
     w.lineoff = reinterpret_cast<int64_t *>(p + 8 * n);
     w.ptoff = w.lineoff + n;
     w.head = w.ptoff + n;
-    w.totals = w.head + 2;
-    w.nblocks = fib::cdiv(nlines, PB_SCAN_TILE);
+    w.totals = reinterpret_cast<LsVec<2> *>(w.head + 2);
     return w;
 }
 
@@ -414,9 +364,7 @@ int pb_check(const PbRun &r, void *work, size_t work_bytes) {
     FIB_CHECK(r.nseed < ((int64_t)1 << 40) / r.nsub, FIB_ERR_UNSUPPORTED, "too many lines");
     const int64_t nlines = r.nseed * r.nsub;
     FIB_CHECK(fib::cdiv(nlines * 64, PB_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "too many lines");
-    FIB_CHECK(work && (reinterpret_cast<uintptr_t>(work) & 7) == 0, FIB_ERR_INVALID, "work must be an 8-byte aligned device buffer");
-    FIB_CHECK(work_bytes >= pb_work_bytes(nlines), FIB_ERR_INVALID, "work holds %zu bytes, fibd_prob_work_size asks for %zu", work_bytes, pb_work_bytes(nlines));
-    return FIB_OK;
+    return ls_check_work(work, work_bytes, pb_work_bytes(nlines), "fibd_prob_work_size");
 }
 
 PbArgs pb_args(const PbRun &r, const PbWork &w) {
@@ -435,10 +383,7 @@ int pb_count(const PbRun &r, const PbWork &w, hipStream_t st, int64_t *nlines_ou
         fib::ProfScope prof("prob_trace_count", st);
         pb_trace_launch(false, pb_args(r, w), st);
     }
-    if (w.nblocks > 0) hipLaunchKernelGGL(pb_scan_block, dim3((unsigned)w.nblocks), dim3(PB_BLOCK), 0, st, w.counts, nlines, r.len_min, w.totals);
-    hipLaunchKernelGGL(pb_scan_totals, dim3(1), dim3(PB_BLOCK), 0, st, w.totals, w.nblocks, w.head);
-    if (w.nblocks > 0)
-        hipLaunchKernelGGL(pb_scan_apply, dim3((unsigned)w.nblocks), dim3(PB_BLOCK), 0, st, w.counts, nlines, r.len_min, w.totals, w.lineoff, w.ptoff);
+    ls_scan(PbItem{w.counts, r.len_min, w.lineoff, w.ptoff, w.head}, nlines, w.totals, st);
     FIB_HIP(hipGetLastError());
     int64_t head[2] = {0, 0};
     FIB_HIP(hipMemcpyAsync(head, w.head, sizeof head, hipMemcpyDeviceToHost, st));
@@ -492,7 +437,7 @@ extern "C" int fib_prob_plan_create(int device, const float *vertices, int nvert
     FIB_CHECK(nvert >= 1 && nvert <= PB_NVERT_MAX, FIB_ERR_UNSUPPORTED, "1 to %d directions, not %d", PB_NVERT_MAX, nvert);
     FIB_CHECK(cosang_thresh > 0.0f, FIB_ERR_INVALID, "cosang_thresh must be > 0 (an angle below 90 degrees): the cone is the only bend limit");
     fib::DeviceGuard guard;
-    PB_RC(fib::use_device(device));
+    FIB_RC(fib::use_device(device));
     std::unique_ptr<fib_prob_plan> p(new fib_prob_plan());
     p->device = device; p->nvert = nvert; p->nchunk = fib_prob_row_pitch(nvert) / 8; p->cosang = cosang_thresh;
     const size_t half = (size_t)nvert * p->nchunk;
@@ -504,8 +449,8 @@ extern "C" int fib_prob_plan_create(int device, const float *vertices, int nvert
             if (fabsf(c) >= cosang_thresh) bits[(size_t)j * p->nchunk + (i >> 3)] |= (uint8_t)(1u << (i & 7));
             if (c > 0.0f) bits[half + (size_t)j * p->nchunk + (i >> 3)] |= (uint8_t)(1u << (i & 7));
         }
-    PB_RC(p->bits.alloc(2 * half));
-    PB_RC(p->U.alloc((size_t)3 * nvert));
+    FIB_RC(p->bits.alloc(2 * half));
+    FIB_RC(p->U.alloc((size_t)3 * nvert));
     FIB_HIP(hipMemcpy(p->bits.p, bits.data(), 2 * half, hipMemcpyHostToDevice));
     FIB_HIP(hipMemcpy(p->U.p, vertices, sizeof(float) * 3 * nvert, hipMemcpyHostToDevice));
     *plan = p.release();
@@ -532,17 +477,17 @@ extern "C" int fibd_prob_run(const fib_prob_plan *plan, int nx, int ny, int nz, 
     FIB_CHECK(nlines && npoints, FIB_ERR_INVALID, "NULL nlines / npoints");
     *nlines = 0; *npoints = 0;
     const PbRun r{plan, nx, ny, nz, len_min, len_max, nsub, step_size, table, seeds, nseed, sublist, rng_seed};
-    PB_RC(pb_check(r, work, work_bytes));
+    FIB_RC(pb_check(r, work, work_bytes));
     FIB_CHECK(lines_cap >= 0 && points_cap >= 0, FIB_ERR_INVALID, "negative capacity");
     FIB_CHECK((lines_cap == 0 || (npts && seed_index)) && (points_cap == 0 || xyz), FIB_ERR_INVALID, "NULL output buffer");
     FIB_CHECK((reinterpret_cast<uintptr_t>(xyz) & 3) == 0, FIB_ERR_INVALID, "xyz must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const PbWork w = pb_work(work, nseed * nsub);
-    PB_RC(pb_count(r, w, st, nlines, npoints));
+    FIB_RC(pb_count(r, w, st, nlines, npoints));
     if (*nlines > lines_cap || *npoints > points_cap)
         return fib::fail(FIB_ERR_CAPACITY, "fibd_prob_run needs room for %lld lines and %lld points (capacities: %lld, %lld); nothing was written",
                          (long long)*nlines, (long long)*npoints, (long long)lines_cap, (long long)points_cap);
-    PB_RC(pb_emit(r, w, npts, seed_index, xyz, st));
+    FIB_RC(pb_emit(r, w, npts, seed_index, xyz, st));
     FIB_HIP(hipStreamSynchronize(st));
     return FIB_OK;
 } FIB_API_CATCH
@@ -557,9 +502,9 @@ extern "C" int fib_prob_stream(int device, int nx, int ny, int nz, const float *
     FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
     FIB_CHECK(nsub >= 1, FIB_ERR_INVALID, "sublist must hold at least one offset");
     fib::DeviceGuard guard;
-    PB_RC(fib::use_device(device));
+    FIB_RC(fib::use_device(device));
     fib_prob_plan *plan_raw = nullptr;
-    PB_RC(fib_prob_plan_create(device, vertices, nvert, cosang_thresh, &plan_raw));
+    FIB_RC(fib_prob_plan_create(device, vertices, nvert, cosang_thresh, &plan_raw));
     struct PlanGuard { fib_prob_plan *p; ~PlanGuard() { fib_prob_plan_destroy(p); } } pg{plan_raw};
     const int64_t nvox = (int64_t)nx * ny * nz;
     const int pitch = fib_prob_row_pitch(nvert);
@@ -568,15 +513,15 @@ extern "C" int fib_prob_stream(int device, int nx, int ny, int nz, const float *
     fib::DevBuf<float> d_odf;
     fib::DevBuf<uint8_t> d_mask;
     const int64_t chunk = std::min<int64_t>(nvox, (int64_t)1 << 18);
-    PB_RC(d_table.alloc((size_t)nvox * pitch));
-    PB_RC(d_odf.alloc((size_t)chunk * nvert));
-    if (mask) PB_RC(d_mask.alloc((size_t)chunk));
+    FIB_RC(d_table.alloc((size_t)nvox * pitch));
+    FIB_RC(d_odf.alloc((size_t)chunk * nvert));
+    if (mask) FIB_RC(d_mask.alloc((size_t)chunk));
     for (int64_t v0 = 0; v0 < nvox; v0 += chunk) {
         const int64_t n = std::min(chunk, nvox - v0);
         FIB_HIP(hipMemcpy2D(d_odf.p, sizeof(float) * (size_t)n, odf + v0, sizeof(float) * (size_t)nvox, sizeof(float) * (size_t)n, (size_t)nvert,
                             hipMemcpyHostToDevice));
         if (mask) FIB_HIP(hipMemcpy(d_mask.p, mask + v0, (size_t)n, hipMemcpyHostToDevice));
-        PB_RC(fibd_prob_table(d_odf.p, mask ? d_mask.p : nullptr, n, nvert, subtract_min, pmf_thresh, d_table.p + (size_t)v0 * pitch, nullptr));
+        FIB_RC(fibd_prob_table(d_odf.p, mask ? d_mask.p : nullptr, n, nvert, subtract_min, pmf_thresh, d_table.p + (size_t)v0 * pitch, nullptr));
         FIB_HIP(hipStreamSynchronize(nullptr));                // (the chunk buffers are written again)
     }
     d_odf.release(); d_mask.release();
@@ -588,21 +533,21 @@ extern "C" int fib_prob_stream(int device, int nx, int ny, int nz, const float *
     fib::DevBuf<int64_t> d_seeds, d_sidx, d_work;
     fib::DevBuf<float> d_sub, d_xyz;
     fib::DevBuf<int32_t> d_npts;
-    PB_RC(d_seeds.alloc((size_t)nseed));
-    PB_RC(d_sub.alloc((size_t)3 * nsub));
+    FIB_RC(d_seeds.alloc((size_t)nseed));
+    FIB_RC(d_sub.alloc((size_t)3 * nsub));
     if (nseed) FIB_HIP(hipMemcpy(d_seeds.p, seeds.data(), sizeof(int64_t) * (size_t)nseed, hipMemcpyHostToDevice));
     FIB_HIP(hipMemcpy(d_sub.p, sublist, sizeof(float) * 3 * nsub, hipMemcpyHostToDevice));
     const size_t wb = pb_work_bytes(nall);
-    PB_RC(d_work.alloc(wb / 8));
+    FIB_RC(d_work.alloc(wb / 8));
     const PbRun r{plan_raw, nx, ny, nz, len_min, len_max, nsub, step_size, d_table.p, d_seeds.p, nseed, d_sub.p, rng_seed};
-    PB_RC(pb_check(r, d_work.p, wb));
+    FIB_RC(pb_check(r, d_work.p, wb));
     const PbWork w = pb_work(d_work.p, nall);
     int64_t nl = 0, np = 0;
-    PB_RC(pb_count(r, w, nullptr, &nl, &np));
-    PB_RC(d_npts.alloc((size_t)nl));
-    PB_RC(d_sidx.alloc((size_t)nl));
-    PB_RC(d_xyz.alloc((size_t)3 * np));
-    PB_RC(pb_emit(r, w, d_npts.p, d_sidx.p, d_xyz.p, nullptr));
+    FIB_RC(pb_count(r, w, nullptr, &nl, &np));
+    FIB_RC(d_npts.alloc((size_t)nl));
+    FIB_RC(d_sidx.alloc((size_t)nl));
+    FIB_RC(d_xyz.alloc((size_t)3 * np));
+    FIB_RC(pb_emit(r, w, d_npts.p, d_sidx.p, d_xyz.p, nullptr));
     out->npts = (int32_t *)malloc(sizeof(int32_t) * (size_t)std::max<int64_t>(nl, 1));
     out->seed_index = (int64_t *)malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nl, 1));
     out->xyz = (float *)malloc(sizeof(float) * 3 * (size_t)std::max<int64_t>(np, 1));

@@ -4,7 +4,8 @@
 // leave them: xyz float32 [npoints][3] (any 4-byte boundary), npts int32 [nlines].
 //
 // Kernels
-//   tm_scan_block / tm_scan_totals / tm_scan_apply   (tm_lines.inc, shared with tractsel.hip) exclusive int64 scan of npts -> first point of every line; the totals kernel also
+//   ls_block / ls_totals / ls_apply <TmItem>   (line_scan.inc; the Item is in tm_lines.inc, shared with tractsel.hip and bundle.hip)
+//                     exclusive int64 scan of npts -> first point of every line; the totals kernel also
 //                     judges the input (a negative count, or a sum that is not npoints) and publishes the verdict in device memory:
 //                     the kernels behind it read it and add nothing to a refused input (no host round trip)
 //   tm_density_points (mode 0)   a flat pass over the points, no line structure: a wave takes 64 consecutive points, merges runs of
@@ -24,8 +25,6 @@
 
 // the statistics are defined as float64 operations rounded one by one (include/fibers_hip.h): nothing in this file may fuse a*b+c
 #pragma clang fp contract(off)
-
-#define TM_RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
 
 namespace {
 
@@ -251,14 +250,14 @@ extern "C" int fibd_str_density(const float *xyz, const int32_t *npts, int64_t n
     FIB_CHECK(what == FIB_DENSITY_POINTS || what == FIB_DENSITY_LINES || what == FIB_DENSITY_ENDPOINTS, FIB_ERR_INVALID, "unknown density mode %d", mode);
     FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
     FIB_CHECK(density && n_outside_dev, FIB_ERR_INVALID, "NULL argument");
-    TM_RC(tm_check_lines(xyz, npts, nlines, npoints));
+    FIB_RC(tm_check_lines(xyz, npts, nlines, npoints));
     const int64_t nvox = (int64_t)nx * ny * nz;
     FIB_CHECK(what != FIB_DENSITY_LINES || nvox < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "FIB_DENSITY_LINES takes volumes of fewer than 2^31 voxels");
     hipStream_t st = (hipStream_t)stream;
     fib::ProfScope prof(what == FIB_DENSITY_POINTS ? "str_density_points" : what == FIB_DENSITY_LINES ? "str_density_lines" : "str_density_ends", st);
     if (!(mode & FIB_DENSITY_ACCUMULATE)) FIB_HIP(hipMemsetAsync(density, 0, sizeof(uint32_t) * (size_t)nvox, st));
     TmWork w;
-    TM_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, n_outside_dev, st, w));
+    FIB_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, n_outside_dev, st, w));
     if (nlines == 0 || npoints == 0) return FIB_OK;
     if (what == FIB_DENSITY_POINTS)
         hipLaunchKernelGGL(tm_density_points, dim3((unsigned)fib::cdiv(npoints, TM_POINTS_PER_BLOCK)), dim3(TM_BLOCK), 0, st, xyz, npoints, nx, ny, nz,
@@ -302,12 +301,12 @@ extern "C" int fibd_str_stats(const float *xyz, const int32_t *npts, int64_t nli
                               int nscalars, float *props, void *work, size_t work_bytes, void *stream) try {
     FIB_CHECK(volres, FIB_ERR_INVALID, "NULL volres");
     FIB_CHECK(nscalars >= 0 && (nscalars == 0 || npoints == 0 || scalars), FIB_ERR_INVALID, "nscalars columns need a scalars array");
-    TM_RC(tm_check_lines(xyz, npts, nlines, npoints));
+    FIB_RC(tm_check_lines(xyz, npts, nlines, npoints));
     FIB_CHECK(nlines == 0 || props, FIB_ERR_INVALID, "NULL props");
     hipStream_t st = (hipStream_t)stream;
     fib::ProfScope prof("str_stats", st);
     TmWork w;
-    TM_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, nullptr, st, w));
+    FIB_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, nullptr, st, w));
     if (nlines == 0) return FIB_OK;
     hipLaunchKernelGGL(tm_stats<TM_STATS_G>, dim3((unsigned)fib::cdiv(nlines * TM_STATS_G, TM_BLOCK)), dim3(TM_BLOCK), 0, st, xyz, npts, w.off, nlines,
                        volres[0], volres[1], volres[2], scalars, nscalars, w.head, props);

@@ -11,9 +11,9 @@
 //                     gathers the 4-byte ROI word of the point's voxel; an OR butterfly over the group gives {visit, end0, end1}, kept
 //                     in LDS.  Then a lane per line evaluates the rule and writes keep / hits as consecutive elements; kept lines and
 //                     points are summed over the workgroup, then one 64-bit atomic each
-//   ts_scan3_block / ts_scan3_totals / ts_scan3_apply   ONE exclusive scan of three int64 sums per line (points so far, kept lines
-//                     so far, points of kept lines so far) on the pattern of tm_scan_*; the totals kernel judges npts AND the
-//                     capacities and publishes totals, status and the go-ahead in device memory
+//   ls_block / ls_totals / ls_apply <TsItem>   (line_scan.inc) ONE exclusive scan of three int64 sums per line (points so far, kept
+//                     lines so far, points of kept lines so far); the totals kernel judges npts AND the capacities and publishes
+//                     totals, status and the go-ahead in device memory.  <TmItem> (tm_lines.inc): the offset scan of select and connectome
 //   ts_gather_copy<G> G lanes per line; a kept line's points (and scalar rows) are copied as 32-bit words to their output offset
 //   ts_connectome<G>  256 consecutive lines per workgroup and at the end a lane per line: two point loads, two label gathers, the remap
 //                     gathers, the atomics.  G = 1 (no W): that is all, and lanes of a wave that add to the same cell are merged into
@@ -26,11 +26,9 @@
 // a line's length is defined as float64 operations rounded one by one (include/fibers_hip.h): nothing in this file may fuse a*b+c
 #pragma clang fp contract(off)
 
-#define TS_RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
-
 namespace {
 
-#include "tm_lines.inc"                                        // TM_BLOCK, TmHead, tm_voxel, the offset scan (tm_offsets), tm_check_lines
+#include "tm_lines.inc"                                        // TM_BLOCK, TmHead, tm_voxel, the offset scan (tm_offsets), tm_check_lines; line_scan.inc
 
 constexpr int TS_SELECT_G = 16;                                // lanes per line of ts_select (profiles/tract_select/README.md)
 constexpr int TS_GATHER_G = 64;                                // lanes per line of ts_gather_copy: 256 B per round
@@ -128,86 +126,35 @@ __global__ __launch_bounds__(TM_BLOCK) void ts_select(const float *xyz, const in
 struct Ts3 {
     int64_t in, ln, pt;
 };
-__device__ __forceinline__ Ts3 ts3_add(Ts3 a, Ts3 b) { return Ts3{a.in + b.in, a.ln + b.ln, a.pt + b.pt}; }
-__device__ __forceinline__ Ts3 ts3_xor(Ts3 a, int d) { return Ts3{__shfl_xor(a.in, d), __shfl_xor(a.ln, d), __shfl_xor(a.pt, d)}; }
-__device__ __forceinline__ Ts3 ts3_up(Ts3 a, int d) { return Ts3{__shfl_up(a.in, d), __shfl_up(a.ln, d), __shfl_up(a.pt, d)}; }
-__device__ __forceinline__ Ts3 ts3_of(int32_t c, uint8_t k) { return Ts3{c, k ? 1 : 0, k ? c : 0}; }
+static_assert(sizeof(Ts3) == sizeof(LsVec<3>), "off3 and the block totals share the work area's element size");
 
-// block b: the sums of its TM_SCAN_TILE lines (a negative count makes `in` -1 - what the totals kernel refuses)
-__global__ __launch_bounds__(TM_BLOCK) void ts_scan3_block(const int32_t *npts, const uint8_t *keep, int64_t nlines, Ts3 *totals) {
-    __shared__ Ts3 s_sum[TM_BLOCK / 64];
-    __shared__ int s_neg;
-    if (threadIdx.x == 0) s_neg = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * TM_SCAN_TILE + (int64_t)threadIdx.x * TM_SCAN_ITEMS;
-    Ts3 sum{0, 0, 0};
-    bool neg = false;
-    for (int j = 0; j < TM_SCAN_ITEMS; j++)
-        if (base + j < nlines) { const int32_t c = npts[base + j]; neg |= c < 0; sum = ts3_add(sum, ts3_of(c, keep[base + j])); }
-    for (int d = 32; d >= 1; d >>= 1) sum = ts3_add(sum, ts3_xor(sum, d));
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
-    if (neg) s_neg = 1;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Ts3 t{0, 0, 0};
-        for (int w = 0; w < TM_BLOCK / 64; w++) t = ts3_add(t, s_sum[w]);
-        if (s_neg) t.in = -1;
-        totals[blockIdx.x] = t;
+// the scan of (points, kept lines, kept points).  Refused: a negative count, a sum that is not npoints, or more than a capacity holds;
+// counts = {kept lines, kept points, status}, and head->ok is the go-ahead of the copy: valid AND within both capacities.
+struct TsItem {
+    static constexpr int N = 3;
+    const int32_t *npts;
+    const uint8_t *keep;
+    int64_t npoints, cap_lines, cap_points;
+    TmHead *head;
+    Ts3 *off3;
+    int64_t *counts;
+    __device__ LsVec<3> load(int64_t l, bool &bad) const {
+        const int32_t c = npts[l];
+        const bool k = keep[l] != 0;
+        bad |= c < 0;
+        return {c, k ? 1 : 0, k ? c : 0};
     }
-}
-
-// one workgroup: totals -> their exclusive scan (in place); the verdict on npts and on the capacities; counts = {kept lines, kept
-// points, status}.  head->ok is the go-ahead of the copy: valid AND within both capacities.
-__global__ __launch_bounds__(TM_BLOCK) void ts_scan3_totals(Ts3 *totals, int64_t nblocks, int64_t npoints, int64_t cap_lines, int64_t cap_points,
-                                                            TmHead *head, int64_t *counts) {
-    __shared__ Ts3 s_part[TM_BLOCK];
-    __shared__ int s_neg;
-    if (threadIdx.x == 0) s_neg = 0;
-    __syncthreads();
-    const int64_t per = (nblocks + TM_BLOCK - 1) / TM_BLOCK, b0 = threadIdx.x * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
-    Ts3 sum{0, 0, 0};
-    bool neg = false;
-    for (int64_t b = b0; b < b1; b++) { const Ts3 t = totals[b]; neg |= t.in < 0; sum = ts3_add(sum, t); }
-    s_part[threadIdx.x] = sum;
-    if (neg) s_neg = 1;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Ts3 run{0, 0, 0};
-        for (int t = 0; t < TM_BLOCK; t++) { const Ts3 v = s_part[t]; s_part[t] = run; run = ts3_add(run, v); }
-        const bool valid = !s_neg && run.in == npoints;
-        const bool fits = run.ln <= cap_lines && run.pt <= cap_points;
+    __device__ void store(int64_t l, const LsVec<3> &run, const LsVec<3> &) const { off3[l] = Ts3{run.v[0], run.v[1], run.v[2]}; }
+    __device__ void verdict(const LsVec<3> &grand, bool bad) const {
+        const bool valid = !bad && grand.v[0] == npoints;
+        const bool fits = grand.v[1] <= cap_lines && grand.v[2] <= cap_points;
         head->ok = valid && fits ? 1 : 0;
-        counts[0] = valid ? run.ln : -1;
-        counts[1] = valid ? run.pt : -1;
+        counts[0] = valid ? grand.v[1] : -1;
+        counts[1] = valid ? grand.v[2] : -1;
         counts[2] = valid && !fits ? -1 : 0;
     }
-    __syncthreads();
-    if (s_neg) return;                                          // (the offsets of a refused input are never read)
-    Ts3 run = s_part[threadIdx.x];
-    for (int64_t b = b0; b < b1; b++) { const Ts3 t = totals[b]; totals[b] = run; run = ts3_add(run, t); }
-}
-
-__global__ __launch_bounds__(TM_BLOCK) void ts_scan3_apply(const int32_t *npts, const uint8_t *keep, int64_t nlines, const Ts3 *totals, const TmHead *head,
-                                                           Ts3 *off3) {
-    __shared__ Ts3 s_sum[TM_BLOCK / 64];
-    if (!head->ok) return;
-    const int64_t base = (int64_t)blockIdx.x * TM_SCAN_TILE + (int64_t)threadIdx.x * TM_SCAN_ITEMS;
-    Ts3 c[TM_SCAN_ITEMS];
-    Ts3 mine{0, 0, 0};
-    for (int j = 0; j < TM_SCAN_ITEMS; j++) {
-        c[j] = base + j < nlines ? ts3_of(npts[base + j], keep[base + j]) : Ts3{0, 0, 0};
-        mine = ts3_add(mine, c[j]);
-    }
-    Ts3 inc = mine;                                             // inclusive scan over the wave
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) { const Ts3 o = ts3_up(inc, d); if (lane >= d) inc = ts3_add(inc, o); }
-    if (lane == 63) s_sum[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    Ts3 run = totals[blockIdx.x];
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) run = ts3_add(run, s_sum[w]);
-    run = Ts3{run.in + inc.in - mine.in, run.ln + inc.ln - mine.ln, run.pt + inc.pt - mine.pt};
-    for (int j = 0; j < TM_SCAN_ITEMS; j++) if (base + j < nlines) { off3[base + j] = run; run = ts3_add(run, c[j]); }
-}
+    __device__ bool go() const { return head->ok != 0; }
+};
 
 // G lanes per line.  Everything is copied as 32-bit words: NaN payloads and -0.0 arrive as they left.
 template <int G>
@@ -321,15 +268,22 @@ __global__ __launch_bounds__(TM_BLOCK) void ts_connectome(const float *xyz, cons
     if (threadIdx.x == 0) ts_add64(n_lines, counted);
 }
 
-size_t ts_work_bytes(int64_t nlines) {
-    return TM_HEAD_BYTES + sizeof(Ts3) * (size_t)(nlines + 1) + sizeof(Ts3) * (size_t)std::max<int64_t>(1, fib::cdiv(nlines, TM_SCAN_TILE));
+// the work area: head | off3 [nlines + 1] | block totals
+struct TsWork {
+    TmHead *head;
+    Ts3 *off3;
+    LsVec<3> *totals;
+};
+size_t ts_work_bytes(int64_t nlines) { return TM_HEAD_BYTES + sizeof(Ts3) * (size_t)(nlines + 1) + sizeof(Ts3) * (size_t)ls_total_slots(nlines); }
+TsWork ts_work(void *work, int64_t nlines) {
+    TsWork w;
+    w.head = reinterpret_cast<TmHead *>(work);
+    w.off3 = reinterpret_cast<Ts3 *>(reinterpret_cast<char *>(work) + TM_HEAD_BYTES);
+    w.totals = reinterpret_cast<LsVec<3> *>(w.off3 + nlines + 1);
+    return w;
 }
-
 int ts_check_work(void *work, size_t work_bytes, int64_t nlines) {
-    FIB_CHECK(work && (reinterpret_cast<uintptr_t>(work) & 7) == 0, FIB_ERR_INVALID, "work must be an 8-byte aligned device buffer");
-    FIB_CHECK(work_bytes >= ts_work_bytes(nlines), FIB_ERR_INVALID, "work holds %zu bytes, fibd_str_select_work_size asks for %zu", work_bytes,
-              ts_work_bytes(nlines));
-    return FIB_OK;
+    return ls_check_work(work, work_bytes, ts_work_bytes(nlines), "fibd_str_select_work_size");
 }
 
 template <int G>
@@ -376,14 +330,14 @@ extern "C" int fibd_str_select(const float *xyz, const int32_t *npts, int64_t nl
     FIB_CHECK(roibits || !(visit_all | visit_none | end_any | end_both), FIB_ERR_INVALID, "a mask is set but roibits is NULL");
     FIB_CHECK(min_npts >= 0 && max_npts >= 0, FIB_ERR_INVALID, "min_npts and max_npts must not be negative");
     FIB_CHECK(counts && (nlines == 0 || keep), FIB_ERR_INVALID, "NULL argument");
-    TS_RC(tm_check_lines(xyz, npts, nlines, npoints));
-    TS_RC(ts_check_work(work, work_bytes, nlines));
+    FIB_RC(tm_check_lines(xyz, npts, nlines, npoints));
+    FIB_RC(ts_check_work(work, work_bytes, nlines));
     FIB_CHECK(fib::cdiv(nlines, TM_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "too many lines");
     hipStream_t st = (hipStream_t)stream;
     fib::ProfScope prof("str_select", st);
     FIB_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
     TmWork w;
-    TS_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, nullptr, st, w));
+    FIB_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, nullptr, st, w));
     const TsRule rule{(uint32_t)visit_all, (uint32_t)visit_none, (uint32_t)end_any, (uint32_t)end_both, min_npts, max_npts};
     int g = TS_SELECT_G;
 #ifdef FIB_AB_VARIANTS                                          // the lane mapping's A/B partners (tools/tract_select_time.py, diagnostic build only)
@@ -407,23 +361,17 @@ extern "C" int fibd_str_gather(const float *xyz, const int32_t *npts, int64_t nl
     FIB_CHECK(!scalars_out || (nscalars > 0 && (npoints == 0 || scalars)), FIB_ERR_INVALID, "scalars_out needs scalars and nscalars > 0");
     FIB_CHECK(((reinterpret_cast<uintptr_t>(xyz_out) | reinterpret_cast<uintptr_t>(scalars) | reinterpret_cast<uintptr_t>(scalars_out)) & 3) == 0,
               FIB_ERR_INVALID, "points and scalars must be 4-byte aligned");
-    TS_RC(tm_check_lines(xyz, npts, nlines, npoints));
-    TS_RC(ts_check_work(work, work_bytes, nlines));
+    FIB_RC(tm_check_lines(xyz, npts, nlines, npoints));
+    FIB_RC(ts_check_work(work, work_bytes, nlines));
     FIB_CHECK(fib::cdiv(nlines * TS_GATHER_G, TM_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "too many lines");
     hipStream_t st = (hipStream_t)stream;
     fib::ProfScope prof("str_gather", st);
-    TmHead *head = reinterpret_cast<TmHead *>(work);
-    Ts3 *off3 = reinterpret_cast<Ts3 *>(reinterpret_cast<char *>(work) + TM_HEAD_BYTES);
-    Ts3 *totals = off3 + nlines + 1;
-    const int64_t nblocks = fib::cdiv(nlines, TM_SCAN_TILE);
-    if (nblocks > 0) hipLaunchKernelGGL(ts_scan3_block, dim3((unsigned)nblocks), dim3(TM_BLOCK), 0, st, npts, keep, nlines, totals);
-    hipLaunchKernelGGL(ts_scan3_totals, dim3(1), dim3(TM_BLOCK), 0, st, totals, nblocks, npoints, cap_lines, cap_points, head, counts);
-    if (nblocks > 0) {
-        hipLaunchKernelGGL(ts_scan3_apply, dim3((unsigned)nblocks), dim3(TM_BLOCK), 0, st, npts, keep, nlines, totals, head, off3);
+    const TsWork w = ts_work(work, nlines);
+    ls_scan(TsItem{npts, keep, npoints, cap_lines, cap_points, w.head, w.off3, counts}, nlines, w.totals, st);
+    if (nlines > 0)
         hipLaunchKernelGGL(ts_gather_copy<TS_GATHER_G>, dim3((unsigned)fib::cdiv(nlines * TS_GATHER_G, TM_BLOCK)), dim3(TM_BLOCK), 0, st,
-                           reinterpret_cast<const uint32_t *>(xyz), npts, keep, off3, nlines, reinterpret_cast<const uint32_t *>(scalars), nscalars, head,
+                           reinterpret_cast<const uint32_t *>(xyz), npts, keep, w.off3, nlines, reinterpret_cast<const uint32_t *>(scalars), nscalars, w.head,
                            reinterpret_cast<uint32_t *>(xyz_out), npts_out, index_out, reinterpret_cast<uint32_t *>(scalars_out));
-    }
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 } FIB_API_CATCH
@@ -437,8 +385,8 @@ extern "C" int fibd_str_connectome(const float *xyz, const int32_t *npts, int64_
     FIB_CHECK(labels && cmat && n_lines_dev, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(!wmat || volres, FIB_ERR_INVALID, "the lengths of W need volres");
     FIB_CHECK(nremap >= 0 && (nremap == 0 || remap), FIB_ERR_INVALID, "nremap entries need a remap array");
-    TS_RC(tm_check_lines(xyz, npts, nlines, npoints));
-    TS_RC(ts_check_work(work, work_bytes, nlines));
+    FIB_RC(tm_check_lines(xyz, npts, nlines, npoints));
+    FIB_RC(ts_check_work(work, work_bytes, nlines));
     FIB_CHECK(fib::cdiv(nlines, TM_BLOCK) < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "too many lines");
     hipStream_t st = (hipStream_t)stream;
     fib::ProfScope prof(wmat ? "str_connectome_w" : "str_connectome", st);
@@ -448,7 +396,7 @@ extern "C" int fibd_str_connectome(const float *xyz, const int32_t *npts, int64_
         if (wmat) FIB_HIP(hipMemsetAsync(wmat, 0, sizeof(double) * cells, st));
     }
     TmWork w;
-    TS_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, n_lines_dev, st, w));      // (*n_lines_dev = 0, or -1 for a refused input)
+    FIB_RC(tm_offsets(npts, nlines, npoints, work, work_bytes, n_lines_dev, st, w));      // (*n_lines_dev = 0, or -1 for a refused input)
     if (nlines == 0) return FIB_OK;
     const float none[3] = {1.0f, 1.0f, 1.0f};
     const float *res = wmat ? volres : none;

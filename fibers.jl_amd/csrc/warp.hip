@@ -154,11 +154,9 @@ XfmMat wp_mat(const float m[16]) {
 
 }  // namespace
 
-#define WP_RC(x) do { int _rc = (x); if (_rc != FIB_OK) return _rc; } while (0)
-
 extern "C" int fibd_warp_pack(const float *disp, int nx, int ny, int nz, void *packed, void *stream) try {
     FIB_CHECK(disp, FIB_ERR_INVALID, "NULL argument");
-    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_RC(wp_field_check(packed, nx, ny, nz));
     FIB_CHECK((reinterpret_cast<uintptr_t>(disp) & 3) == 0, FIB_ERR_INVALID, "the field must be 4-byte aligned");
     const int64_t nvox = (int64_t)nx * ny * nz;
     FIB_CHECK(wp_disjoint(disp, 12ull * (uint64_t)nvox, packed, 16ull * (uint64_t)nvox), FIB_ERR_INVALID, "disp and packed must not overlap");
@@ -172,7 +170,7 @@ extern "C" int fibd_warp_pack(const float *disp, int nx, int ny, int nz, void *p
 
 extern "C" int fibd_warp_points(const void *packed, int nx, int ny, int nz, const float to_ras[16], const float to_field[16], const float from_ras[16],
                                 const float *xyz, float *out, int64_t npoints, void *stream) try {
-    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_RC(wp_field_check(packed, nx, ny, nz));
     FIB_CHECK(to_ras && to_field && from_ras, FIB_ERR_INVALID, "NULL matrix");
     FIB_CHECK(npoints >= 0, FIB_ERR_INVALID, "npoints must not be negative");
     if (npoints == 0) return FIB_OK;
@@ -195,7 +193,7 @@ extern "C" int fibd_warp_points(const void *packed, int nx, int ny, int nz, cons
 extern "C" int fibd_warp_volume(const void *packed, int nx, int ny, int nz, const float to_ras[16], const float to_field[16], const float from_ras[16],
                                 const void *vol, int nxi, int nyi, int nzi, int nframes, int interp, int32_t outside_bits, void *out, int nxo, int nyo,
                                 int nzo, void *stream) try {
-    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_RC(wp_field_check(packed, nx, ny, nz));
     FIB_CHECK(to_ras && to_field && from_ras && vol && out, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nxi > 0 && nyi > 0 && nzi > 0 && nxo > 0 && nyo > 0 && nzo > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
     FIB_CHECK(interp == FIB_VOL_NEAREST || interp == FIB_VOL_TRILINEAR, FIB_ERR_INVALID, "unknown interpolation %d", interp);
@@ -225,7 +223,7 @@ extern "C" int fibd_warp_volume(const void *packed, int nx, int ny, int nz, cons
 
 extern "C" int fibd_warp_invert(const void *packed, int nx, int ny, int nz, const float out_to_ras[16], const float ras_to_field[16], int niter,
                                 float *inv, float *err, int nxo, int nyo, int nzo, void *stream) try {
-    WP_RC(wp_field_check(packed, nx, ny, nz));
+    FIB_RC(wp_field_check(packed, nx, ny, nz));
     FIB_CHECK(out_to_ras && ras_to_field && inv, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(niter >= 0, FIB_ERR_INVALID, "niter must not be negative");
     FIB_CHECK(nxo > 0 && nyo > 0 && nzo > 0, FIB_ERR_INVALID, "the output dimensions must be positive");
