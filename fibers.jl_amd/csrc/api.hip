@@ -13,9 +13,11 @@
 //   * plans (the reference's work structs) are cached per device, keyed by the tables they were built from.
 // The voxel fits share their argument handling (fit_call) and their per-worker body (fit_run); what a form keeps is its own checks, its
 // rows, its plan and the layout of a chunk on the device.
-// The tractogram forms (fib_str_*) run on one device and copy chunk after chunk with blocking copies: each takes a TmLease (the worker,
-// its lock, the device, the buffer set); the five that take lines of any length walk them with tm_walk_lines, in the chunks that
-// fibh::next_line_chunk cuts (host_tier.h), and keep a body per chunk.
+// Every other host form but fib_xfm_apply runs on one device with blocking copies, under a DevLease (the worker, its lock, the device).
+// The tractogram forms (fib_str_*) take a TmLease, which adds the worker's buffer set; the five that take lines of any length walk them with
+// tm_walk_lines, in the chunks that fibh::next_line_chunk cuts (host_tier.h), and keep a body per chunk.
+// The volume, warp, structure-tensor, RUMBA and peak-finder forms keep nothing between calls: their buffers are local.  The two frame
+// resamplers share frame_checks / frame_chunks, the peak finders find_peaks_host; the sizes taken from the free memory are host_tier.h's.
 #include <sched.h>
 #include <sys/mman.h>
 
@@ -386,6 +388,24 @@ int for_each_worker(const std::vector<Worker> &ws, const std::function<int(int, 
     return FIB_OK;
 }
 
+// One call of a single-device, blocking-copy host form on its worker.  take() finds the worker of `device` (workers_for checks the index
+// and makes the device current) and waits for its lock; the caller's device comes back when the lease goes.  FIB_DEVICE_ALL names no
+// worker: refused under the form's sentence all_msg, or (NULL) answered as the index -1 that it is.  What is declared after the lease
+// (buffers, plans) goes while it holds the lock.
+struct DevLease {
+    fib::DeviceGuard guard;
+    Worker wk;
+    std::unique_lock<std::mutex> lk;
+    int take(int device, const char *all_msg) {
+        if (device == FIB_DEVICE_ALL) return all_msg ? fib::fail(FIB_ERR_UNSUPPORTED, "%s", all_msg) : fib::use_device(device);
+        std::vector<Worker> ws;
+        RC(workers_for(device, ws));
+        wk = ws[0];
+        lk = std::unique_lock<std::mutex>(wk->mu);
+        return FIB_OK;
+    }
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -591,8 +611,8 @@ extern "C" int fib_st_eigen(int device, const float *const S[6], int64_t nvox, f
     FIB_CHECK(S && eigvec && eigval, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nvox > 0, FIB_ERR_INVALID, "nvox must be positive");
     for (int k = 0; k < 6; k++) FIB_CHECK(S[k] != nullptr, FIB_ERR_INVALID, "NULL structure tensor volume %d", k);
-    fib::DeviceGuard guard;
-    RC(fib::use_device(device));
+    DevLease lease;
+    RC(lease.take(device, nullptr));
     fib::DevBuf<float> d_in, d_out;
     RC(d_in.alloc((size_t)nvox * 6));
     RC(d_out.alloc((size_t)nvox * 12));
@@ -636,19 +656,17 @@ extern "C" int fib_st_recon(int device, const float *vol, int nx, int ny, int nz
     FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "st_recon runs on one device (FIB_DEVICE_ALL is not supported)");
     int halo = 0;
     RC(fib_st_recon_halo(sigma, rho, &halo));
-    fib::DeviceGuard guard;
-    RC(fib::use_device(device));
+    DevLease lease;
+    RC(lease.take(device, nullptr));                       // (FIB_DEVICE_ALL: refused above, before the radii)
     const size_t plane = (size_t)nx * ny;
     int nzs = 0;
-    if (const char *e = fib::env("FIBERS_ST_RECON_SLAB")) nzs = atoi(e);
-    if (nzs <= 0) {                     // half the free memory: per output plane 4 (vol) + 12 (gradients) + 48 (outputs) bytes a voxel
+    if (const char *e = fib::env("FIBERS_ST_RECON_SLAB")) nzs = std::min(atoi(e), nz);
+    if (nzs <= 0) {
         size_t fr = 0, tot = 0;
         FIB_HIP(hipMemGetInfo(&fr, &tot));
-        const double planes = (double)(fr / 2) / (double)plane - 16.0 * 2 * halo;   // less the halos of vol and of the gradients
-        nzs = planes / 64.0 >= nz ? nz : (int)(planes / 64.0);
+        nzs = fibh::planes_per_slab(fr, plane, halo, nz);
         FIB_CHECK(nzs >= 1, FIB_ERR_NOMEM, "st_recon: one %d x %d plane with its halo does not fit in device memory", nx, ny);
     }
-    if (nzs > nz) nzs = nz;
     size_t work_bytes = 0;
     RC(fibd_st_recon_work_size(nx, ny, nzs, sigma, rho, &work_bytes));
     const int nzin_max = std::min(nz, nzs + 2 * halo);
@@ -671,41 +689,52 @@ extern "C" int fib_st_recon(int device, const float *vol, int nx, int ny, int nz
     return FIB_OK;
 } FIB_API_CATCH
 
-// vol_xform host form: chunks of whole frames (they are independent); per chunk upload, one launch, download.  Copies block on the NULL
-// stream, so the read-back comes behind the kernel.  The buffers are local: nothing is kept between calls.
-extern "C" int fib_vol_xform(int device, const float out2in[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp,
-                             int32_t outside_bits, void *out, int nxo, int nyo, int nzo) try {
-    FIB_CHECK(out2in && vol && out, FIB_ERR_INVALID, "NULL argument");
+// The frame resampler of fib_vol_xform and fib_warp_volume, in the two pieces a form puts around its lease: frame_checks after its own
+// checks; frame_chunks once what stays resident is on the device.  Frames are independent: chunks of whole frames, per chunk upload,
+// launch(d_in, d_out, nf) = the form's fibd_* call, download.  Copies block on the NULL stream: the read-back comes behind the kernel.
+namespace {
+int frame_checks(const void *vol, int nxi, int nyi, int nzi, int nframes, int interp, const void *out, int nxo, int nyo, int nzo) {
     FIB_CHECK(nxi > 0 && nyi > 0 && nzi > 0 && nxo > 0 && nyo > 0 && nzo > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
     FIB_CHECK(interp == FIB_VOL_NEAREST || interp == FIB_VOL_TRILINEAR, FIB_ERR_INVALID, "unknown interpolation %d", interp);
     const size_t nvi = (size_t)nxi * nyi * nzi, nvo = (size_t)nxo * nyo * nzo;
     const uintptr_t ai = reinterpret_cast<uintptr_t>(vol), ao = reinterpret_cast<uintptr_t>(out);
     FIB_CHECK(ai + 4 * nvi * nframes <= ao || ao + 4 * nvo * nframes <= ai, FIB_ERR_INVALID, "vol and out must not overlap");
-    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "vol_xform runs on one device (FIB_DEVICE_ALL is not supported)");
-    fib::DeviceGuard guard;
-    RC(fib::use_device(device));
+    return FIB_OK;
+}
+// frames of nvi voxels in, nvo out; a chunk holds env_name's count of them, else what fits in half the memory free now (or nomem_msg)
+template <typename Launch>
+int frame_chunks(const void *vol, size_t nvi, void *out, size_t nvo, int nframes, const char *env_name, const char *nomem_msg, Launch launch) {
     int nfc = 0;
-    if (const char *e = fib::env("FIBERS_VOL_XFORM_FRAMES")) nfc = atoi(e);
-    if (nfc <= 0) {                     // half the free memory: 4 (in) + 4 (out) bytes per voxel of a frame pair
+    if (const char *e = fib::env(env_name)) nfc = std::min(atoi(e), nframes);
+    if (nfc <= 0) {
         size_t fr = 0, tot = 0;
         FIB_HIP(hipMemGetInfo(&fr, &tot));
-        const size_t fit = (fr / 2) / (4 * (nvi + nvo));
-        FIB_CHECK(fit >= 1, FIB_ERR_NOMEM, "vol_xform: one input and one output frame do not fit in device memory");
-        nfc = (int)std::min<size_t>(fit, (size_t)nframes);
+        nfc = fibh::frames_per_chunk(fr, nvi, nvo, nframes);
+        FIB_CHECK(nfc >= 1, FIB_ERR_NOMEM, "%s", nomem_msg);
     }
-    if (nfc > nframes) nfc = nframes;
     fib::DevBuf<uint32_t> d_in, d_out;
     RC(d_in.alloc(nvi * nfc));
     RC(d_out.alloc(nvo * nfc));
-    const uint32_t *src = static_cast<const uint32_t *>(vol);
-    uint32_t *dst = static_cast<uint32_t *>(out);
     for (int f0 = 0; f0 < nframes; f0 += nfc) {
         const int nf = std::min(nfc, nframes - f0);
-        RC(h2d(d_in.p, src + nvi * f0, sizeof(uint32_t) * nvi * nf));
-        RC(fibd_vol_xform(out2in, d_in.p, nxi, nyi, nzi, nf, interp, outside_bits, d_out.p, nxo, nyo, nzo, nullptr));
-        RC(d2h(dst + nvo * f0, d_out.p, sizeof(uint32_t) * nvo * nf));
+        RC(h2d(d_in.p, static_cast<const uint32_t *>(vol) + nvi * f0, sizeof(uint32_t) * nvi * nf));
+        RC(launch(d_in.p, d_out.p, nf));
+        RC(d2h(static_cast<uint32_t *>(out) + nvo * f0, d_out.p, sizeof(uint32_t) * nvo * nf));
     }
     return FIB_OK;
+}
+}  // namespace
+
+extern "C" int fib_vol_xform(int device, const float out2in[16], const void *vol, int nxi, int nyi, int nzi, int nframes, int interp,
+                             int32_t outside_bits, void *out, int nxo, int nyo, int nzo) try {
+    FIB_CHECK(out2in && vol && out, FIB_ERR_INVALID, "NULL argument");
+    RC(frame_checks(vol, nxi, nyi, nzi, nframes, interp, out, nxo, nyo, nzo));
+    DevLease lease;
+    RC(lease.take(device, "vol_xform runs on one device (FIB_DEVICE_ALL is not supported)"));
+    return frame_chunks(vol, (size_t)nxi * nyi * nzi, out, (size_t)nxo * nyo * nzo, nframes, "FIBERS_VOL_XFORM_FRAMES",
+                        "vol_xform: one input and one output frame do not fit in device memory", [&](const uint32_t *d_in, uint32_t *d_out, int nf) {
+                            return fibd_vol_xform(out2in, d_in, nxi, nyi, nzi, nf, interp, outside_bits, d_out, nxo, nyo, nzo, nullptr);
+                        });
 } FIB_API_CATCH
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -713,10 +742,8 @@ extern "C" int fib_vol_xform(int device, const float out2in[16], const void *vol
 // or the frames travel in chunks.  Copies block on the NULL stream, so a read-back comes behind its kernel.  The buffers are local.
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {
-// the field of a host call on the current device: upload, pack, and the planar copy goes back to the driver
+// the field of a host call (checked by the form) on the current device: upload, pack, and the planar copy goes back to the driver
 int warp_field_upload(const float *disp, int nx, int ny, int nz, fib::DevBuf<float> &packed) {
-    FIB_CHECK(disp, FIB_ERR_INVALID, "NULL field");
-    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "the field's dimensions must be positive");
     const size_t nvox = (size_t)nx * ny * nz;
     fib::DevBuf<float> planar;
     RC(planar.alloc(3 * nvox));
@@ -735,9 +762,8 @@ extern "C" int fib_warp_points(int device, const float *disp, int nx, int ny, in
     FIB_CHECK(npoints >= 0, FIB_ERR_INVALID, "npoints must not be negative");
     FIB_CHECK(npoints == 0 || (xyz && out), FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(xyz == out || xyz + 3 * npoints <= out || out + 3 * npoints <= xyz, FIB_ERR_INVALID, "xyz and out must be the same array or not overlap");
-    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "warp_points runs on one device (FIB_DEVICE_ALL is not supported)");
-    fib::DeviceGuard guard;
-    RC(fib::use_device(device));
+    DevLease lease;
+    RC(lease.take(device, "warp_points runs on one device (FIB_DEVICE_ALL is not supported)"));
     if (npoints == 0) return FIB_OK;
     int64_t chunk = (int64_t)1 << 22;                       // 48 MB of points per chunk
     if (const char *e = fib::env("FIBERS_WARP_POINTS")) { const long long v = atoll(e); if (v > 0) chunk = v; }
@@ -758,39 +784,18 @@ extern "C" int fib_warp_volume(int device, const float *disp, int nx, int ny, in
                                void *out, int nxo, int nyo, int nzo) try {
     FIB_CHECK(disp && to_ras && to_field && from_ras && vol && out, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "the field's dimensions must be positive");
-    FIB_CHECK(nxi > 0 && nyi > 0 && nzi > 0 && nxo > 0 && nyo > 0 && nzo > 0 && nframes > 0, FIB_ERR_INVALID, "volume dimensions and nframes must be positive");
-    FIB_CHECK(interp == FIB_VOL_NEAREST || interp == FIB_VOL_TRILINEAR, FIB_ERR_INVALID, "unknown interpolation %d", interp);
-    const size_t nvi = (size_t)nxi * nyi * nzi, nvo = (size_t)nxo * nyo * nzo, nvf = (size_t)nx * ny * nz;
-    const uintptr_t ai = reinterpret_cast<uintptr_t>(vol), ao = reinterpret_cast<uintptr_t>(out);
-    FIB_CHECK(ai + 4 * nvi * nframes <= ao || ao + 4 * nvo * nframes <= ai, FIB_ERR_INVALID, "vol and out must not overlap");
-    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "warp_volume runs on one device (FIB_DEVICE_ALL is not supported)");
-    fib::DeviceGuard guard;
-    RC(fib::use_device(device));
+    RC(frame_checks(vol, nxi, nyi, nzi, nframes, interp, out, nxo, nyo, nzo));
+    DevLease lease;
+    RC(lease.take(device, "warp_volume runs on one device (FIB_DEVICE_ALL is not supported)"));
     fib::DevBuf<float> d_field;
-    RC(warp_field_upload(disp, nx, ny, nz, d_field));
-    int nfc = 0;
-    if (const char *e = fib::env("FIBERS_WARP_FRAMES")) nfc = atoi(e);
-    if (nfc <= 0) {                     // half the free memory (the field is resident already): 4 (in) + 4 (out) bytes per voxel of a frame pair
-        size_t fr = 0, tot = 0;
-        FIB_HIP(hipMemGetInfo(&fr, &tot));
-        const size_t fit = (fr / 2) / (4 * (nvi + nvo));
-        FIB_CHECK(fit >= 1, FIB_ERR_NOMEM, "warp_volume: the field (%zu voxels), one input and one output frame do not fit in device memory", nvf);
-        nfc = (int)std::min<size_t>(fit, (size_t)nframes);
-    }
-    if (nfc > nframes) nfc = nframes;
-    fib::DevBuf<uint32_t> d_in, d_out;
-    RC(d_in.alloc(nvi * nfc));
-    RC(d_out.alloc(nvo * nfc));
-    const uint32_t *src = static_cast<const uint32_t *>(vol);
-    uint32_t *dst = static_cast<uint32_t *>(out);
-    for (int f0 = 0; f0 < nframes; f0 += nfc) {
-        const int nf = std::min(nfc, nframes - f0);
-        RC(h2d(d_in.p, src + nvi * f0, sizeof(uint32_t) * nvi * nf));
-        RC(fibd_warp_volume(d_field.p, nx, ny, nz, to_ras, to_field, from_ras, d_in.p, nxi, nyi, nzi, nf, interp, outside_bits, d_out.p, nxo, nyo,
-                            nzo, nullptr));
-        RC(d2h(dst + nvo * f0, d_out.p, sizeof(uint32_t) * nvo * nf));
-    }
-    return FIB_OK;
+    RC(warp_field_upload(disp, nx, ny, nz, d_field));       // (resident before frame_chunks looks at the free memory)
+    char nomem[128];
+    snprintf(nomem, sizeof nomem, "warp_volume: the field (%zu voxels), one input and one output frame do not fit in device memory", (size_t)nx * ny * nz);
+    return frame_chunks(vol, (size_t)nxi * nyi * nzi, out, (size_t)nxo * nyo * nzo, nframes, "FIBERS_WARP_FRAMES", nomem,
+                        [&](const uint32_t *d_in, uint32_t *d_out, int nf) {
+                            return fibd_warp_volume(d_field.p, nx, ny, nz, to_ras, to_field, from_ras, d_in, nxi, nyi, nzi, nf, interp, outside_bits,
+                                                    d_out, nxo, nyo, nzo, nullptr);
+                        });
 } FIB_API_CATCH
 
 extern "C" int fib_warp_invert(int device, const float *disp, int nx, int ny, int nz, const float out_to_ras[16], const float ras_to_field[16],
@@ -798,9 +803,8 @@ extern "C" int fib_warp_invert(int device, const float *disp, int nx, int ny, in
     FIB_CHECK(disp && out_to_ras && ras_to_field && inv, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nx > 0 && ny > 0 && nz > 0 && nxo > 0 && nyo > 0 && nzo > 0, FIB_ERR_INVALID, "the field's and the output's dimensions must be positive");
     FIB_CHECK(niter >= 0, FIB_ERR_INVALID, "niter must not be negative");
-    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "warp_invert runs on one device (FIB_DEVICE_ALL is not supported)");
-    fib::DeviceGuard guard;
-    RC(fib::use_device(device));
+    DevLease lease;
+    RC(lease.take(device, "warp_invert runs on one device (FIB_DEVICE_ALL is not supported)"));
     const size_t nvo = (size_t)nxo * nyo * nzo;
     fib::DevBuf<float> d_field, d_out;
     RC(warp_field_upload(disp, nx, ny, nz, d_field));
@@ -830,20 +834,12 @@ int tm_host_check(const int32_t *npts, int64_t nlines, int64_t npoints) {
     return FIB_OK;
 }
 
-// One call of a tractogram host form on its worker.  take() refuses FIB_DEVICE_ALL, finds the worker of `device`, waits for its lock,
-// makes the device current (the caller's comes back when the lease goes) and hands out the worker's buffer set, b.
-struct TmLease {
-    Worker wk;
-    std::unique_lock<std::mutex> lk;
-    std::unique_ptr<fib::DeviceGuard> guard;
+// One call of a tractogram host form on its worker: a DevLease, and the worker's buffer set, b.  (init: the forms use nothing it makes,
+// but DevState::trim releases the set only on a worker that is ready.)
+struct TmLease : DevLease {
     DevState::TractMapBufs *b = nullptr;
     int take(int device) {
-        FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "the tract maps, the selection and the connectome run on one device (FIB_DEVICE_ALL is not supported)");
-        std::vector<Worker> ws;
-        RC(workers_for(device, ws));
-        wk = ws[0];
-        lk = std::unique_lock<std::mutex>(wk->mu);
-        guard.reset(new fib::DeviceGuard());
+        RC(DevLease::take(device, "the tract maps, the selection and the connectome run on one device (FIB_DEVICE_ALL is not supported)"));
         RC(wk->init(copy_threads(1)));
         if (!wk->tm) wk->tm.reset(new DevState::TractMapBufs());
         b = wk->tm.get();
@@ -1284,11 +1280,11 @@ extern "C" int fib_rumba_rec(int device, const float *dwi, int nx, int ny, int n
                              int use_tv, const fib_rumba_out *out, float *snr_mean, float *snr_std) try {
     FIB_CHECK(dwi && mask && out, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
-    fib::DeviceGuard guard;
-    fib_rumba_plan *p = nullptr;
+    DevLease lease;
+    fib_rumba_plan *p = nullptr;                             // the constructor's refusals come first, the device index among them (FIB_DEVICE_ALL too)
     RC(fib_rumba_plan_create(device, bval, bvec, nvol, verts, nverts, lam_para, lam_perp, lam_csf, lam_gm, &p));
     struct PlanDel { fib_rumba_plan *p; ~PlanDel() { fib_rumba_plan_destroy(p); } } del{p};
-    FIB_HIP(hipSetDevice(device));
+    RC(lease.take(device, nullptr));
     const int64_t nvox = (int64_t)nx * ny * nz;
     const int nvert = nverts / 2;
     std::vector<uint8_t> m8;
@@ -1319,58 +1315,48 @@ extern "C" int fib_rumba_rec(int device, const float *dwi, int nx, int ny, int n
 // nvox values, like MRI.vol[:,:,:,v]); isort_top [3 x nvox] planar, 0-based first-half vertex rows, -1 where the
 // tessellation has fewer vertices; nvalid [nvox] = count(odf_peak .> 0) (gqi.jl:200).
 namespace {
-// the peak finders take only the folded neighbour table from a plan: a GQI plan of one dummy frame, destroyed with this object
-struct PeaksPlan {
-    fib_odf_plan *p = nullptr;
-    int create(int device, const float *verts, int nverts, const int32_t *faces, int nfaces) {
-        const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};
-        return fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, &p);
-    }
-    ~PeaksPlan() { fib_odf_plan_destroy(p); }
-};
+// fib_find_peaks / fib_find_peaks_work: the checks, the plan (its constructor refuses what is left, the device index among them), the lease,
+// the ODFs up, call(plan, d_odf, d_a, d_b, d_nv) = the form's fibd_* call, the outputs back.  a and, for a form that has_b, b are the
+// form's own outputs, of wa and wb elements per voxel.
+template <typename A, typename B, typename Call>
+int find_peaks_host(int device, const float *odf, int64_t nvox, const float *verts, int nverts, const int32_t *faces, int nfaces, A *a, int wa,
+                    bool has_b, B *b, int wb, int32_t *nvalid, Call call) {
+    FIB_CHECK(odf && verts && faces && a && (b || !has_b) && nvalid, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nvox > 0 && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid sizes");
+    DevLease lease;
+    const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};   // (only the folded neighbour table is used: a GQI plan of one dummy frame)
+    fib_odf_plan *plan = nullptr;
+    RC(fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, &plan));
+    struct PlanDel { fib_odf_plan *p; ~PlanDel() { fib_odf_plan_destroy(p); } } del{plan};
+    RC(lease.take(device, nullptr));
+    const size_t nv = (size_t)nvox, n = nv * (nverts / 2);
+    fib::DevBuf<float> d_odf;
+    fib::DevBuf<A> d_a;
+    fib::DevBuf<B> d_b;
+    fib::DevBuf<int32_t> d_nv;
+    RC(d_odf.alloc(n)); RC(d_a.alloc(nv * wa)); RC(d_nv.alloc(nv));
+    if (has_b) RC(d_b.alloc(nv * wb));
+    RC(h2d(d_odf.p, odf, n * sizeof(float)));
+    RC(call(plan, d_odf.p, d_a.p, d_b.p, d_nv.p));
+    FIB_HIP(hipDeviceSynchronize());
+    RC(d2h(a, d_a.p, nv * wa * sizeof(A)));
+    if (has_b) RC(d2h(b, d_b.p, nv * wb * sizeof(B)));
+    return d2h(nvalid, d_nv.p, nv * sizeof(int32_t));
+}
 }  // namespace
 
 extern "C" int fib_find_peaks(int device, const float *odf, int64_t nvox, const float *verts, int nverts,
                               const int32_t *faces, int nfaces, int32_t *isort_top, int32_t *nvalid) try {
-    FIB_CHECK(odf && verts && faces && isort_top && nvalid, FIB_ERR_INVALID, "NULL argument");
-    FIB_CHECK(nvox > 0 && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid sizes");
-    fib::DeviceGuard guard;
-    PeaksPlan plan;
-    RC(plan.create(device, verts, nverts, faces, nfaces));
-    FIB_HIP(hipSetDevice(device));
-    const int nvert = nverts / 2;
-    fib::DevBuf<float> d_odf;
-    fib::DevBuf<int32_t> d_top, d_nv;
-    RC(d_odf.alloc((size_t)nvox * nvert));
-    RC(d_top.alloc((size_t)nvox * 3));
-    RC(d_nv.alloc((size_t)nvox));
-    RC(h2d(d_odf.p, odf, (size_t)nvox * nvert * sizeof(float)));
-    RC(fibd_find_peaks(plan.p, d_odf.p, nvox, d_top.p, d_nv.p, nullptr));
-    FIB_HIP(hipDeviceSynchronize());
-    RC(d2h(isort_top, d_top.p, (size_t)nvox * 3 * sizeof(int32_t)));
-    RC(d2h(nvalid, d_nv.p, (size_t)nvox * sizeof(int32_t)));
-    return FIB_OK;
+    return find_peaks_host(device, odf, nvox, verts, nverts, faces, nfaces, isort_top, 3, false, (int32_t *)nullptr, 0, nvalid,
+                           [&](const fib_odf_plan *plan, const float *d_odf, int32_t *d_top, int32_t *, int32_t *d_nv) {
+                               return fibd_find_peaks(plan, d_odf, nvox, d_top, d_nv, nullptr); });
 } FIB_API_CATCH
 
 extern "C" int fib_find_peaks_work(int device, const float *odf, int64_t nvox, const float *verts, int nverts,
                                    const int32_t *faces, int nfaces, float *odf_peak, int32_t *isort, int32_t *nvalid) try {
-    FIB_CHECK(odf && verts && faces && odf_peak && isort && nvalid, FIB_ERR_INVALID, "NULL argument");
-    FIB_CHECK(nvox > 0 && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid sizes");
-    fib::DeviceGuard guard;
-    PeaksPlan plan;
-    RC(plan.create(device, verts, nverts, faces, nfaces));
-    FIB_HIP(hipSetDevice(device));
-    const size_t n = (size_t)nvox * (nverts / 2);
-    fib::DevBuf<float> d_odf, d_pk;
-    fib::DevBuf<int32_t> d_is, d_nv;
-    RC(d_odf.alloc(n)); RC(d_pk.alloc(n)); RC(d_is.alloc(n)); RC(d_nv.alloc((size_t)nvox));
-    RC(h2d(d_odf.p, odf, n * sizeof(float)));
-    RC(fibd_find_peaks_work(plan.p, d_odf.p, nvox, d_pk.p, d_is.p, d_nv.p, nullptr));
-    FIB_HIP(hipDeviceSynchronize());
-    RC(d2h(odf_peak, d_pk.p, n * sizeof(float)));
-    RC(d2h(isort, d_is.p, n * sizeof(int32_t)));
-    RC(d2h(nvalid, d_nv.p, (size_t)nvox * sizeof(int32_t)));
-    return FIB_OK;
+    return find_peaks_host(device, odf, nvox, verts, nverts, faces, nfaces, odf_peak, nverts / 2, true, isort, nverts / 2, nvalid,
+                           [&](const fib_odf_plan *plan, const float *d_odf, float *d_pk, int32_t *d_is, int32_t *d_nv) {
+                               return fibd_find_peaks_work(plan, d_odf, nvox, d_pk, d_is, d_nv, nullptr); });
 } FIB_API_CATCH
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -7,8 +7,8 @@
 // the chunk schedule are read by tools, not only by reviewers.
 //
 // Contents: mask element-type conversion; CPU binding; the copy pool; LiveMap (the runs of a mask) + the piece list of a chunk;
-// row gather / scatter; chunk size, chunk schedule, slabs; the line-chunk schedule of the tractogram host forms;
-// run_chunks<Dev> -- the three-stage pipeline over voxel chunks.
+// row gather / scatter; chunk size, chunk schedule, slabs; the line-chunk schedule of the tractogram host forms; the chunk sizes
+// the frame resamplers and fib_st_recon take from the free device memory; run_chunks<Dev> -- the three-stage pipeline over voxel chunks.
 #pragma once
 #include <emmintrin.h>
 #include <sched.h>
@@ -294,6 +294,18 @@ inline LineChunk next_line_chunk(const int32_t *npts, int64_t nlines, int64_t l0
     int64_t l = l0, n = 0;
     while (l < nlines && (l == l0 || (l - l0 < max_lines && n + npts[l] <= max_points))) n += npts[l++];
     return {l, n};
+}
+
+// ---- chunk sizes from half the device's free memory; 0: not even one fits (the form refuses with FIB_ERR_NOMEM) -------------------
+// fib_vol_xform / fib_warp_volume: whole frames per chunk, at most nframes; 4 (in) + 4 (out) bytes per voxel of a frame pair
+inline int frames_per_chunk(size_t free_bytes, size_t nvi, size_t nvo, int nframes) {
+    return (int)std::min<size_t>((free_bytes / 2) / (4 * (nvi + nvo)), (size_t)nframes);
+}
+// fib_st_recon: output planes per z-slab, at most nz.  Per voxel of a plane: 4 (vol) + 12 (gradients) + 48 (outputs) = 64 bytes an
+// output plane, and 16 for each of the 2 * halo planes that vol and the gradients reach beyond the slab
+inline int planes_per_slab(size_t free_bytes, size_t plane, int halo, int nz) {
+    const double planes = ((double)(free_bytes / 2) / (double)plane - 16.0 * 2 * halo) / 64.0;
+    return planes >= nz ? nz : (planes >= 1.0 ? (int)planes : 0);
 }
 
 // ---- the chunk pipeline ----------------------------------------------------------------------------------------------------

@@ -237,6 +237,45 @@ static void units() {
                 }
             }
     }
+    // frames per chunk of fib_vol_xform / fib_warp_volume: (free / 2) / (4 * (nvi + nvo)) whole frames, at most nframes.  The free bytes
+    // are built from the count they must give: 2 * per * k holds exactly k frame pairs of per = 4 * (nvi + nvo) bytes each, and as many
+    // bytes short of the next pair as there can be (2 * per - 1) change nothing.
+    for (const auto &v : {std::pair<size_t, size_t>{105, 216}, {1, 1}, {2744000, 6902752}, {(size_t)1 << 32, ((size_t)1 << 31) + 5}}) {
+        const size_t per = 4 * (v.first + v.second);
+        CHECK(per / 4 == v.first + v.second);                                              // (no wrap in the test's own arithmetic)
+        const int n = 9;
+        CHECK(frames_per_chunk(0, v.first, v.second, n) == 0 && frames_per_chunk(2 * per - 1, v.first, v.second, n) == 0);     // nothing fits
+        CHECK(frames_per_chunk(2 * per, v.first, v.second, n) == 1 && frames_per_chunk(4 * per - 1, v.first, v.second, n) == 1);   // exactly one
+        CHECK(frames_per_chunk(2 * per * (n - 1), v.first, v.second, n) == n - 1);
+        CHECK(frames_per_chunk(2 * per * n - 1, v.first, v.second, n) == n - 1 && frames_per_chunk(2 * per * n, v.first, v.second, n) == n);   // exactly n
+        CHECK(frames_per_chunk(2 * per * (n + 1), v.first, v.second, n) == n && frames_per_chunk(2 * per * 1000, v.first, v.second, n) == n);  // clamped
+        CHECK(frames_per_chunk(2 * per * 1000, v.first, v.second, 1) == 1);
+    }
+    // 2^32 + 2^31 + 5 voxels a frame pair: 4 * that is 25 769 803 796 bytes; wrapped to 32 bits it would be 20, and 2^36 free bytes would
+    // hold 2^36 / 2 / 20 frames instead of floor(2^35 / 25 769 803 796) = 1
+    CHECK(frames_per_chunk((size_t)1 << 36, (size_t)1 << 32, ((size_t)1 << 31) + 5, 1000) == 1);
+    // planes per slab of fib_st_recon: ((free / 2) / plane - 32 * halo) / 64 output planes, at most nz: a voxel column of the slab costs
+    // 64 bytes per output plane and 16 for each of its 2 * halo halo planes.  free = 2 * plane * (64 * k + 32 * halo) holds exactly k.
+    for (size_t plane : {(size_t)1, (size_t)120, (size_t)140 * 140, (size_t)1 << 33})                     // (2^33 voxels a plane: no wrap)
+        for (int halo : {0, 1, 5, 17}) {
+            const int nz = 11;
+            const auto bytes = [&](size_t k) { return 2 * plane * (64 * k + 32 * (size_t)halo); };
+            CHECK(bytes(1000) / plane / 2 == 64000 + 32 * (size_t)halo);
+            CHECK(planes_per_slab(0, plane, halo, nz) == 0 && planes_per_slab(bytes(1) - 2, plane, halo, nz) == 0);   // nothing fits
+            CHECK(planes_per_slab(bytes(0), plane, halo, nz) == 0);                         // the halo eats the whole budget ..
+            if (halo) CHECK(planes_per_slab(bytes(0) / 2, plane, halo, nz) == 0);           // .. or more than that (a negative count)
+            CHECK(planes_per_slab(bytes(1), plane, halo, nz) == 1 && planes_per_slab(bytes(2) - 2, plane, halo, nz) == 1);   // exactly one
+            CHECK(planes_per_slab(bytes(nz - 1), plane, halo, nz) == nz - 1);
+            CHECK(planes_per_slab(bytes(nz) - 2, plane, halo, nz) == nz - 1 && planes_per_slab(bytes(nz), plane, halo, nz) == nz);   // exactly nz
+            CHECK(planes_per_slab(bytes(nz + 1), plane, halo, nz) == nz && planes_per_slab(bytes(5000), plane, halo, nz) == nz);    // clamped
+            CHECK(planes_per_slab(bytes(5000), plane, halo, 1) == 1);
+        }
+    // the same in doubles for a size that is no power of two: 192 GB free, 2048 x 2048 planes, halo 7: (96e9 / 4194304 - 224) / 64 = 354.1..
+    {
+        const double want = ((double)((size_t)192000000000 / 2) / 4194304.0 - 224.0) / 64.0;
+        CHECK(want > 354.0 && want < 355.0);
+        CHECK(planes_per_slab((size_t)192000000000, (size_t)2048 * 2048, 7, 4000) == 354 && planes_per_slab((size_t)192000000000, (size_t)2048 * 2048, 7, 300) == 300);
+    }
 }
 
 int main() {
