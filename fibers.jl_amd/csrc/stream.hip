@@ -14,7 +14,8 @@
 // lines evicted to HBM.)  Worst-case rows are affordable with 288 GB: 1 M lines x 284 slots x 12 B = 3.4 GB.
 // A scan over the per-line counts gives every kept line its offset; the pack kernel transposes 16-slot x
 // 64-line blocks through LDS and emits the reference's point order [fwd_N .. fwd_1, bwd_1 .. bwd_M]
-// (prepend!/append!, stream.jl:652) in 48-byte pieces.
+// (prepend!/append!, stream.jl:652) in 48-byte pieces.  The pack side -- the pack kernels and the fused trace kernel's pack tail --
+// is stream_pack.inc, included below behind the scan kernels.
 //
 // Arithmetic.  No a*b+c contraction anywhere in this file: positions are compared after round-to-nearest-
 // even (stream.jl:514) so one ulp moves a line to another voxel; with contraction off every operation is
@@ -258,8 +259,7 @@ __device__ __forceinline__ int lcm_match_edge(int dx, int dy, int dz, int sd0, i
 // (three more) -- include/fibers_hip.h, fib_stream_params.interp.
 // WIDE: 64-bit voxel indices and gather offsets, for orientation fields of 2^28 vectors (4 GiB) or more -- the microscopy
 // regime's whole-slide sections (stream.jl:83,147-172); chosen at launch, bit-identical to the 32-bit form on small fields.
-struct FuseLds;   // (defined with the pack kernels below)
-template <int NVEC> __device__ void fused_pack_block(const TraceArgs &a, int64_t b, int64_t li, bool live, int npts, int nf, int gap);
+template <int NVEC> __device__ void fused_pack_block(const TraceArgs &a, int64_t b, int64_t li, bool live, int npts, int nf, int gap);   // (stream_pack.inc)
 
 // [rk] The stages of RK2 / RK4 probe the SAME register cell cache as the final evaluation (NVEC == 1): the positions a line visits --
 // pos + h/2, pos + h/2, pos + h, nxt, then the next step's -- advance along the line, so the stages reload the cell where the Euler
@@ -834,409 +834,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_totals_kernel(Pair *block_tot, in
 }
 
 #include "xfm_apply.inc"
-
-struct PackArgs {
-    const float *scratch;
-    const int32_t *npts, *nfwd;
-    const Pair *excl, *block_off;
-    int32_t *out_npts;
-    int64_t *out_seed;
-    float *out_xyz;
-    int64_t nlines, line0, out_line0, out_pt0;
-    int stride, nslots, len_min, scratch_plain;
-    int64_t lines_cap, points_cap;   // capped: a line whose place lies beyond the caller's buffers is dropped (fibd_stream_run reports the need)
-    int capped;
-    int trk;                    // 1: out_xyz is a .trk body: [Int32 npts, npts x 3 Float32 ((xyz+.5)*voxel_size)] per line
-    float vs[3];
-    // LCM runs (the tile kernel; not with trk): the method-difference flag of a point rides in the sign bit of its x (stream.jl:666) -- the pack
-    // strips it and, if flags != NULL, writes it out as one byte per point ([r5] a second pass over the packed points did this: 3.0 of
-    // the 17 ms of the 2048^2 benchmark section)
-    int lcm;
-    uint8_t *out_flags;
-    XfmMat xf;                  // the pack kernels' XF variant (fibd_stream_pack_trk_xfm): vox2vox applied before the .trk epilogue
-};
-
-// One wave per scratch tile (16 lines), four independent waves per workgroup: no workgroup barriers.  A chunk = 16 slots of
-// the tile = 3 KiB of contiguous scratch: three 16-byte loads per lane, parked in a wave-private LDS tile (rows padded
-// to 52 dwords), then written out line by line: 16 lanes per line, one point each -> a wave instruction emits 4 runs
-// of 192 contiguous bytes.  The next chunk's loads fly during the write-out.  Forward slots are reversed on the way out,
-// backward slots follow (stream.jl:652).
-constexpr int PK_LINES = SCR_TILE, PK_SLOTS = 16, PK_ROW = 52, PK_WAVES = 4;
-static_assert(PK_LINES == 16, "the pack kernel maps 16 lanes to the 16 lines of a tile");
-// XF (with a.trk): str_xform's xfm_apply (trk.jl:345, util.jl:401-420) on every point before the .trk epilogue; XF = false is the
-// kernel fibd_stream_pack / fibd_stream_pack_trk have always run
-template <bool XF = false>
-__global__ __launch_bounds__(PK_WAVES * 64) void stream_pack_kernel(const PackArgs a) {
-    __shared__ __attribute__((aligned(16))) float tile[PK_WAVES][2][PK_SLOTS * PK_ROW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t tix = (int64_t)blockIdx.x * PK_WAVES + wave;   // scratch tile of this wave
-    const int64_t line0 = tix * PK_LINES;
-    if (line0 >= a.nlines) return;
-    // lanes 0..15: the tile's lines
-    int nf = 0, nb = 0, bs = 0;
-    int64_t p0 = 0;
-    {
-        const int64_t li = line0 + (lane & 15);
-        if (lane < PK_LINES && li < a.nlines) {
-            const int n = a.npts[li];
-            if (n >= a.len_min) {                               // stream.jl:769
-                const int nfr = a.nfwd[li];
-                nf = nfr & 0x3fffffff; nb = n - nf; bs = nf + (nfr >> 30);
-                const Pair e = a.excl[li], bo = a.block_off[li / SCAN_B];
-                const int64_t pt = a.out_pt0 + e.pts + bo.pts, l0 = a.out_line0 + e.lines + bo.lines;
-                if (a.capped && (l0 >= a.lines_cap || pt + n > a.points_cap)) { nf = 0; nb = 0; bs = 0; }   // no room: dropped
-                else if (a.trk) {
-                    reinterpret_cast<int32_t *>(a.out_xyz)[l0 + 3 * pt] = n;          // write(io, Int32(npts)), trk.jl:472
-                    p0 = pt * 3 + l0 + 1;
-                } else {
-                    a.out_npts[l0] = n; a.out_seed[l0] = a.line0 + li;
-                    p0 = pt * 3;
-                }
-            }
-        }
-    }
-    int cnt = nb > 0 ? bs + nb : nf;                            // slots of the tile that hold points of kept lines
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) cnt = max(cnt, __shfl_xor(cnt, o));
-    cnt = __builtin_amdgcn_readfirstlane(cnt);
-    const int nch = (cnt + PK_SLOTS - 1) / PK_SLOTS;
-    // write-out mapping: lane = (line group lg, point pt); line tl = lg + 4 j
-    const int lg = lane >> 4, pt = lane & 15;
-    int wnf[4], wnb[4], wbs[4];
-    int64_t wp0[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        wnf[j] = __shfl(nf, lg + 4 * j); wnb[j] = __shfl(nb, lg + 4 * j); wbs[j] = __shfl(bs, lg + 4 * j);
-        wp0[j] = ((int64_t)__shfl((int)(p0 >> 32), lg + 4 * j) << 32) | (uint32_t)__shfl((int)(uint32_t)p0, lg + 4 * j);
-    }
-    const float4 *tbase = reinterpret_cast<const float4 *>(a.scratch + scratch_line_base(line0, a.nslots));
-    float4 v[3];
-    auto fetch = [&](int c) {                                   // 16 slots of the tile
-        const int s0 = c * PK_SLOTS;
-        const int live = cnt - s0;                              // live slots of the chunk
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int f = lane + 64 * i;                        // float4 index within the chunk: slot f / 12 (rows of 16 lines: one contiguous 3-KiB run)
-            v[i] = (f < live * 12) ? tbase[(int64_t)(s0 + f / 12) * (SCR_SLOT_FLOATS / 4) + f % 12] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    if (nch > 0) fetch(0);
-    for (int c = 0; c < nch; c++) {
-        float *T = tile[wave][c & 1];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int f = lane + 64 * i;
-            *reinterpret_cast<float4 *>(T + (f / 12) * PK_ROW + (f % 12) * 4) = v[i];
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (c + 1 < nch) fetch(c + 1);                          // next chunk's loads fly during the write-out
-        const int sidx = c * PK_SLOTS + pt;                     // the slot = the loop trip that emitted the point
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int tl = lg + 4 * j;
-            int64_t p = -1;                                     // forward points reversed, backward points behind them (stream.jl:652)
-            if (sidx < wnf[j]) p = (int64_t)(wnf[j] - 1 - sidx);
-            else if (sidx >= wbs[j] && sidx - wbs[j] < wnb[j]) p = (int64_t)wnf[j] + (sidx - wbs[j]);
-            if (p >= 0) {
-                struct P3 { float x, y, z; };
-                const float *t = T + pt * PK_ROW + tl * 3;
-                float *d = a.out_xyz + wp0[j] + p * 3;
-                if (XF) {                                       // xfm_apply, then the epilogue below (always .trk)
-                    const float3 r = xfm_point(a.xf, t[0], t[1], t[2]);
-                    *reinterpret_cast<P3 *>(d) =
-                        P3{(float)(((double)r.x + 0.5) * (double)a.vs[0]), (float)(((double)r.y + 0.5) * (double)a.vs[1]),
-                           (float)(((double)r.z + 0.5) * (double)a.vs[2])};
-                } else if (a.trk)                               // T.((xyz .+ .5) .* voxel_size), Float64 arithmetic (trk.jl:475-476)
-                    *reinterpret_cast<P3 *>(d) =
-                        P3{(float)(((double)t[0] + 0.5) * (double)a.vs[0]), (float)(((double)t[1] + 0.5) * (double)a.vs[1]),
-                           (float)(((double)t[2] + 0.5) * (double)a.vs[2])};
-                else
-                    *reinterpret_cast<P3 *>(d) = P3{t[0], t[1], t[2]};
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// Default pack kernel: one workgroup per scratch tile.  The kept lines of a tile occupy ONE contiguous range of the packed
-// output (or of the .trk body), so the workgroup assembles that whole range in LDS -- thread = (slot, line) reads its
-// 12-byte point from the contiguous tile (coalesced) and drops it at its final position -- and then streams the range
-// out with 16-byte stores aligned to the output address (fill-like: 12-byte stores in 192-byte runs reached 2.7 TB/s,
-// aligned 16-byte stores of whole lines reach twice that).  LDS = 16 (len_max + 2) points; longer lines than the LDS
-// holds go through stream_pack_kernel above.
-template <int TL, int SPC, bool XF = false>   // TL lines per tile (a whole fraction of a scratch row); SPC slots per pass of the workgroup's
-                                              // SPC x TL threads; XF: as stream_pack_kernel's
-__global__ __launch_bounds__(SPC * TL) void stream_pack_tile_kernel(const PackArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float obuf[];
-    __shared__ int s_nf[TL], s_nb[TL], s_bs[TL], s_o[TL];   // per line: forward / backward counts (0 if dropped), first backward slot, offset in obuf
-    __shared__ int s_cnt[4];                                        // slots in use, -, range length (floats), misalignment
-    __shared__ int64_t s_g0;                                        // first float of the range in out_xyz
-    const int tid = threadIdx.x;
-    const int64_t line0 = (int64_t)blockIdx.x * TL;
-    if (tid < 64) {
-        const int64_t li = line0 + tid;
-        int nf = 0, nb = 0, bs = 0, n = 0;
-        int64_t p0 = 0, gs = INT64_MAX, ge = -1;
-        if (tid < TL && li < a.nlines) {
-            n = a.npts[li];
-            if (n >= a.len_min) {                               // stream.jl:769
-                const int nfr = a.nfwd[li];
-                nf = nfr & 0x3fffffff; nb = n - nf; bs = nf + (nfr >> 30);
-                const Pair e = a.excl[li], bo = a.block_off[li / SCAN_B];
-                const int64_t pt = a.out_pt0 + e.pts + bo.pts, l0 = a.out_line0 + e.lines + bo.lines;
-                if (a.capped && (l0 >= a.lines_cap || pt + n > a.points_cap)) { n = 0; nf = 0; nb = 0; bs = 0; }   // no room: dropped
-                else {
-                    if (a.trk) { p0 = pt * 3 + l0 + 1; gs = p0 - 1; }   // the Int32 point count precedes the points (trk.jl:472)
-                    else { a.out_npts[l0] = n; a.out_seed[l0] = a.line0 + li; p0 = pt * 3; gs = p0; }
-                    ge = p0 + (int64_t)n * 3;
-                }
-            } else n = 0;
-        }
-        int mf = nb > 0 ? bs + nb : nf;                        // slots of the tile that hold points of kept lines
-        int64_t g0 = gs, g1 = ge;
-#pragma unroll
-        for (int o = 1; o < TL; o <<= 1) {
-            mf = max(mf, __shfl_xor(mf, o));
-            const int64_t og0 = ((int64_t)__shfl_xor((int)(g0 >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)g0, o);
-            const int64_t og1 = ((int64_t)__shfl_xor((int)(g1 >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)g1, o);
-            g0 = og0 < g0 ? og0 : g0; g1 = og1 > g1 ? og1 : g1;
-        }
-        const int mis = g1 >= 0 ? (int)((reinterpret_cast<uintptr_t>(a.out_xyz + g0) >> 2) & 3) : 0;
-        if (tid < TL) {
-            s_nf[tid] = nf; s_nb[tid] = nb; s_bs[tid] = bs; s_o[tid] = n > 0 ? (int)(p0 - g0) + mis : 0;
-            if (a.trk && n > 0) obuf[(int)(p0 - g0) + mis - 1] = __int_as_float(n);
-        }
-        if (tid == 0) { s_cnt[0] = mf; s_cnt[1] = 0; s_cnt[2] = g1 >= 0 ? (int)(g1 - g0) : 0; s_cnt[3] = mis; s_g0 = g0; }
-    }
-    __syncthreads();
-    const int cnt = s_cnt[0], len = s_cnt[2], mis = s_cnt[3];
-    if (len == 0) return;
-    uint8_t *fbuf = reinterpret_cast<uint8_t *>(obuf + ((size_t)TL * a.stride * 3 + TL + 8));   // [TL * stride] flags of the range's points (LCM runs)
-    const int nch = (cnt + SPC - 1) / SPC;
-    const int l = tid % TL, sl = tid / TL;                      // thread = (line, slot within the SPC-slot chunk)
-    const int nf = s_nf[l], nb = s_nb[l], bs = s_bs[l], o = s_o[l];
-    struct P3 { float x, y, z; };
-    const P3 *tbase = reinterpret_cast<const P3 *>(a.scratch + scratch_line_base(line0, a.nslots)) + l + sl * SCR_ROW;
-    for (int c0 = 0; c0 < nch; c0 += 4) {
-        P3 v[4];
-        int pos[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int c = c0 + i;
-            const int t = c * SPC + sl;                         // the slot = the loop trip that emitted the point
-            pos[i] = -1;                                        // forward points reversed, backward points behind them (stream.jl:652)
-            if (c < nch) {
-                if (t < nf) pos[i] = nf - 1 - t;
-                else if (t >= bs && t - bs < nb) pos[i] = nf + (t - bs);
-            }
-            if (pos[i] >= 0) {                                  // read once: non-temporal (the orientation field should keep the Infinity Cache)
-                const float *src = reinterpret_cast<const float *>(tbase + (int64_t)c * (SPC * SCR_ROW));
-#ifdef FIB_AB_VARIANTS
-                if (a.scratch_plain) { f32x3_t q; asm volatile("global_load_dwordx3 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(q) : "v"(src) : "memory"); v[i] = P3{q[0], q[1], q[2]}; }
-                else
-#endif
-                v[i] = P3{__builtin_nontemporal_load(src), __builtin_nontemporal_load(src + 1), __builtin_nontemporal_load(src + 2)};
-            } else v[i] = P3{0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            if (pos[i] < 0) continue;
-            float *d = obuf + o + pos[i] * 3;
-            if (XF) {                                           // xfm_apply, then the epilogue below (always .trk)
-                const float3 r = xfm_point(a.xf, v[i].x, v[i].y, v[i].z);
-                d[0] = (float)(((double)r.x + 0.5) * (double)a.vs[0]); d[1] = (float)(((double)r.y + 0.5) * (double)a.vs[1]);
-                d[2] = (float)(((double)r.z + 0.5) * (double)a.vs[2]);
-            } else if (a.trk) {                                        // T.((xyz .+ .5) .* voxel_size), Float64 arithmetic (trk.jl:475-476)
-                d[0] = (float)(((double)v[i].x + 0.5) * (double)a.vs[0]); d[1] = (float)(((double)v[i].y + 0.5) * (double)a.vs[1]);
-                d[2] = (float)(((double)v[i].z + 0.5) * (double)a.vs[2]);
-            } else if (a.lcm) {
-                d[0] = fabsf(v[i].x); d[1] = v[i].y; d[2] = v[i].z;
-                fbuf[(o - mis) / 3 + pos[i]] = (uint8_t)(__float_as_uint(v[i].x) >> 31);
-            } else { d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; }
-        }
-    }
-    __syncthreads();
-    if (a.lcm && a.out_flags) {                                 // the range's flags: one byte per point, in the order of the points
-        uint8_t *fg = a.out_flags + s_g0 / 3;
-        for (int k = tid; k < len / 3; k += SPC * TL) fg[k] = fbuf[k];
-    }
-    // obuf[mis .. mis + len) -> out_xyz[g0 .. g0 + len): obuf[4k..4k+3] lands on a 16-byte aligned address
-    float *gbase = a.out_xyz + s_g0 - mis;
-    const int nq = (mis + len + 3) >> 2;
-    for (int k = tid; k < nq; k += SPC * TL) {
-        const float4 q = reinterpret_cast<const float4 *>(obuf)[k];
-        if (4 * k >= mis && 4 * k + 4 <= mis + len) {            // written once, read by nobody on the device: non-temporal
-            typedef float nt4_t __attribute__((ext_vector_type(4)));
-            const nt4_t qn = {q.x, q.y, q.z, q.w};
-            __builtin_nontemporal_store(qn, reinterpret_cast<nt4_t *>(gbase + 4 * k));
-        }
-        else {
-            const float e[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 0; j < 4; j++) if (4 * k + j >= mis && 4 * k + j < mis + len) gbase[4 * k + j] = e[j];
-        }
-    }
-}
-
-// ---- [r5] FUSED: the block that traced 512 lines packs them (fibd_stream_run) --------------------------------------
-// After its trace loop a block knows its kept lines and points; a decoupled look-back over the blocks' totals (one 64-bit granule per
-// block: status | kept lines | points -- the data is the flag, agent-scope atomics, no fence; blocks are dispatched in order, so every
-// block a block waits for is running or done) gives it its place in the packed output, and it then packs its own 32 scratch tiles
-// exactly as stream_pack_tile_kernel does: the tile's kept lines are ONE contiguous output range, assembled in LDS and streamed out with
-// aligned 16-byte non-temporal stores.  No scan kernels, no pack launch; the scratch is still written and read back (512 lines x 144
-// slots x 12 B = 885 KB per block: it does not stay on chip), but blocks that pack overlap with blocks that still trace.
-constexpr unsigned long long FG_PTS_MASK = (1ull << 36) - 1ull, FG_VAL_MASK = (1ull << 62) - 1ull;
-__device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int off) {
-    return ((unsigned long long)(unsigned)__shfl_up((int)(v >> 32), off) << 32) | (unsigned)__shfl_up((int)(unsigned)v, off);
-}
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int off) {
-    return ((unsigned long long)(unsigned)__shfl_xor((int)(v >> 32), off) << 32) | (unsigned)__shfl_xor((int)(unsigned)v, off);
-}
-typedef __attribute__((address_space(1))) unsigned long long fib_gu64s;
-template <int NVEC>
-__device__ void fused_pack_block(const TraceArgs &a, int64_t b, int64_t li, bool live, int npts, int nf, int gap) {
-    extern __shared__ __attribute__((aligned(16))) float f_obuf[];              // [FT * stride * 3 + slack]: a tile's output range
-    __shared__ uint16_t f_nf[FUSED_BLOCK], f_nb[FUSED_BLOCK], f_bs[FUSED_BLOCK];                        // (16 bits: a tile of such lines fits the LDS, so len_max < 2^15)
-    __shared__ int64_t f_p0[FUSED_BLOCK];
-    constexpr int FB = FUSED_BLOCK, FW = FB / 64;
-    __shared__ unsigned long long f_wsum[FW], f_base;
-    constexpr int FT = FUSED_TILE, FSL = FB / FT;                               // lines per tile; slots a pass of the 512 threads covers
-    __shared__ int t_nf[FT], t_nb[FT], t_bs[FT], t_o[FT], t_cnt[4];
-    __shared__ int64_t t_g0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __builtin_amdgcn_s_setprio(3);                                               // the pack's few memory instructions go ahead of the neighbours' trace loops
-    const bool keep = live && npts >= a.len_min;                                 // stream.jl:769
-    const unsigned long long v = keep ? ((1ull << 36) | (unsigned long long)npts) : 0ull;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const unsigned long long o = shfl_up_u64(inc, off); if (lane >= off) inc += o; }
-    if (lane == 63) f_wsum[wave] = inc;
-    __syncthreads();
-    unsigned long long wbase = 0ull;
-    for (int w = 0; w < wave; w++) wbase += f_wsum[w];
-    unsigned long long agg = 0ull;
-    for (int w = 0; w < FW; w++) agg += f_wsum[w];
-    if (wave == 0) {
-        if (lane == 0)
-            __hip_atomic_store((fib_gu64s *)(a.fstate + b), ((b == 0 ? 2ull : 1ull) << 62) | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned long long excl = 0ull;
-        int64_t j0 = b - 1;                                                     // lane l looks at block j0 - l
-        while (j0 >= 0) {
-            const int64_t j = j0 - lane;
-            unsigned long long g = 2ull << 62;                                   // (before block 0: an inclusive prefix of nothing)
-            if (j >= 0) {
-                for (;;) {
-                    g = __hip_atomic_load((fib_gu64s *)(a.fstate + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((g >> 62) != 0ull) break;
-                    __builtin_amdgcn_s_sleep(4);                                 // (a predecessor still tracing: do not take its issue slots)
-                }
-            }
-            const unsigned long long pre = __ballot((g >> 62) == 2ull);          // nearest predecessor that knows its inclusive prefix
-            const int first = pre ? __builtin_ctzll(pre) : 63;
-            unsigned long long c = lane <= first ? (g & FG_VAL_MASK) : 0ull;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) c += shfl_xor_u64(c, off);
-            excl += c;
-            if (pre) break;
-            j0 -= 64;
-        }
-        if (lane == 0) {
-            if (b > 0) __hip_atomic_store((fib_gu64s *)(a.fstate + b), (2ull << 62) | (excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            f_base = excl;
-            if (b == (int64_t)gridDim.x - 1) {
-                const unsigned long long tot = excl + agg;
-                a.ftotal->pts = (int64_t)(tot & FG_PTS_MASK); a.ftotal->lines = (int64_t)(tot >> 36);
-                if (a.fcounts) { a.fcounts[0] = (int64_t)(tot >> 36); a.fcounts[1] = (int64_t)(tot & FG_PTS_MASK); }
-            }
-        }
-    }
-    __syncthreads();
-    {
-        const unsigned long long ex = f_base + wbase + inc - v;                  // kept lines / points before this line
-        const int64_t l0 = (int64_t)(ex >> 36), pt = (int64_t)(ex & FG_PTS_MASK);
-        int mnf = 0, mnb = 0, mbs = 0;
-        int64_t p0 = 0;
-        if (keep && !(l0 >= a.lines_cap || pt + npts > a.points_cap)) {          // (no room: dropped; the totals say what was needed)
-            a.out_npts[l0] = npts; a.out_seed[l0] = a.line0 + li;
-            mnf = nf; mnb = npts - nf; mbs = nf + gap; p0 = pt * 3;
-        }
-        f_nf[tid] = (uint16_t)mnf; f_nb[tid] = (uint16_t)mnb; f_bs[tid] = (uint16_t)mbs; f_p0[tid] = p0;
-    }
-    __syncthreads();
-    struct P3 { float x, y, z; };
-    // per tile: [one wave: the tile's summary] barrier [gather the tile's points into its output range in LDS] barrier [stream the range out]
-    // barrier.  (Preparing the next tile's summary beside the stream-out -- two barriers per tile -- measured SLOWER: C4 1.18 against 1.05 ms.)
-    for (int t = 0; t < FB / FT; t++) {
-        if (tid < 64) {                                                         // the tile's summary (as stream_pack_tile_kernel)
-            int tnf = 0, tnb = 0, tbs = 0, n = 0;
-            int64_t p0 = 0, gs = INT64_MAX, ge = -1;
-            if (tid < FT) {
-                tnf = f_nf[t * FT + tid]; tnb = f_nb[t * FT + tid]; tbs = f_bs[t * FT + tid]; n = tnf + tnb; p0 = f_p0[t * FT + tid];
-                if (n > 0) { gs = p0; ge = p0 + (int64_t)n * 3; }
-            }
-            int mf = tnb > 0 ? tbs + tnb : tnf;
-            int64_t g0 = gs, g1 = ge;
-#pragma unroll
-            for (int o = 1; o < FT; o <<= 1) {
-                mf = max(mf, __shfl_xor(mf, o));
-                const int64_t og0 = (int64_t)shfl_xor_u64((unsigned long long)g0, o), og1 = (int64_t)shfl_xor_u64((unsigned long long)g1, o);
-                g0 = og0 < g0 ? og0 : g0; g1 = og1 > g1 ? og1 : g1;
-            }
-            const int mis = g1 >= 0 ? (int)((reinterpret_cast<uintptr_t>(a.out_xyz + g0) >> 2) & 3) : 0;
-            if (tid < FT) { t_nf[tid] = tnf; t_nb[tid] = tnb; t_bs[tid] = tbs; t_o[tid] = n > 0 ? (int)(p0 - g0) + mis : 0; }
-            if (tid == 0) { t_cnt[0] = mf; t_cnt[1] = g1 >= 0 ? (int)(g1 - g0) : 0; t_cnt[2] = mis; t_g0 = g0; }
-        }
-        __syncthreads();
-        const int cnt = t_cnt[0], len = t_cnt[1], mis = t_cnt[2];
-        if (len > 0) {
-            const int nch = (cnt + FSL - 1) / FSL;
-            const int l = tid % FT, sl = tid / FT;                              // thread = (line, slot within the pass): a pass reads FB x 12 contiguous bytes
-            const int lnf = t_nf[l], lnb = t_nb[l], lbs = t_bs[l], lo = t_o[l];
-            const P3 *tbase = reinterpret_cast<const P3 *>(a.scratch + scratch_line_base((b * (FB / FT) + t) * FT, a.nslots)) + l + sl * SCR_ROW;
-            for (int c0 = 0; c0 < nch; c0 += 4) {
-                P3 q[4];
-                int pos[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int c = c0 + i, tt = c * FSL + sl;
-                    pos[i] = -1;                                                // forward points reversed, backward points behind them (stream.jl:652)
-                    if (c < nch) {
-                        if (tt < lnf) pos[i] = lnf - 1 - tt;
-                        else if (tt >= lbs && tt - lbs < lnb) pos[i] = lnf + (tt - lbs);
-                    }
-                    if (pos[i] >= 0) {
-                        const float *src = reinterpret_cast<const float *>(tbase + (int64_t)c * (FSL * SCR_ROW));
-                        q[i] = P3{__builtin_nontemporal_load(src), __builtin_nontemporal_load(src + 1), __builtin_nontemporal_load(src + 2)};
-                    } else q[i] = P3{0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    if (pos[i] < 0) continue;
-                    float *d = f_obuf + lo + pos[i] * 3;
-                    d[0] = q[i].x; d[1] = q[i].y; d[2] = q[i].z;
-                }
-            }
-        }
-        __syncthreads();
-        if (len > 0) {
-            float *gbase = a.out_xyz + t_g0 - mis;
-            const int nq = (mis + len + 3) >> 2;
-            for (int k = tid; k < nq; k += FB) {
-                const float4 qq = reinterpret_cast<const float4 *>(f_obuf)[k];
-                if (4 * k >= mis && 4 * k + 4 <= mis + len) {
-                    typedef float nt4_t __attribute__((ext_vector_type(4)));
-                    const nt4_t qn = {qq.x, qq.y, qq.z, qq.w};
-                    __builtin_nontemporal_store(qn, reinterpret_cast<nt4_t *>(gbase + 4 * k));
-                } else {
-                    const float e[4] = {qq.x, qq.y, qq.z, qq.w};
-#pragma unroll
-                    for (int jj = 0; jj < 4; jj++) if (4 * k + jj >= mis && 4 * k + jj < mis + len) gbase[4 * k + jj] = e[jj];
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
+#include "stream_pack.inc"   // PackArgs, the tile packer, stream_pack_kernel / stream_pack_tile_kernel, fused_pack_block
 
 __global__ __launch_bounds__(256) void copy_i32_kernel(const int32_t *src, int32_t *dst, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -201,16 +201,19 @@ def _lcm_case(n, seed, nvec=2):
     return ovs, mask, lcms
 
 
-@pytest.mark.parametrize("nvec,seed,thr", [(2, 7, 0.2), (3, 8, 0.099), (1, 9, 0.5)])
-def test_stream_lcm_guided_exact(fj, orc, nvec, seed, thr):
+@pytest.mark.parametrize("nvec,seed,thr,len_max", [(2, 7, 0.2, 40), (3, 8, 0.099, 40), (1, 9, 0.5, 40), (2, 7, 0.2, 3000)],
+                         ids=["2-7-0.2", "3-8-0.099", "1-9-0.5", "2-7-0.2-len_max3000"])
+def test_stream_lcm_guided_exact(fj, orc, nvec, seed, thr, len_max):
     """LCM-guided tracking (stream.jl:380-495, 526-538) with the counter-based uniform stream of the ABI: bit-exact
-    lines and per-point method-difference flags against the oracle; a different rng_seed gives different lines"""
+    lines and per-point method-difference flags against the oracle; a different rng_seed gives different lines.
+    len_max 3000: a tile of such lines does not fit the LDS, so the pack is the wave-per-tile kernel and the flags
+    are stripped by a pass of their own (fibd_stream_pack_flags)"""
     n = 24
     ovs, mask, lcms = _lcm_case(n, seed, nvec)
     sub = np.array([[0.1, -0.2, 0.0], [0.3, 0.25, 0.0], [-0.35, 0.05, 0.0]], np.float32)
     tr = fj.stream([fj.MRI(o) for o in ovs], mask=fj.MRI(mask), lcms=fj.MRI(lcms), lcm_thresh=thr, sublist=sub,
-                   rng_seed=1234 + seed, len_max=40)
-    ref = orc.stream(ovs, sub, mask=mask, lcms=lcms, lcm_thresh=thr, rng_seed=1234 + seed, len_max=40, nthreads=4)
+                   rng_seed=1234 + seed, len_max=len_max)
+    ref = orc.stream(ovs, sub, mask=mask, lcms=lcms, lcm_thresh=thr, rng_seed=1234 + seed, len_max=len_max, nthreads=4)
     assert len(ref["npts"]) > 100
     assert np.array_equal(tr.npts, ref["npts"]) and np.array_equal(tr.seed_index, ref["seed_index"])
     assert np.array_equal(tr.xyz, ref["xyz"])
@@ -218,7 +221,7 @@ def test_stream_lcm_guided_exact(fj, orc, nvec, seed, thr):
     if nvec > 1:
         assert 0.0 < tr.scalars.mean() < 1.0                   # both picks occur
     tr2 = fj.stream([fj.MRI(o) for o in ovs], mask=fj.MRI(mask), lcms=fj.MRI(lcms), lcm_thresh=thr, sublist=sub,
-                    rng_seed=99, len_max=40)
+                    rng_seed=99, len_max=len_max)
     assert not (np.array_equal(tr2.npts, tr.npts) and np.array_equal(tr2.xyz, tr.xyz))
 
 

@@ -2,8 +2,9 @@
 """The FUSED tracer (trace + decoupled look-back + pack in one launch: fibd_stream_run from 2^21 lines on) against trace + scan + pack on
 SMALL inputs, where only the DIAGNOSTIC build can force it (FIBERS_STREAM_FUSED=1; the product's full-size tests are the only other cover:
 ADVICE r5).  For 1, 2 and 3 vectors per voxel: a line count that is not a multiple of the 512-line workgroup, lines dropped by len_min,
-buffers that are too small (FIB_ERR_CAPACITY: the totals say what is needed, nothing is written past the capacities), and the enqueue
-form whose counts stay on the device.  Lines must be bit-identical (stream.jl:625-690, 769-787).  Exit code 0 = all identical."""
+buffers that are too small (FIB_ERR_CAPACITY: the totals say what is needed, nothing is written past the capacities), the enqueue
+form whose counts stay on the device, and (two vectors) an xyz buffer that starts 1, 2 and 3 floats behind a 16-byte boundary, with
+sentinels on both sides.  Lines must be bit-identical (stream.jl:625-690, 769-787).  Exit code 0 = all identical."""
 import ctypes as C
 import os
 import sys
@@ -65,10 +66,26 @@ def main():
             cap_ok = (rc == _lib.FIB_ERR_CAPACITY and nl.value == nl_ref and npnt.value == np_ref and bool((small_x[capp:] == -7.0).all()))
             kept = small_n != -7
             cap_ok = cap_ok and torch.equal(small_n[kept], ref["npts"][:capl][kept])
+            # every alignment of the output: xyz starts 1, 2 and 3 floats into a sentinel-filled tensor (16-byte aligned itself)
+            mis_ok = True
+            if nvec == 2 and len_min == 2:
+                for shift in (1, 2, 3):
+                    big_n = torch.empty(nl_ref, dtype=torch.int32, device=dev)
+                    big_s = torch.empty(nl_ref, dtype=torch.int64, device=dev)
+                    big_x = torch.full((3 * np_ref + 16,), -7.0, device=dev)
+                    assert big_x.data_ptr() % 16 == 0
+                    rc = _lib.lib().fibd_stream_run(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sub.data_ptr(), sub.shape[0],
+                                                    big_n.data_ptr(), big_s.data_ptr(), nl_ref, big_x.data_ptr() + 4 * shift, np_ref,
+                                                    C.byref(nl), C.byref(npnt), None)
+                    torch.cuda.synchronize()
+                    mis_ok = mis_ok and rc == 0 and nl.value == nl_ref and npnt.value == np_ref
+                    mis_ok = mis_ok and torch.equal(big_n, ref["npts"]) and torch.equal(big_s, ref["seed_index"])
+                    mis_ok = mis_ok and torch.equal(big_x[shift: shift + 3 * np_ref], ref["xyz"].reshape(-1))
+                    mis_ok = mis_ok and bool((big_x[:shift] == -7.0).all()) and bool((big_x[shift + 3 * np_ref:] == -7.0).all())
             os.environ.pop("FIBERS_STREAM_FUSED", None)
-            ok = same and cap_ok and nl_ref > (200 if len_min > 2 else 5000)
-            print("%d vector(s), len_min %2d: lines %6d of %6d, points %8d  fused == trace + pack: %s, capacity path: %s" % (
-                nvec, len_min, nl_ref, seeds.numel() * 2, np_ref, same, cap_ok), flush=True)
+            ok = same and cap_ok and mis_ok and nl_ref > (200 if len_min > 2 else 5000)
+            print("%d vector(s), len_min %2d: lines %6d of %6d, points %8d  fused == trace + pack: %s, capacity path: %s, shifted xyz: %s" % (
+                nvec, len_min, nl_ref, seeds.numel() * 2, np_ref, same, cap_ok, mis_ok), flush=True)
             bad += 0 if ok else 1
     print("stream fused check:", "ok" if bad == 0 else "%d FAILURES" % bad)
     return 1 if bad else 0
