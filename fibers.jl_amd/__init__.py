@@ -12,6 +12,9 @@ from .dki import DKI, DkiPlan, dki_design, dki_fit, dki_fit_device  # noqa: F401
 # (the device tier of csd_rec is reached through the module: csd.csd_rec_device)
 from . import csd  # noqa: F401
 from .csd import CSD, CsdPlan, csd_design, csd_rec, csd_response, csd_write  # noqa: F401
+# (the device tier of dwi_denoise is reached through the module: denoise.dwi_denoise_device)
+from . import denoise  # noqa: F401
+from .denoise import Denoised, dwi_denoise  # noqa: F401
 from .gqi import (DSI, GQI, OdfPlan, dsi_rec, find_peaks, find_peaks_device, find_peaks_work, gqi_rec, odf_rec_device,  # noqa: F401
                   qa_normalize_device)
 from .rumba import RUMBASD, RumbaPlan, rumba_rec, rumba_rec_device  # noqa: F401

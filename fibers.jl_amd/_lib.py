@@ -110,6 +110,10 @@ _PROTOS = {
     "fibd_st_recon_work_size": (i32, [i32, i32, i32, f32, f32, C.POINTER(C.c_uint64)]),
     "fibd_st_recon": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, C.c_uint64, vp]),
     "fib_st_recon": (i32, [i32, vp, i32, i32, i32, f32, f32, vp, vp]),
+    "fib_dwi_denoise_check": (i32, [i32, i32, i32, i32, i32, i32]),
+    "fibd_dwi_denoise_work_size": (i32, [i32, i32, i32, i32, i32, C.POINTER(C.c_uint64)]),
+    "fibd_dwi_denoise": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fib_dwi_denoise": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "fibd_dti_last_partial_count": (i32, [vp, vp, C.POINTER(i64)]),
     "fibd_odf_rec": (i32, [vp, vp, vp, i64, vp, vp, P3, P3, vp, i32, vp]),
     "fibd_qa_normalize": (i32, [P3, i64, f32, vp]),

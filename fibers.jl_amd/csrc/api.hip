@@ -689,6 +689,58 @@ extern "C" int fib_st_recon(int device, const float *vol, int nx, int ny, int nz
     return FIB_OK;
 } FIB_API_CATCH
 
+// dwi_denoise host form: z-slabs of every frame, each uploaded with the planes its clamped patches reach (P - 1 beyond the slab, all to
+// one side at a face); a slab's rows scatter into the [nx,ny,nz,nvol] array
+extern "C" int fib_dwi_denoise(int device, const float *dwi, int nx, int ny, int nz, int nvol, const uint8_t *mask, int patch, int estimator,
+                               float *out, float *sigma, float *rank) try {
+    FIB_CHECK(dwi && mask && out && sigma && rank, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "nx, ny, nz must be positive");
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "dwi_denoise runs on one device (FIB_DEVICE_ALL is not supported)");
+    RC(fib_dwi_denoise_check(nx, ny, nz, nvol, patch, estimator));
+    DevLease lease;
+    RC(lease.take(device, nullptr));                       // (FIB_DEVICE_ALL: refused above, before the shape)
+    const size_t plane = (size_t)nx * ny;
+    size_t work_bytes = 0;
+    RC(fibd_dwi_denoise_work_size(nx, ny, nz, nvol, patch, &work_bytes));   // (the whole volume's: no slab needs more)
+    int nzs = 0;
+    if (const char *e = fib::env("FIBERS_DENOISE_SLAB")) nzs = std::min(atoi(e), nz);
+    if (nzs <= 0) {
+        size_t fr = 0, tot = 0;
+        FIB_HIP(hipMemGetInfo(&fr, &tot));
+        // planes_per_slab counts 64 bytes a voxel of an output plane and 16 a voxel of each of 2 * halo further planes.  Here an output
+        // plane costs 8 nvol + 9 (frames in and out, sigma, rank, mask) and each of the P - 1 further planes 4 nvol: with planes of
+        // ceil((8 nvol + 9) / 64) voxels' worth and halo = P - 1 both are covered.  It plans with half of what it is given, so the
+        // workspace comes off twice
+        const size_t scale = ((size_t)8 * nvol + 9 + 63) / 64;
+        nzs = fibh::planes_per_slab(fr > 2 * work_bytes ? fr - 2 * work_bytes : 0, plane * scale, patch - 1, nz);
+        FIB_CHECK(nzs >= 1, FIB_ERR_NOMEM, "dwi_denoise: one %d x %d plane of %d frames with its halo does not fit in device memory", nx, ny, nvol);
+    }
+    const int nzin_max = std::min(nz, nzs + patch - 1), h = patch / 2;
+    fib::DevBuf<float> d_in, d_out;
+    fib::DevBuf<uint8_t> d_mask;
+    fib::DevBuf<char> d_work;
+    RC(d_in.alloc(plane * nzin_max * nvol));
+    RC(d_out.alloc(plane * nzs * ((size_t)nvol + 2)));
+    RC(d_mask.alloc(plane * nzs));
+    RC(d_work.alloc(work_bytes));
+    const size_t nvox = plane * nz;
+    for (int z0 = 0; z0 < nz; z0 += nzs) {
+        const int z1 = std::min(nz, z0 + nzs);
+        const int zin0 = std::min(std::max(z0 - h, 0), nz - patch), zin1 = std::min(std::max(z1 - 1 - h, 0), nz - patch) + patch;
+        const size_t nin = plane * (zin1 - zin0), nout = plane * (z1 - z0);
+        for (int f = 0; f < nvol; f++) RC(h2d(d_in.p + f * nin, dwi + f * nvox + plane * zin0, sizeof(float) * nin));
+        RC(h2d(d_mask.p, mask + plane * z0, nout));
+        float *d_sigma = d_out.p + (size_t)nvol * nout, *d_rank = d_sigma + nout;
+        RC(fibd_dwi_denoise(d_in.p, nx, ny, nz, zin0, zin1 - zin0, z0, z1, nvol, patch, estimator, d_mask.p, d_out.p, d_sigma, d_rank,
+                            d_work.p, work_bytes, nullptr));
+        FIB_HIP(hipDeviceSynchronize());
+        for (int f = 0; f < nvol; f++) RC(d2h(out + f * nvox + plane * z0, d_out.p + f * nout, sizeof(float) * nout));
+        RC(d2h(sigma + plane * z0, d_sigma, sizeof(float) * nout));
+        RC(d2h(rank + plane * z0, d_rank, sizeof(float) * nout));
+    }
+    return FIB_OK;
+} FIB_API_CATCH
+
 // The frame resampler of fib_vol_xform and fib_warp_volume, in the two pieces a form puts around its lease: frame_checks after its own
 // checks; frame_chunks once what stays resident is on the device.  Frames are independent: chunks of whole frames, per chunk upload,
 // launch(d_in, d_out, nf) = the form's fibd_* call, download.  Copies block on the NULL stream: the read-back comes behind the kernel.

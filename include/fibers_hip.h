@@ -256,6 +256,40 @@ int fib_csd_plan_tables(const fib_csd_plan *plan, int32_t *frames, int *nshell, 
  * voxel.  The plan holds the peak finder's scratch of the call: one call at a time per plan. */
 int fibd_csd_rec(const fib_csd_plan *plan, const float *dwi, const uint8_t *mask, int64_t nvox, const fib_csd_out *out, void *stream);
 
+/* ---- Marchenko-Pastur PCA denoising (not in the reference; this section and DESIGN.md §5 are the definition) ----
+ * Inputs: dwi float32 [N][nvox] planar, x fastest, N >= 2 frames; a uint8 mask; a patch edge P in {3, 5, 7}; an estimator.  Every
+ *   dimension of the volume must be >= P (FIB_ERR_INVALID otherwise).
+ * Patch of voxel (x, y, z): the P^3 block that starts at x0 = min(max(x - P / 2, 0), nx - P) (integer division), likewise y0, z0: the
+ *   block nearest to the voxel that lies wholly inside the volume (no mirroring: mirrored patches of small volumes repeat rows and make
+ *   the Gram matrix exactly singular).  The patch reads every voxel, whatever the mask says.
+ * X is M x N, M = P^3; row (dz P + dy) P + dx holds the N samples of that voxel, c is the row of the voxel itself.  r = min(M, N),
+ *   q = max(M, N).  G = X X' when M <= N, else X' X: r x r, float64 sums of float64 products of the float32 samples, with eigenvalues
+ *   l_0 <= ... <= l_{r-1}.
+ * The rule (Veraart et al. 2016 as EXP1, Cordero-Grande's variant as EXP2):
+ *   lam_p = max(l_p, 0) / q;  clam = 0;  cutoff = 0;  sigma2 = 0
+ *   for p = 0 .. r-1:  clam += lam_p;  gam = (p + 1) / q (EXP1) or (p + 1) / (q - (r - p - 1)) (EXP2);
+ *                      s1 = clam / (p + 1);  s2 = (lam_p - lam_0) / (4 sqrt(gam));  if s2 < s1: sigma2 = s1, cutoff = p + 1
+ * Per voxel inside the mask: rank = r - cutoff; sigma = sqrt(sigma2); the denoised row from E, the eigenvectors of the `rank` largest
+ *   eigenvalues (equal eigenvalues: the lower index counts as the smaller): X' (E E' e_c) when M <= N, else E E' x_c.  Everything is
+ *   float64 and is rounded to float32 once.  cutoff = 0 leaves the row as it is (the projector is the identity) with sigma = 0;
+ *   cutoff = r gives a zero row.  Outside the mask all three outputs are 0.  rank is a count stored as float32, like every volume.
+ * The eigen-decomposition is cyclic Jacobi in float64, a rotation being skipped when |g_pq| <= 2^-52 sqrt|g_pp g_qq|; a voxel that
+ *   has not converged after 24 sweeps gets its input row back with sigma = NaN and rank = -1.
+ * r > 128 is FIB_ERR_UNSUPPORTED: P = 5 serves any N, P = 7 up to 128 frames. */
+#define FIB_DENOISE_EXP1 1
+#define FIB_DENOISE_EXP2 2
+/* Host only (no device needed): the refusals above for a whole volume, FIB_OK when fib_dwi_denoise would accept it. */
+int fib_dwi_denoise_check(int nx, int ny, int nz, int nvol, int patch, int estimator);
+/* bytes of workspace fibd_dwi_denoise needs for nz output planes: a ticket counter and the rotation records of its persistent
+ * workgroups (at most 512 of them, each sized by the cap on sweeps), so it does not grow with the volume. */
+int fibd_dwi_denoise_work_size(int nx, int ny, int nz, int nvol, int patch, size_t *bytes);
+/* dwi holds planes [zin0, zin0 + nzin) of every frame, [nvol][nx * ny * nzin]; outputs cover planes [z0, z1): out [nvol][n], sigma [n],
+ * rank [n], mask uint8 [n] with n = nx * ny * (z1 - z0).  The patch clamp is taken against the whole volume's nz, so dwi must hold the
+ * planes from the patch of plane z0 to the patch of plane z1 - 1: at most P - 1 planes beyond [z0, z1), all to one side at a face.
+ * work: 8-byte aligned, work_bytes >= fibd_dwi_denoise_work_size(nx, ny, z1 - z0, ...); one call at a time per workspace. */
+int fibd_dwi_denoise(const float *dwi, int nx, int ny, int nz, int zin0, int nzin, int z0, int z1, int nvol, int patch, int estimator,
+                     const uint8_t *mask, float *out, float *sigma, float *rank, void *work, size_t work_bytes, void *stream);
+
 /* gqi_rec / dsi_rec volume loop + find_peaks! + peak/qa extraction (gqi.jl:132-162,
  * dsi.jl:197-261).  odf [nvox*nvert] planar; pdf [nvox*nvol] (DSI plans only, else NULL);
  * peak[k] [nvox*3] planar, qa[k] [nvox].  `flags` is a bit set:
@@ -869,6 +903,11 @@ int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigve
  * volume larger than the device's memory still goes through; results do not depend on the slab thickness.  FIB_DEVICE_ALL:
  * FIB_ERR_UNSUPPORTED. */
 int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sigma, float rho, float *eigvec, float *eigval);
+/* host-buffer form of fibd_dwi_denoise: dwi and out [nx,ny,nz,nvol], mask uint8 [nx,ny,nz], sigma and rank [nx,ny,nz] (column-major).
+ * The volume goes through the device in z-slabs with a halo of P - 1 planes (FIBERS_DENOISE_SLAB forces the output planes per slab);
+ * results do not depend on the slab thickness.  FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED. */
+int fib_dwi_denoise(int device, const float *dwi, int nx, int ny, int nz, int nvol, const uint8_t *mask, int patch, int estimator,
+                    float *out, float *sigma, float *rank);
 /* xfm_apply(xfm, point) (util.jl:385-420) on npoints float32 points [npoints][3] (x, y, z of a point adjacent, as the 3N vector the
  * reference takes).  vox2vox is ROW-major: vox2vox[4 * i + j] = xfm.vox2vox[i + 1, j + 1] (Julia passes permutedims(vox2vox)).
  * Per point, in float32 with every multiply and add rounded on its own, in the reference's order: w = 0 + m41 x + m42 y + m43 z + m44,

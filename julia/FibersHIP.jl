@@ -271,6 +271,29 @@ function st_recon(vol::Array{Float32,3}, sigma::Number, rho::Number; device::Int
   return eigvec, eigval
 end
 
+"Container for outputs of dwi_denoise: the denoised series, the noise level and the number of components kept per voxel"
+struct Denoised
+  dwi::MRI; sigma::MRI; rank::MRI
+end
+
+"dwi_denoise(dwi, mask; patch, estimator) — Marchenko-Pastur PCA denoising (not in the reference; include/fibers_hip.h).
+ patch in (3, 5, 7); estimator :exp1 or :exp2.  The mask is read as nonzero = inside."
+function dwi_denoise(dwi::MRI, mask::MRI; patch::Integer=5, estimator::Symbol=:exp2, device::Integer=0)
+  nx, ny, nz, nvol = size(dwi.vol)
+  est = estimator == :exp1 ? 1 : estimator == :exp2 ? 2 : error("estimator must be :exp1 or :exp2")
+  fib_check(ccall((:fib_dwi_denoise_check, libfibers), Cint, (Cint, Cint, Cint, Cint, Cint, Cint), nx, ny, nz, nvol, patch, est))
+  vol = dwi.vol::Array{Float32,4}
+  m = UInt8.(view(mask.vol, :, :, :, 1) .!= 0)
+  out = Array{Float32,4}(undef, nx, ny, nz, nvol)
+  S = MRI(mask, 1, Float32); R = MRI(mask, 1, Float32)
+  GC.@preserve vol m out S R fib_check(ccall((:fib_dwi_denoise, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Cint, Ptr{UInt8}, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+      device, vol, nx, ny, nz, nvol, m, patch, est, out, pointer(S.vol), pointer(R.vol)))
+  D = deepcopy(dwi)
+  D.vol = out
+  return Denoised(D, S, R)
+end
+
 "rumba_rec(dwi, mask, odf_dirs, niter, ...) — replaces rusd.jl:419-636"
 function rumba_rec(dwi::MRI, mask::MRI, odf_dirs::ODF=sphere_724, niter::Integer=600, λ_para::Float32=Float32(1.7e-3),
                    λ_perp::Float32=Float32(0.2e-3), λ_csf::Float32=Float32(3.0e-3), λ_gm::Float32=Float32(0.8e-4),
