@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._dev import ArgError, Launch, Plan, tensor
-from .dti import _check_tables, _dwi_arg, _fit_args, _mask_arg, _mask_checked
+from .dti import _check_tables, _table_args, _dwi_arg, _fit_args, _mask_arg, _mask_checked
 from .gqi import _odf_args, _p3
 from .mri import MRI
 from .nifti import csd_write  # noqa: F401
@@ -44,14 +44,6 @@ def _params(response, lmax, b0_thresh, shell, b_tol, lam, tau, niter):
                           float(tau), int(niter))
 
 
-def _tables(bval, bvec):
-    bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
-    bv = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
-    if bv.shape[0] != bval.shape[0]:
-        raise ValueError("gradient table must be [%d x 3], got %s" % (bval.shape[0], bv.shape))
-    return bval, bv
-
-
 def csd_response(dti, mask, fa_thresh: float = 0.7):
     """The single-fibre response from a tensor fit: (mean eigval1, mean (eigval2 + eigval3) / 2, mean s0) over the voxels inside the
     mask whose fa exceeds fa_thresh, summed in float64 on the host.  Raises when no voxel qualifies."""
@@ -72,7 +64,7 @@ def csd_design(bval, bvec, response, odf_dirs: ODF = sphere_724, lmax: int = DEF
     """The reconstruction's tables, built on the host in float64 and rounded once: dict(frames int32 [nshell] (0-based), R float32
     [lmax / 2 + 1], X [nshell, n], B [nreg, n], Y [nreg, n], rank).  response = (lambda_para, lambda_perp, s0).  A shell of fewer than n
     frames, or one whose kernel matrix has a rank below n, raises FibersError (code -1)."""
-    bval, bv = _tables(bval, bvec)
+    bval, bv = _table_args(bval, bvec)
     nvol, n, nreg = int(bval.shape[0]), ncoef(lmax), odf_dirs.nvert
     v, _ = _odf_args(odf_dirs)
     p = _params(response, lmax, b0_thresh, shell, b_tol, lam, DEFAULTS["tau"], DEFAULTS["niter"])
@@ -121,7 +113,7 @@ class CsdPlan(Plan):
                  b0_thresh: float = DEFAULTS["b0_thresh"], shell=DEFAULTS["shell"], b_tol: float = DEFAULTS["b_tol"],
                  lam: float = DEFAULTS["lam"], tau: float = DEFAULTS["tau"], niter: int = DEFAULTS["niter"], device: int = 0):
         Plan.__init__(self, device)
-        bval, bv = _tables(bval, bvec)
+        bval, bv = _table_args(bval, bvec)
         self.nvol, self.lmax, self.n, self.nreg = int(bval.shape[0]), int(lmax), ncoef(lmax), odf_dirs.nvert
         v, fc = _odf_args(odf_dirs)
         p = _params(response, lmax, b0_thresh, shell, b_tol, lam, tau, niter)

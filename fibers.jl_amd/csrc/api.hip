@@ -462,7 +462,7 @@ struct FitCall {
 int fit_call(FitCall &c, int device, const float *bval, int nvol, bool bvec_ok, bool ptrs_ok, int nx, int ny, int nz, int mask_dtype, bool outs_ok,
              const char *outs_msg = "NULL output volume", bool tess_ok = true, bool dims_more_ok = true,
              const char *dims_msg = "volume dimensions must be positive") {
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
+    FIB_RC(fib::check_tables(bval, nullptr, nvol, false));
     FIB_CHECK(bvec_ok, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
     FIB_CHECK(tess_ok, FIB_ERR_INVALID, "invalid ODF tessellation");
     FIB_CHECK(ptrs_ok, FIB_ERR_INVALID, "NULL argument");
@@ -1376,9 +1376,8 @@ int find_peaks_host(int device, const float *odf, int64_t nvox, const float *ver
     FIB_CHECK(odf && verts && faces && a && (b || !has_b) && nvalid, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nvox > 0 && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid sizes");
     DevLease lease;
-    const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};   // (only the folded neighbour table is used: a GQI plan of one dummy frame)
     fib_odf_plan *plan = nullptr;
-    RC(fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, &plan));
+    RC(fib::peaks_plan_create(device, verts, nverts, faces, nfaces, &plan));
     struct PlanDel { fib_odf_plan *p; ~PlanDel() { fib_odf_plan_destroy(p); } } del{plan};
     RC(lease.take(device, nullptr));
     const size_t nv = (size_t)nvox, n = nv * (nverts / 2);

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -68,6 +69,40 @@ struct DevBuf {  // RAII device allocation
     }
     int ensure(size_t count) { return (count <= n && p) ? FIB_OK : alloc(count); }
 };
+
+// ---- what every plan constructor is made of (host only) -----------------------------------
+// alloc + copy of `count` elements; a count of zero allocates as DevBuf::alloc(0) does and copies nothing
+template <typename T>
+int upload(DevBuf<T> &buf, const T *host, size_t count) {
+    FIB_RC(buf.alloc(count));
+    if (count) FIB_HIP(hipMemcpy(buf.p, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return FIB_OK;
+}
+template <typename T>
+int upload(DevBuf<T> &buf, const std::vector<T> &host) { return upload(buf, host.data(), host.size()); }
+
+template <typename T>
+int zeroed(DevBuf<T> &buf, size_t count) {  // alloc + clear
+    FIB_RC(buf.alloc(count));
+    FIB_HIP(hipMemset(buf.p, 0, buf.n * sizeof(T)));
+    return FIB_OK;
+}
+
+// the body of every fib_*_plan_destroy: the plan's buffers are freed on the device that holds them
+template <typename Plan>
+void plan_destroy(Plan *plan) {
+    if (!plan) return;
+    DeviceGuard guard;
+    (void)hipSetDevice(plan->device);
+    delete plan;
+}
+
+// the b-table refusals, in the reference's words
+static inline int check_tables(const float *bval, const float *bvec, int nvol, bool need_bvec = true) {
+    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
+    FIB_CHECK(!need_bvec || bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    return FIB_OK;
+}
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -132,6 +167,8 @@ int host_neighbours(const int32_t *faces, int nfaces, int nverts, std::vector<in
 // [nrows x ncols]; S, out planar (row stride n); `ones` = n bytes of 1 on the device; recompact = (re)build the column
 // list (needed once per n)
 int matrix_plan_create(int device, const float *A, int nrows, int ncols, fib_odf_plan **plan);
+// the plan fib_find_peaks* and CSD hand to the peak finder: fib_gqi_plan_create on one dummy frame, with its refusals
+int peaks_plan_create(int device, const float *verts, int nverts, const int32_t *faces, int nfaces, fib_odf_plan **plan);
 int matrix_plan_run(const fib_odf_plan *plan, const float *S, const uint8_t *ones, int64_t n, float *out, bool recompact, void *stream);
 
 }  // namespace fib

@@ -400,8 +400,7 @@ extern "C" int fib_csd_design(const float *bval, const float *bvec, int nvol, co
                               int32_t *frames, int *nshell, float *R, float *X, float *B, float *Y, int *rank) try {
     if (rank) *rank = 0;
     if (nshell) *nshell = 0;
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    FIB_RC(fib::check_tables(bval, bvec, nvol));
     FIB_CHECK(verts != nullptr && nverts >= 2 && nverts % 2 == 0, FIB_ERR_INVALID, "the ODF tessellation needs an even number of vertices");
     FIB_CHECK(params != nullptr, FIB_ERR_INVALID, "CSD needs its parameters (the response has no default)");
     CsdDesign d;
@@ -431,7 +430,7 @@ struct fib_csd_plan {
     fib::DevBuf<int32_t> frames;
     fib::DevBuf<float> Xd, Brow, Yt, verts;
     fib::DevBuf<double> G0, G1, M0;
-    fib_odf_plan *peaks = nullptr;        // the folded neighbour table of the tessellation: a GQI plan of one dummy frame
+    fib_odf_plan *peaks = nullptr;        // the folded neighbour table of the tessellation (fib::peaks_plan_create)
     mutable fib::DevBuf<int32_t> top, nvalid;   // the peak finder's results of the call in flight (grow-only)
     ~fib_csd_plan() { if (peaks) fib_odf_plan_destroy(peaks); }
 };
@@ -461,20 +460,17 @@ extern "C" int fib_csd_plan_create(int device, const float *bval, const float *b
                                    const int32_t *faces, int nfaces, const fib_csd_params *params, fib_csd_plan **plan) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan output pointer is NULL");
     *plan = nullptr;
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    FIB_RC(fib::check_tables(bval, bvec, nvol));
     FIB_CHECK(verts != nullptr && faces != nullptr && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid ODF tessellation");
     FIB_CHECK(params != nullptr, FIB_ERR_INVALID, "CSD needs its parameters (the response has no default)");
     CsdDesign d;
-    int rc = csd_design(bval, bvec, nvol, verts, nverts, *params, d);
-    if (rc != FIB_OK) return rc;
+    FIB_RC(csd_design(bval, bvec, nvol, verts, nverts, *params, d));
     FIB_CHECK(d.rank == d.n, FIB_ERR_INVALID, "the shell's directions do not determine the %d harmonics of lmax %d (the kernel matrix has rank %d on %d frames)",
               d.n, d.lmax, d.rank, d.nshell);
     FIB_CHECK(d.nshell <= CSD_MAXSHELL, FIB_ERR_UNSUPPORTED, "a shell of %d frames exceeds the supported %d", d.nshell, CSD_MAXSHELL);
     FIB_CHECK(d.nreg <= 64 * CSD_MAXW, FIB_ERR_UNSUPPORTED, "a tessellation of %d directions exceeds the supported %d", d.nreg, 64 * CSD_MAXW);
     fib::DeviceGuard guard;
-    rc = fib::use_device(device);
-    if (rc != FIB_OK) return rc;
+    FIB_RC(fib::use_device(device));
     std::unique_ptr<fib_csd_plan> p(new fib_csd_plan());
     const int n = d.n, ns = n | 1, np = (n + 7) / 8 * 8;
     p->device = device; p->lmax = d.lmax; p->n = n; p->nshell = d.nshell; p->nreg = d.nreg; p->nverts = nverts; p->rank = d.rank;
@@ -515,40 +511,20 @@ extern "C" int fib_csd_plan_create(int device, const float *bval, const float *b
 #endif
     p->smem = csd_smem(n, d.nshell, d.nreg, p->b_lds);
     FIB_CHECK(p->smem <= (size_t)CSD_LDS_LIMIT, FIB_ERR_UNSUPPORTED, "the CSD workgroup does not fit the LDS");
-    {
-        const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};
-        rc = fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, &p->peaks);
-        if (rc != FIB_OK) return rc;
-    }
-    std::vector<float> vh((size_t)3 * nverts);
-    memcpy(vh.data(), verts, vh.size() * sizeof(float));
-    rc = p->frames.alloc(d.frames.size());
-    if (rc == FIB_OK) rc = p->Xd.alloc(Xr.size());
-    if (rc == FIB_OK) rc = p->Brow.alloc(Br.size());
-    if (rc == FIB_OK) rc = p->Yt.alloc(Yt.size());
-    if (rc == FIB_OK) rc = p->verts.alloc(vh.size());
-    if (rc == FIB_OK) rc = p->G0.alloc(G0.size());
-    if (rc == FIB_OK) rc = p->G1.alloc(G1.size());
-    if (rc == FIB_OK) rc = p->M0.alloc(M0.size());
-    if (rc != FIB_OK) return rc;
-    FIB_HIP(hipMemcpy(p->frames.p, d.frames.data(), d.frames.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->Xd.p, Xr.data(), Xr.size() * sizeof(float), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->Brow.p, Br.data(), Br.size() * sizeof(float), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->Yt.p, Yt.data(), Yt.size() * sizeof(float), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->verts.p, vh.data(), vh.size() * sizeof(float), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->G0.p, G0.data(), G0.size() * sizeof(double), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->G1.p, G1.data(), G1.size() * sizeof(double), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->M0.p, M0.data(), M0.size() * sizeof(double), hipMemcpyHostToDevice));
+    FIB_RC(fib::peaks_plan_create(device, verts, nverts, faces, nfaces, &p->peaks));
+    FIB_RC(fib::upload(p->frames, d.frames));
+    FIB_RC(fib::upload(p->Xd, Xr));
+    FIB_RC(fib::upload(p->Brow, Br));
+    FIB_RC(fib::upload(p->Yt, Yt));
+    FIB_RC(fib::upload(p->verts, verts, (size_t)3 * nverts));
+    FIB_RC(fib::upload(p->G0, G0));
+    FIB_RC(fib::upload(p->G1, G1));
+    FIB_RC(fib::upload(p->M0, M0));
     *plan = p.release();
     return FIB_OK;
 } FIB_API_CATCH
 
-extern "C" void fib_csd_plan_destroy(fib_csd_plan *plan) try {
-    if (!plan) return;
-    fib::DeviceGuard guard;
-    (void)hipSetDevice(plan->device);
-    delete plan;
-} FIB_API_CATCH_VOID
+extern "C" void fib_csd_plan_destroy(fib_csd_plan *plan) try { fib::plan_destroy(plan); } FIB_API_CATCH_VOID
 
 extern "C" int fib_csd_plan_tables(const fib_csd_plan *plan, int32_t *frames, int *nshell, float *R, float *X, float *B, float *Y) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan is NULL");

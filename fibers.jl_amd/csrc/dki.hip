@@ -168,26 +168,21 @@ extern "C" int fib_dki_plan_create(int device, const float *bval, const float *b
                                    const fib_dki_params *params, fib_dki_plan **plan) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan output pointer is NULL");
     *plan = nullptr;
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    FIB_RC(fib::check_tables(bval, bvec, nvol));
     FIB_CHECK(verts != nullptr && nverts >= 2, FIB_ERR_INVALID, "the ODF tessellation needs at least two vertices");
     fib_dki_params pr{1e-4f, 1e-6f, -3.0f / 7.0f, 10.0f};
     if (params) pr = *params;
     FIB_CHECK(pr.min_signal > 0.0f && pr.min_diffusivity > 0.0f, FIB_ERR_INVALID, "min_signal and min_diffusivity must be positive");
     FIB_CHECK(pr.min_kurtosis == pr.min_kurtosis && pr.max_kurtosis == pr.max_kurtosis, FIB_ERR_INVALID, "the kurtosis limits must not be NaN");
     fib::DeviceGuard guard;
-    int rc = fib::use_device(device);
-    if (rc != FIB_OK) return rc;
-    std::vector<float> A((size_t)nvol * 22), pA((size_t)nvol * 22);
-    rc = fib_dki_design(bval, bvec, nvol, A.data(), pA.data(), nullptr);
-    if (rc != FIB_OK) return rc;
-    fib_dki_plan *p = new (std::nothrow) fib_dki_plan();
-    FIB_CHECK(p != nullptr, FIB_ERR_NOMEM, "out of host memory");
+    FIB_RC(fib::use_device(device));
+    std::unique_ptr<fib_dki_plan> p(new fib_dki_plan());
     p->device = device;
     p->nvol = nvol;
     p->ndir = nverts / 2;
-    p->A.swap(A);
-    p->pA.swap(pA);
+    p->A.resize((size_t)nvol * 22);
+    p->pA.resize((size_t)nvol * 22);
+    FIB_RC(fib_dki_design(bval, bvec, nvol, p->A.data(), p->pA.data(), nullptr));
     p->dirs.resize((size_t)p->ndir * 21);
     for (int v = 0; v < p->ndir; v++) {
         double row[21];
@@ -204,22 +199,13 @@ extern "C" int fib_dki_plan_create(int device, const float *bval, const float *b
     std::vector<double> coef((size_t)nvol * 24, 0.0);
     for (int i = 0; i < nvol; i++)
         for (int j = 0; j < 22; j++) coef[(size_t)24 * i + j] = p->pA[j + (size_t)22 * i];
-    rc = p->coef.alloc(coef.size());
-    if (rc == FIB_OK) rc = p->dirtab.alloc(p->dirs.size());
-    if (rc != FIB_OK) { delete p; return rc; }
-    hipError_t e = hipMemcpy(p->coef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->dirtab.p, p->dirs.data(), p->dirs.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { delete p; return fib::fail(FIB_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e)); }
-    *plan = p;
+    FIB_RC(fib::upload(p->coef, coef));
+    FIB_RC(fib::upload(p->dirtab, p->dirs));
+    *plan = p.release();
     return FIB_OK;
 } FIB_API_CATCH
 
-extern "C" void fib_dki_plan_destroy(fib_dki_plan *plan) try {
-    if (!plan) return;
-    fib::DeviceGuard guard;
-    (void)hipSetDevice(plan->device);
-    delete plan;
-} FIB_API_CATCH_VOID
+extern "C" void fib_dki_plan_destroy(fib_dki_plan *plan) try { fib::plan_destroy(plan); } FIB_API_CATCH_VOID
 
 extern "C" int fib_dki_plan_tables(const fib_dki_plan *plan, float *A, float *pA, float *dirs) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan is NULL");

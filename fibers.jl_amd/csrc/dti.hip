@@ -330,12 +330,10 @@ struct fib_dti_plan {
 extern "C" int fib_dti_plan_create(int device, const float *bval, const float *bvec, int nvol, fib_dti_plan **plan) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan output pointer is NULL");
     *plan = nullptr;
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
+    FIB_RC(fib::check_tables(bval, bvec, nvol, false));
     fib::DeviceGuard guard;
-    int rc = fib::use_device(device);
-    if (rc != FIB_OK) return rc;
-    fib_dti_plan *p = new (std::nothrow) fib_dti_plan();
-    FIB_CHECK(p != nullptr, FIB_ERR_NOMEM, "out of host memory");
+    FIB_RC(fib::use_device(device));
+    std::unique_ptr<fib_dti_plan> p(new fib_dti_plan());
     p->device = device;
     p->nvol = nvol;
     p->np = bvec ? 7 : 2;
@@ -354,24 +352,14 @@ extern "C" int fib_dti_plan_create(int device, const float *bval, const float *b
         }
         coef[(size_t)8 * i + 7] = (bval[i] == bmin) ? 1.0f : 0.0f;   // ib0, dti.jl:117
     }
-    rc = p->coef.alloc(coef.size());
-    if (rc == FIB_OK) rc = p->design.alloc(design.size());
-    if (rc == FIB_OK) rc = p->partial_count.alloc(2);
-    if (rc != FIB_OK) { delete p; return rc; }
-    hipError_t e = hipMemcpy(p->coef.p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->design.p, design.data(), design.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(p->partial_count.p, 0, 2 * sizeof(int));
-    if (e != hipSuccess) { delete p; return fib::fail(FIB_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e)); }
-    *plan = p;
+    FIB_RC(fib::upload(p->coef, coef));
+    FIB_RC(fib::upload(p->design, design));
+    FIB_RC(fib::zeroed(p->partial_count, 2));
+    *plan = p.release();
     return FIB_OK;
 } FIB_API_CATCH
 
-extern "C" void fib_dti_plan_destroy(fib_dti_plan *plan) try {
-    if (!plan) return;
-    fib::DeviceGuard guard;
-    (void)hipSetDevice(plan->device);
-    delete plan;
-} FIB_API_CATCH_VOID
+extern "C" void fib_dti_plan_destroy(fib_dti_plan *plan) try { fib::plan_destroy(plan); } FIB_API_CATCH_VOID
 
 extern "C" int fib_dti_plan_tables(const fib_dti_plan *plan, float *A, float *pA, int *np) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan is NULL");

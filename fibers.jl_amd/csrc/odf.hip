@@ -208,15 +208,9 @@ int finish_plan(fib_odf_plan *p, const float *verts, int nverts, const int32_t *
         std::vector<uint16_t> A3;
         std::vector<float> AX;
         build(nullptr, A3, AX);
-        int rc3 = p->At3.alloc(A3.size());
-        if (rc3 != FIB_OK) return rc3;
-        if (p->gRow0 == 0 && p->scale_frame < 0 && faces) {     // GQI: +Inf samples are repaired after the GEMM
-            if ((rc3 = p->Gdev.alloc(p->G.size())) != FIB_OK) return rc3;
-            FIB_HIP(hipMemcpy(p->Gdev.p, p->G.data(), p->G.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if ((rc3 = p->Aextra.alloc(AX.size())) != FIB_OK) return rc3;
-        FIB_HIP(hipMemcpy(p->At3.p, A3.data(), A3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        FIB_HIP(hipMemcpy(p->Aextra.p, AX.data(), AX.size() * sizeof(float), hipMemcpyHostToDevice));
+        FIB_RC(fib::upload(p->At3, A3));
+        if (p->gRow0 == 0 && p->scale_frame < 0 && faces) FIB_RC(fib::upload(p->Gdev, p->G));   // GQI: +Inf samples are repaired after the GEMM
+        FIB_RC(fib::upload(p->Aextra, AX));
         // single-tile image of mb blocks (+ nx extra rows) whose image row r holds row rowfn(r) of G (< 0: padding)
         auto build_one = [&](int mb, int nx, auto rowfn, std::vector<uint16_t> &A3o, std::vector<float> &AXo) {
             A3o.assign((size_t)nst * NP * mb * 512, 0);
@@ -243,30 +237,23 @@ int finish_plan(fib_odf_plan *p, const float *verts, int nverts, const int32_t *
         if (p->dsi2_shape) {
             const int r0 = p->gRow0;
             build_one(10, 1, [&](int r) { return r < FQ_NV ? r0 + fib_f642_pos_vertex[r] : -1; }, A3, AX);
-            if ((rc3 = p->At3f.alloc(A3.size())) != FIB_OK || (rc3 = p->Aextraf.alloc(AX.size())) != FIB_OK) return rc3;
-            FIB_HIP(hipMemcpy(p->At3f.p, A3.data(), A3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            FIB_HIP(hipMemcpy(p->Aextraf.p, AX.data(), AX.size() * sizeof(float), hipMemcpyHostToDevice));
+            FIB_RC(fib::upload(p->At3f, A3));
+            FIB_RC(fib::upload(p->Aextraf, AX));
             build_one(p->MBB, 0, [&](int r) { return r < r0 ? r : -1; }, A3, AX);
-            if ((rc3 = p->At3b.alloc(A3.size())) != FIB_OK || (rc3 = p->pair_flags.alloc(8 * 32)) != FIB_OK) return rc3;
-            FIB_HIP(hipMemcpy(p->At3b.p, A3.data(), A3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            FIB_RC(fib::upload(p->At3b, A3));
+            FIB_RC(p->pair_flags.alloc(8 * 32));
         }
         p->fused_shape = faces && p->gRow0 == 0 && p->scale_frame < 0 && M == FQ_NV && p->MB == 10 && p->NX == 1 && p->ntile_m == 1 && p->Kpad <= 512 &&
                          nst >= 3;                              // (the sample tiles are requested two stages ahead)
         if (p->fused_shape) {                                   // second image in the row order of sphere642_fused.inc
             build(fib_f642_pos_vertex, A3, AX);
-            if ((rc3 = p->At3f.alloc(A3.size())) != FIB_OK || (rc3 = p->Aextraf.alloc(AX.size())) != FIB_OK) return rc3;
-            FIB_HIP(hipMemcpy(p->At3f.p, A3.data(), A3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            FIB_HIP(hipMemcpy(p->Aextraf.p, AX.data(), AX.size() * sizeof(float), hipMemcpyHostToDevice));
+            FIB_RC(fib::upload(p->At3f, A3));
+            FIB_RC(fib::upload(p->Aextraf, AX));
         }
     }
     std::vector<int32_t> nbr32;
-    int rc = FIB_OK;
-    if (faces) {
-        rc = fib::host_neighbours(faces, nfaces, nverts, nbr32, &p->maxdeg);
-        if (rc != FIB_OK) return rc;
-    } else {                                            // matrix-only plan (fib::matrix_plan_create): no peak finder tables
-        p->maxdeg = 0;
-    }
+    p->maxdeg = 0;                                      // (stays 0 in a matrix-only plan, fib::matrix_plan_create: no peak finder tables)
+    if (faces) FIB_RC(fib::host_neighbours(faces, nfaces, nverts, nbr32, &p->maxdeg));
     p->deg_pad = p->maxdeg <= 6 ? 6 : (p->maxdeg <= 8 ? 8 : 16);
     p->rows_pad = (p->nvert + 7) / 8 * 8;
     const int nv_even = (p->nvert + 1) / 2 * 2;
@@ -289,31 +276,23 @@ int finish_plan(fib_odf_plan *p, const float *verts, int nverts, const int32_t *
     p->dsi2 = p->dsi2_shape && p->is_s642 && p->At3f.p != nullptr && p->At3b.p != nullptr;
     std::vector<int32_t> nbr64(nbr);
     for (auto &u : nbr64) if (u == p->rows_pad) u = p->nvert;
-    if ((rc = p->nbr64.alloc(nbr64.size())) != FIB_OK) return rc;
-    FIB_HIP(hipMemcpy(p->nbr64.p, nbr64.data(), nbr64.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    FIB_RC(fib::upload(p->nbr64, nbr64));
     std::vector<float> v3((size_t)p->nvert * 3, 0.0f);
     if (verts)
         for (int v = 0; v < p->nvert; v++)
             for (int c = 0; c < 3; c++) v3[3 * v + c] = verts[v + (size_t)nverts * c];
-    if ((rc = p->At.alloc(At.size())) != FIB_OK) return rc;
     std::vector<uint32_t> effbits((size_t)p->Kpad / KT, 0u);
     for (int k = 0; k < K; k++) { if (frame_eff[k] != 0.0f) effbits[k / KT] |= 1u << (k % KT); else p->has_ineff = true; }
-    if ((rc = p->effbits.alloc(effbits.size())) != FIB_OK) return rc;
-    if ((rc = p->verts.alloc(v3.size())) != FIB_OK) return rc;
-    if ((rc = p->nbr.alloc(nbr.size())) != FIB_OK) return rc;
-    if ((rc = p->maxenc.alloc(4)) != FIB_OK) return rc;
-    if ((rc = p->live_counts.alloc(4)) != FIB_OK) return rc;
-    if ((rc = p->tickets.alloc(4)) != FIB_OK) return rc;
-    FIB_HIP(hipMemset(p->tickets.p, 0, 4 * sizeof(unsigned)));
-    if ((rc = p->selctr.alloc(2)) != FIB_OK) return rc;
-    FIB_HIP(hipMemset(p->selctr.p, 0, 2 * sizeof(unsigned)));
-    if ((rc = p->sellist.alloc(POST_SELCAP)) != FIB_OK) return rc;
-    FIB_HIP(hipMemset(p->sellist.p, 0, POST_SELCAP * sizeof(unsigned long long)));
-    if ((rc = p->odfmax.alloc(2)) != FIB_OK) return rc;
-    FIB_HIP(hipMemcpy(p->At.p, At.data(), At.size() * sizeof(float), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->effbits.p, effbits.data(), effbits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->verts.p, v3.data(), v3.size() * sizeof(float), hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->nbr.p, nbr.data(), nbr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    FIB_RC(fib::upload(p->At, At));
+    FIB_RC(fib::upload(p->effbits, effbits));
+    FIB_RC(fib::upload(p->verts, v3));
+    FIB_RC(fib::upload(p->nbr, nbr));
+    FIB_RC(p->maxenc.alloc(4));
+    FIB_RC(p->live_counts.alloc(4));
+    FIB_RC(fib::zeroed(p->tickets, 4));
+    FIB_RC(fib::zeroed(p->selctr, 2));
+    FIB_RC(fib::zeroed(p->sellist, POST_SELCAP));
+    FIB_RC(p->odfmax.alloc(2));
     return FIB_OK;
 }
 
@@ -321,8 +300,7 @@ int check_plan_args(const float *bval, const float *bvec, int nvol, const float 
                     const int32_t *faces, int nfaces, fib_odf_plan **plan) {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan output pointer is NULL");
     *plan = nullptr;
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    FIB_RC(fib::check_tables(bval, bvec, nvol));
     FIB_CHECK(verts && faces && nverts >= 2 && nverts % 2 == 0 && nfaces > 0, FIB_ERR_INVALID, "invalid ODF tessellation");
     FIB_CHECK(nverts / 2 < 32768, FIB_ERR_UNSUPPORTED, "too many ODF vertices");
     return FIB_OK;
@@ -360,20 +338,17 @@ extern "C" int fib_odf_plan_list_unit(const fib_odf_plan *plan, void *stream) tr
 extern "C" int fib_gqi_plan_create_fmt(int device, const float *bval, const float *bvec, int nvol,
                                        const float *verts, int nverts, const int32_t *faces, int nfaces,
                                        float sigma, int format, fib_odf_plan **plan) try {
-    int rc = check_plan_args(bval, bvec, nvol, verts, nverts, faces, nfaces, plan);
-    if (rc != FIB_OK) return rc;
+    FIB_RC(check_plan_args(bval, bvec, nvol, verts, nverts, faces, nfaces, plan));
     FIB_CHECK(format >= FIB_ODF_FORMAT_DEFAULT && format <= FIB_ODF_FORMAT_F32, FIB_ERR_INVALID, "unknown operand format %d", format);
     fib::DeviceGuard guard;
-    if ((rc = fib::use_device(device)) != FIB_OK) return rc;
-    fib_odf_plan *p = new (std::nothrow) fib_odf_plan();
-    FIB_CHECK(p != nullptr, FIB_ERR_NOMEM, "out of host memory");
+    FIB_RC(fib::use_device(device));
+    std::unique_ptr<fib_odf_plan> p(new fib_odf_plan());
     p->device = device; p->nvol = nvol; p->nvert = nverts / 2; p->nrows = p->nvert; p->nrow0 = 0;
     p->A.resize((size_t)p->nrows * nvol);
     fib::host_gqi_matrix(bval, bvec, nvol, verts, nverts, sigma, p->A.data());
     std::vector<float> eff((size_t)nvol, 1.0f);
-    rc = finish_plan(p, verts, nverts, faces, nfaces, eff, format);
-    if (rc != FIB_OK) { delete p; return rc; }
-    *plan = p;
+    FIB_RC(finish_plan(p.get(), verts, nverts, faces, nfaces, eff, format));
+    *plan = p.release();
     return FIB_OK;
 } FIB_API_CATCH
 
@@ -386,19 +361,16 @@ extern "C" int fib_dsi_plan_create(int device, const float *bval, const float *b
 extern "C" int fib_dsi_plan_create_fmt(int device, const float *bval, const float *bvec, int nvol,
                                        const float *verts, int nverts, const int32_t *faces, int nfaces,
                                        int hann_width, int format, fib_odf_plan **plan) try {
-    int rc = check_plan_args(bval, bvec, nvol, verts, nverts, faces, nfaces, plan);
-    if (rc != FIB_OK) return rc;
+    FIB_RC(check_plan_args(bval, bvec, nvol, verts, nverts, faces, nfaces, plan));
     FIB_CHECK(format >= FIB_ODF_FORMAT_DEFAULT && format <= FIB_ODF_FORMAT_F32, FIB_ERR_INVALID, "unknown operand format %d", format);
     FIB_CHECK(hann_width >= 0, FIB_ERR_INVALID, "hann_width must be >= 0");
     fib::DeviceGuard guard;
-    if ((rc = fib::use_device(device)) != FIB_OK) return rc;
-    fib_odf_plan *p = new (std::nothrow) fib_odf_plan();
-    FIB_CHECK(p != nullptr, FIB_ERR_NOMEM, "out of host memory");
+    FIB_RC(fib::use_device(device));
+    std::unique_ptr<fib_odf_plan> p(new fib_odf_plan());
     p->device = device; p->nvol = nvol; p->nvert = nverts / 2; p->nrows = nvol + p->nvert; p->nrow0 = nvol;
     p->A.resize((size_t)p->nrows * nvol);
     std::vector<int> iq;
-    rc = fib::host_dsi_matrix(bval, bvec, nvol, verts, nverts, hann_width, p->A.data(), &p->scale_frame, &p->scale_coef, &iq);
-    if (rc != FIB_OK) { delete p; return rc; }
+    FIB_RC(fib::host_dsi_matrix(bval, bvec, nvol, verts, nverts, hann_width, p->A.data(), &p->scale_frame, &p->scale_coef, &iq));
     // a frame overwritten by a later one on the same lattice point never reaches X (dsi.jl:205): its column is 0
     std::vector<float> eff((size_t)nvol, 0.0f);
     for (int j = 0; j < nvol; j++)
@@ -437,24 +409,17 @@ extern "C" int fib_dsi_plan_create_fmt(int device, const float *bval, const floa
                     for (int j = t0; j < std::min(nrep, t0 + KT); j++) if ((*side)[j] >= 0) { lo = std::min(lo, (*side)[j]); hi = std::max(hi, (*side)[j]); }
                     if (hi >= 0) p->fold_span_max = std::max(p->fold_span_max, hi - lo + 1);
                 }
-            if ((rc = p->foldA.alloc(nrep)) != FIB_OK || (rc = p->foldB.alloc(nrep)) != FIB_OK) { delete p; return rc; }
-            (void)hipMemcpy(p->foldA.p, fa.data(), nrep * sizeof(int32_t), hipMemcpyHostToDevice);
-            (void)hipMemcpy(p->foldB.p, fb.data(), nrep * sizeof(int32_t), hipMemcpyHostToDevice);
+            FIB_RC(fib::upload(p->foldA, fa));
+            FIB_RC(fib::upload(p->foldB, fb));
             eff.assign((size_t)nrep, 1.0f);
         }
     }
-    rc = finish_plan(p, verts, nverts, faces, nfaces, eff, format);
-    if (rc != FIB_OK) { delete p; return rc; }
-    *plan = p;
+    FIB_RC(finish_plan(p.get(), verts, nverts, faces, nfaces, eff, format));
+    *plan = p.release();
     return FIB_OK;
 } FIB_API_CATCH
 
-extern "C" void fib_odf_plan_destroy(fib_odf_plan *plan) try {
-    if (!plan) return;
-    fib::DeviceGuard guard;
-    (void)hipSetDevice(plan->device);
-    delete plan;
-} FIB_API_CATCH_VOID
+extern "C" void fib_odf_plan_destroy(fib_odf_plan *plan) try { fib::plan_destroy(plan); } FIB_API_CATCH_VOID
 
 extern "C" int fib_odf_plan_matrix(const fib_odf_plan *plan, float *A, int *nrows, int *nvol, int *nvert) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan is NULL");
@@ -785,17 +750,21 @@ int fib::matrix_plan_create(int device, const float *A, int nrows, int ncols, fi
     FIB_CHECK(A && plan && nrows > 0 && ncols > 0, FIB_ERR_INVALID, "invalid matrix plan arguments");
     *plan = nullptr;
     fib::DeviceGuard guard;
-    int rc = fib::use_device(device);
-    if (rc != FIB_OK) return rc;
-    fib_odf_plan *p = new (std::nothrow) fib_odf_plan();
-    FIB_CHECK(p != nullptr, FIB_ERR_NOMEM, "out of host memory");
+    FIB_RC(fib::use_device(device));
+    std::unique_ptr<fib_odf_plan> p(new fib_odf_plan());
     p->device = device; p->nvol = ncols; p->nvert = 2; p->nrows = nrows; p->nrow0 = 0;
     p->A.assign(A, A + (size_t)nrows * ncols);
     std::vector<float> eff((size_t)ncols, 1.0f);
-    rc = finish_plan(p, nullptr, 4, nullptr, 0, eff);
-    if (rc != FIB_OK) { delete p; return rc; }
-    *plan = p;
+    FIB_RC(finish_plan(p.get(), nullptr, 4, nullptr, 0, eff));
+    *plan = p.release();
     return FIB_OK;
+}
+
+// the plan of the peak finders that have no model of their own (fib_find_peaks*, CSD): only the folded neighbour table of the
+// tessellation is used, so it is a GQI plan of one dummy frame
+int fib::peaks_plan_create(int device, const float *verts, int nverts, const int32_t *faces, int nfaces, fib_odf_plan **plan) {
+    const float bval1[1] = {1000.0f}, bvec1[3] = {1.0f, 0.0f, 0.0f};
+    return fib_gqi_plan_create(device, bval1, bvec1, 1, verts, nverts, faces, nfaces, 1.25f, plan);
 }
 
 int fib::matrix_plan_run(const fib_odf_plan *plan, const float *S, const uint8_t *ones, int64_t n, float *out, bool recompact, void *stream) {

@@ -449,20 +449,13 @@ extern "C" int fib_prob_plan_create(int device, const float *vertices, int nvert
             if (fabsf(c) >= cosang_thresh) bits[(size_t)j * p->nchunk + (i >> 3)] |= (uint8_t)(1u << (i & 7));
             if (c > 0.0f) bits[half + (size_t)j * p->nchunk + (i >> 3)] |= (uint8_t)(1u << (i & 7));
         }
-    FIB_RC(p->bits.alloc(2 * half));
-    FIB_RC(p->U.alloc((size_t)3 * nvert));
-    FIB_HIP(hipMemcpy(p->bits.p, bits.data(), 2 * half, hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(p->U.p, vertices, sizeof(float) * 3 * nvert, hipMemcpyHostToDevice));
+    FIB_RC(fib::upload(p->bits, bits));
+    FIB_RC(fib::upload(p->U, vertices, (size_t)3 * nvert));
     *plan = p.release();
     return FIB_OK;
 } FIB_API_CATCH
 
-extern "C" void fib_prob_plan_destroy(fib_prob_plan *plan) try {
-    if (!plan) return;
-    fib::DeviceGuard guard;
-    (void)hipSetDevice(plan->device);
-    delete plan;
-} FIB_API_CATCH_VOID
+extern "C" void fib_prob_plan_destroy(fib_prob_plan *plan) try { fib::plan_destroy(plan); } FIB_API_CATCH_VOID
 
 extern "C" int fibd_prob_work_size(int64_t nlines, size_t *bytes) try {
     FIB_CHECK(bytes && nlines >= 0, FIB_ERR_INVALID, "NULL bytes or negative nlines");

@@ -314,23 +314,16 @@ struct fib_rumba_plan {
     // work arrays of a call (grow-only, kept for the next call on this plan: ten fresh GB cost ~0.3 s of hipMalloc per call;
     // a plan serves one call at a time)
     mutable fib::DevBuf<float> w_sig, w_dodf, w_ir, w_x, w_fodf, w_fodf2, w_rl, w_rl2;
+    ~fib_rumba_plan() { fib_odf_plan_destroy(pT); fib_odf_plan_destroy(pK); }
 };
 
-extern "C" void fib_rumba_plan_destroy(fib_rumba_plan *p) try {
-    if (!p) return;
-    fib::DeviceGuard guard;
-    (void)hipSetDevice(p->device);
-    fib_odf_plan_destroy(p->pT);
-    fib_odf_plan_destroy(p->pK);
-    delete p;
-} FIB_API_CATCH_VOID
+extern "C" void fib_rumba_plan_destroy(fib_rumba_plan *plan) try { fib::plan_destroy(plan); } FIB_API_CATCH_VOID
 
 extern "C" int fib_rumba_plan_create(int device, const float *bval, const float *bvec, int nvol, const float *verts, int nverts,
                                      float lam_para, float lam_perp, float lam_csf, float lam_gm, fib_rumba_plan **plan) try {
     FIB_CHECK(plan != nullptr, FIB_ERR_INVALID, "plan output pointer is NULL");
     *plan = nullptr;
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");   // rusd.jl:421
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");              // rusd.jl:425
+    FIB_RC(fib::check_tables(bval, bvec, nvol));                                                                      // rusd.jl:421, 425
     FIB_CHECK(verts && nverts >= 2 && nverts % 2 == 0, FIB_ERR_INVALID, "invalid ODF tessellation");
     const int nvert = nverts / 2;
     double ang_neig;
@@ -338,11 +331,8 @@ extern "C" int fib_rumba_plan_create(int device, const float *bval, const float 
     else if (nvert == 181) ang_neig = 16.0;                       // sphere_362 (:478-479)
     else return fib::fail(FIB_ERR_UNSUPPORTED, "rumba_rec defines its peak neighbourhood for sphere_362/642/724 only (rusd.jl:476-480)");
     fib::DeviceGuard guard;
-    int rc = fib::use_device(device);
-    if (rc != FIB_OK) return rc;
-    fib_rumba_plan *p = new (std::nothrow) fib_rumba_plan();
-    FIB_CHECK(p != nullptr, FIB_ERR_NOMEM, "out of host memory");
-    struct Guard { fib_rumba_plan *p; bool ok = false; ~Guard() { if (!ok) fib_rumba_plan_destroy(p); } } gd{p};
+    FIB_RC(fib::use_device(device));
+    std::unique_ptr<fib_rumba_plan> p(new fib_rumba_plan());
     p->device = device; p->nvol = nvol; p->nvert = nvert; p->ncomp = nvert + 2;
     float bmin = bval[0];
     for (int i = 1; i < nvol; i++) bmin = bval[i] < bmin ? bval[i] : bmin;
@@ -380,8 +370,8 @@ extern "C" int fib_rumba_plan_create(int device, const float *bval, const float 
     }
     std::vector<float> KT((size_t)ncomp * ndir);
     for (int r = 0; r < ndir; r++) for (int k = 0; k < ncomp; k++) KT[k + (size_t)ncomp * r] = p->K[r + (size_t)ndir * k];
-    if ((rc = fib::matrix_plan_create(device, KT.data(), ncomp, ndir, &p->pT)) != FIB_OK) return rc;
-    if ((rc = fib::matrix_plan_create(device, p->K.data(), ndir, ncomp, &p->pK)) != FIB_OK) return rc;
+    FIB_RC(fib::matrix_plan_create(device, KT.data(), ncomp, ndir, &p->pT));
+    FIB_RC(fib::matrix_plan_create(device, p->K.data(), ndir, ncomp, &p->pK));
     // peak neighbourhoods (rusd.jl:475-493)
     std::vector<int32_t> off(nvert + 1, 0), idx;
     std::vector<float> v3((size_t)nvert * 3);
@@ -401,17 +391,15 @@ extern "C" int fib_rumba_plan_create(int device, const float *bval, const float 
     std::vector<float> f0((size_t)ncomp), d0((size_t)ndir, 0.0f);
     { float s = 0.0f; for (int k = 0; k < ncomp; k++) { f0[k] = 1.0f / (float)(2 * nvert + 2); s += f0[k]; } for (int k = 0; k < ncomp; k++) f0[k] = f0[k] / s; }
     for (int r = 0; r < ndir; r++) { float s = 0.0f; for (int k = 0; k < ncomp; k++) s += p->K[r + (size_t)ndir * k] * f0[k]; d0[r] = s; }
-    auto up = [&](auto &buf, const auto &host) -> int {
-        int r2 = buf.alloc(host.size());
-        if (r2 != FIB_OK) return r2;
-        FIB_HIP(hipMemcpy(buf.p, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice));
-        return FIB_OK;
-    };
-    if ((rc = up(p->d_b0, p->b0_frames)) != FIB_OK || (rc = up(p->d_dw, p->dw_frames.empty() ? std::vector<int32_t>{0} : p->dw_frames)) != FIB_OK ||
-        (rc = up(p->d_nb_off, off)) != FIB_OK || (rc = up(p->d_nb_idx, idx.empty() ? std::vector<int32_t>{0} : idx)) != FIB_OK ||
-        (rc = up(p->d_verts, v3)) != FIB_OK || (rc = up(p->d_fodf0, f0)) != FIB_OK || (rc = up(p->d_dodf0, d0)) != FIB_OK) return rc;
-    gd.ok = true;
-    *plan = p;
+    const std::vector<int32_t> none{0};                           // (an empty list is uploaded as one zero)
+    FIB_RC(fib::upload(p->d_b0, p->b0_frames));
+    FIB_RC(fib::upload(p->d_dw, p->dw_frames.empty() ? none : p->dw_frames));
+    FIB_RC(fib::upload(p->d_nb_off, off));
+    FIB_RC(fib::upload(p->d_nb_idx, idx.empty() ? none : idx));
+    FIB_RC(fib::upload(p->d_verts, v3));
+    FIB_RC(fib::upload(p->d_fodf0, f0));
+    FIB_RC(fib::upload(p->d_dodf0, d0));
+    *plan = p.release();
     return FIB_OK;
 } FIB_API_CATCH
 

@@ -443,8 +443,7 @@ extern "C" int fib_device_count(void) try {
 
 extern "C" int fib_dki_design(const float *bval, const float *bvec, int nvol, float *A, float *pA, int *rank) try {
     if (rank) *rank = 0;
-    FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
-    FIB_CHECK(bvec != nullptr, FIB_ERR_MISSING_BVEC, "Missing gradient table from input DWI structure");
+    FIB_RC(fib::check_tables(bval, bvec, nvol));
     std::vector<double> Ad((size_t)nvol * 22), pd((size_t)nvol * 22);
     const int r = fib::host_dki_design(bval, bvec, nvol, Ad.data(), pd.data());
     if (rank) *rank = r;

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._dev import Launch, Plan, tensor
-from .dti import DTI_FIELDS, _check_tables, _dwi_arg, _fit_args, _mask_checked
+from .dti import DTI_FIELDS, _check_tables, _table_args, _dwi_arg, _fit_args, _mask_checked
 from .mri import MRI
 from .odf import ODF, sphere_642
 
@@ -55,11 +55,8 @@ def _verts(odf_dirs: ODF):
 def dki_design(bval, bvec):
     """The fit's tables, built on the host in float64 and rounded once: (A [nvol, 22] with b in ms/um^2, pA [22, nvol] scaled to
     mm^2/s and mm^4/s^2, rank).  A scheme whose design has a rank below 22 raises FibersError (code -1)."""
-    bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
+    bval, bv = _table_args(bval, bvec)
     nvol = int(bval.shape[0])
-    bv = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
-    if bv.shape[0] != nvol:
-        raise ValueError("gradient table must be [%d x 3], got %s" % (nvol, bv.shape))
     A = np.zeros((nvol, 22), np.float32, order="F")
     pA = np.zeros((22, nvol), np.float32, order="F")
     rank = C.c_int(0)
@@ -95,11 +92,8 @@ class DkiPlan(Plan):
                  min_diffusivity: float = DEFAULTS["min_diffusivity"], min_kurtosis: float = DEFAULTS["min_kurtosis"],
                  max_kurtosis: float = DEFAULTS["max_kurtosis"], device: int = 0):
         Plan.__init__(self, device)
-        bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
+        bval, bv = _table_args(bval, bvec)
         self.nvol = int(bval.shape[0])
-        bv = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
-        if bv.shape[0] != self.nvol:
-            raise ValueError("gradient table must be [%d x 3], got %s" % (self.nvol, bv.shape))
         v = _verts(odf_dirs)
         self.ndir = odf_dirs.nvert
         p = _params(min_signal, min_diffusivity, min_kurtosis, max_kurtosis)

@@ -49,6 +49,18 @@ def _dwi_arg(dwi):
     return dwi.vol if dwi.vol.flags.f_contiguous else np.asfortranarray(dwi.vol)
 
 
+def _table_args(bval, bvec, need_bvec=True):
+    """A b-table as the C ABI reads it: (bval float32 contiguous [nvol], bvec float32 Fortran-ordered [nvol, 3], or None where
+    the form needs no gradient table).  A gradient table of another row count would be read past its end: ValueError."""
+    bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
+    if not need_bvec:
+        return bval, None
+    bvec = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
+    if bvec.shape[0] != bval.shape[0]:
+        raise ValueError("gradient table must be [%d x 3], got %s" % (bval.shape[0], bvec.shape))
+    return bval, bvec
+
+
 def _check_tables(dwi, need_bvec=True):
     """The reference's table checks (dti.jl:166-168, 223-229) plus the shapes the C ABI relies on.  Returns
     (bval float32 contiguous [nframes], bvec float32 Fortran-ordered [nframes, 3] or None): the arrays whose pointers go
@@ -115,9 +127,8 @@ class DtiPlan(Plan):
 
     def __init__(self, bval, bvec=None, device: int = 0):
         Plan.__init__(self, device)
-        bval = np.ascontiguousarray(bval, np.float32)
+        bval, bv = _table_args(bval, bvec, need_bvec=bvec is not None)
         self.nvol = int(bval.shape[0])
-        bv = None if bvec is None else np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
         _lib.check(_lib.lib().fib_dti_plan_create(device, bval.ctypes.data, None if bv is None else bv.ctypes.data,
                                                   self.nvol, C.byref(self._h)))
         self.np = 7 if bv is not None else 2

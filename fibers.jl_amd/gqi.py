@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._dev import ArgError, Launch, Plan, stream_ptr, tensor
-from .dti import _check_tables, _dwi_arg, _fit_args, _mask_arg, _mask_checked
+from .dti import _check_tables, _table_args, _dwi_arg, _fit_args, _mask_arg, _mask_checked
 from .mri import MRI
 from .odf import ODF, sphere_642
 
@@ -135,8 +135,7 @@ class OdfPlan(Plan):
         fmt = ODF_FORMATS[format]
         Plan.__init__(self, device)
         self.kind = kind
-        bval = np.ascontiguousarray(bval, np.float32)
-        bvec = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
+        bval, bvec = _table_args(bval, bvec)
         v, f = _odf_args(odf_dirs)
         L = _lib.lib()
         self.nvol, self.nvert = int(bval.shape[0]), odf_dirs.nvert

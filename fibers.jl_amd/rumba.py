@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._dev import ArgError, Launch, Plan, tensor
-from .dti import _check_tables, _dwi_arg, _mask_checked
+from .dti import _check_tables, _table_args, _dwi_arg, _mask_checked
 from .mri import MRI
 from .odf import ODF, sphere_724
 
@@ -65,8 +65,7 @@ class RumbaPlan(Plan):
     def __init__(self, bval, bvec, odf_dirs: ODF = sphere_724, lam_para=1.7e-3, lam_perp=0.2e-3, lam_csf=3.0e-3,
                  lam_gm=0.8e-4, device: int = 0):
         Plan.__init__(self, device)
-        bval = np.ascontiguousarray(bval, np.float32)
-        bvec = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
+        bval, bvec = _table_args(bval, bvec)
         v = np.asfortranarray(odf_dirs.vertices, dtype=np.float32)
         self.nvert, self.nvol = odf_dirs.nvert, int(bval.shape[0])
         _lib.check(_lib.lib().fib_rumba_plan_create(device, bval.ctypes.data, bvec.ctypes.data, self.nvol, v.ctypes.data,
