@@ -48,7 +48,7 @@ constexpr int WG_VOX = 128;   // voxels per workgroup (4 waves x 32)
 // plan
 // ------------------------------------------------------------------------------------------
 struct fib_odf_plan {
-    int device = 0;
+    int device = 0, ncu = 256;                       // ncu: compute units of `device` (the persistent grids)
     int nvol = 0, nvert = 0, nrows = 0, nrow0 = 0;   // nrow0 = rows that go to the pdf output (DSI), else 0
     int MB = 11, NX = 0, ntile_m = 1, Kpad = 0, maxdeg = 0;   // M tile = MB 32-row MFMA blocks + NX VALU rows
     int scale_frame = -1;
@@ -120,6 +120,7 @@ int finish_plan(fib_odf_plan *p, const float *verts, int nverts, const int32_t *
                 const std::vector<float> &frame_eff, int format = FIB_ODF_FORMAT_DEFAULT) {
     if (p->G.empty()) { p->G = p->A; p->gM = p->nrows; p->gK = p->nvol; p->gRow0 = p->nrow0; }
     const int M = p->gM, K = p->gK;
+    if (hipDeviceGetAttribute(&p->ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess) p->ncu = 256;
     // the operand format of the contraction (header: FIB_ODF_FORMAT_*): two fp16 pieces per f32 operand (default), three exact
     // bf16 pieces, or v_mfma_f32_32x32x2_f32 (a k-ordered f32 fma chain, bit-identical to the oracle's loop)
     format = resolve_format(format);
@@ -436,55 +437,198 @@ extern "C" int fib_odf_plan_matrix(const fib_odf_plan *plan, float *A, int *nrow
 namespace {
 
 constexpr int FOLD_MB_MAX = 10;   // M tiles that the fused-fold variant is built for (room for 16 raw samples per lane and stage)
-template <int MB, int NX>
-void launch_gemm(const GemmArgs &ga, unsigned grid, hipStream_t st) {
-    if (ga.At3) {
-        // persistent grid: one 8-wave workgroup per CU (two 4-wave workgroups per CU were measured 6 % slower), a multiple of 8
-        // so that blockIdx & 7 is the XCD
-        int ncu = 256, dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        GemmArgs g2 = ga;
-        const int nw = 8;
-        const int64_t items = fib::cdiv(ga.nvox, nw * 32) * ga.ntile_m;
-        unsigned pg = (unsigned)std::min<int64_t>((int64_t)ncu * (8 / nw), items);
-        pg = (pg + 7) / 8 * 8;
-        auto go = [&](auto h2_) {
-            constexpr bool H2 = decltype(h2_)::value;
-            if (ga.fold) {
-                if constexpr (MB <= FOLD_MB_MAX) hipLaunchKernelGGL((odf_gemm3_kernel<MB, NX, 8, true, false, H2>), dim3(pg), dim3(512), 0, st, g2);
-                return;
-            }
-            if constexpr (MB == 10 && NX == 1) {
-                if (ga.mean_hi) { hipLaunchKernelGGL((odf_gemm3_kernel<10, 1, 8, false, true, H2>), dim3(pg), dim3(512), 0, st, g2); return; }
-            }
-            hipLaunchKernelGGL((odf_gemm3_kernel<MB, NX, 8, false, false, H2>), dim3(pg), dim3(512), 0, st, g2);
-        };
-        if (ga.h2) go(std::true_type{}); else go(std::false_type{});
+// odf_post_kernel's workgroups.  FIB_ODF_NORMALIZE relies on ALL of them being resident at once: every workgroup waits for the divisor
+// that the last one to arrive publishes, and nothing checks that the device can hold them.
+constexpr int POST_GRID = 384;
+
+// Which kernels one call takes.  odf_route() is the only place that decides; the scratch, the argument builders and the launches
+// below read it and decide nothing themselves.
+struct OdfRoute {
+    bool compact = false;     // launch 1 runs: the voxel and tile lists are (re)built
+    bool split = false;       // the contraction runs on the piece-split images (odf_gemm3_kernel / odf_dsi2_kernel), else odf_gemm_kernel
+    bool fused = false;       // .. and finds the peaks on its accumulators (sphere_642 GQI: gemm3_epilogue_fused)
+    bool dsi2 = false;        // .. as odf_dsi2_kernel (folded DSI on sphere_642: fused ODF tile + pdf tile)
+    bool fold_fused = false;  // a folded lattice's antipodal pairs are summed inside the contraction's sample load ..
+    bool fold_pre = false;    // .. or by a pre-pass into the plan's scratch,
+    bool fold4 = false;       // .. which is dsi_fold4_kernel (16-byte accesses), else dsi_fold_kernel
+    bool inf_fix = false;     // GQI on the split images: voxels with a +Inf sample are listed and recomputed
+    bool peaks = false;       // separate peak finder on the stored ODF (other tessellations, unaligned pieces, FIB_ODF_SEPARATE_PEAKS)
+    bool vec_ok = false;      // the output rows take 16-byte stores
+    bool scan() const { return fused || dsi2; }   // find_peaks! ran inside the contraction: redo list instead of a peak finder
+};
+
+// out16: nvox % 4 == 0 and the outputs 16-byte aligned; in16: nvox % 4 == 0, dwi 16-byte and mask 4-byte aligned
+OdfRoute odf_route(const fib_odf_plan *plan, int64_t nvox, bool out16, bool in16, int flags) {
+    OdfRoute r;
+    const bool sep = (flags & FIB_ODF_SEPARATE_PEAKS) != 0;
+    r.compact = true;
+    r.vec_ok = out16;
+    r.split = plan->split_bf16 && nvox <= ((int64_t)1 << 26);
+    r.inf_fix = r.split && plan->Gdev.p != nullptr;      // (no cap: the list holds every voxel)
+    r.fused = plan->fused && r.split && out16 && !sep;
+    const bool fold_ok = plan->folded && r.split && plan->Kpad <= FKMAX && plan->scale_frame_raw >= 0 &&
+                         (int64_t)plan->fold_span_max * nvox * 4 < (int64_t)0xE0000000ll;
+    r.dsi2 = plan->dsi2 && fold_ok && out16 && !sep;
+    r.fold_fused = (fold_ok && plan->MB <= FOLD_MB_MAX) || r.dsi2;
+    r.fold_pre = plan->folded && !r.fold_fused;
+    r.fold4 = r.fold_pre && in16;
+    r.peaks = !r.scan();
+    return r;
+}
+
+// every grow-only buffer the route needs (the compaction's own state: launch_mask_compact)
+int odf_scratch(const fib_odf_plan *plan, const OdfRoute &r, int64_t nvox) {
+    if (r.compact) {
+        FIB_RC(plan->live_vox.ensure((size_t)nvox));
+        FIB_RC(plan->live_tiles.ensure((size_t)fib::cdiv(nvox, 64)));
     }
-    else hipLaunchKernelGGL((odf_gemm_kernel<MB, NX>), dim3(grid), dim3(256), 0, st, ga);
+    if (r.inf_fix) FIB_RC(plan->inf_list.ensure((size_t)nvox));
+    if (r.scan() || r.peaks) FIB_RC(plan->mean_hi.ensure((size_t)nvox + 4));   // whoever finds the peaks bounds each voxel's mean
+    if (r.scan()) FIB_RC(plan->redo_list.ensure((size_t)nvox));
+    if (r.fold_pre) FIB_RC(plan->folded_dwi.ensure((size_t)plan->gK * nvox));
+    return FIB_OK;
+}
+
+// ---- the arguments of the contraction kernels ----
+// persistent grid of the split kernels: one 8-wave workgroup per CU (two 4-wave workgroups per CU were measured 6 % slower) or one per
+// work item if those are fewer, a multiple of `unit` (8: blockIdx & 7 is the XCD; 16: an even number of workgroups per XCD)
+unsigned persistent_grid(const fib_odf_plan *plan, const GemmArgs &ga, unsigned unit) {
+    const int64_t items = fib::cdiv(ga.nvox, 8 * 32) * ga.ntile_m;
+    const unsigned pg = (unsigned)std::min<int64_t>((int64_t)plan->ncu, items);
+    return (pg + unit - 1) / unit * unit;
+}
+
+// what both callers set (fibd_odf_rec, fib::matrix_plan_run): images, lists, outputs, sizes, the DSI scale and fold tables.  S: the
+// samples the kernel reads (the raw frames, or the fold pre-pass's scratch)
+GemmArgs gemm_args(const fib_odf_plan *plan, const OdfRoute &r, const float *S, const uint8_t *mask, float *out0, float *out1, int64_t nvox) {
+    GemmArgs ga{};
+    ga.At = plan->At.p; ga.S = S;
+    if (!r.scan()) { ga.At3 = r.split ? plan->At3.p : nullptr; ga.Aextra = plan->Aextra.p; }
+    ga.h2 = plan->h2 ? 1 : 0; ga.h2_inv_sa = 1.0f / plan->h2_sa;
+    ga.vidx = plan->live_vox.p; ga.nlive = plan->live_counts.p; ga.mask = mask; ga.effbits = plan->effbits.p;
+    ga.out0 = out0; ga.out1 = out1; ga.nvox = nvox; ga.stride = nvox; ga.vec_ok = r.vec_ok ? 1 : 0;
+    ga.K = plan->gK; ga.Kpad = plan->Kpad; ga.M = plan->gM; ga.nrow0 = plan->gRow0;
+    if (!r.dsi2) ga.ntile_m = plan->ntile_m;
+    ga.fold = r.fold_fused ? 1 : 0;
+    ga.rowA = plan->foldA.p; ga.rowB = plan->foldB.p;   // (NULL unless the plan is folded)
+    ga.scale_frame = plan->nrow0 > 0 ? (r.fold_fused ? plan->scale_frame_raw : plan->scale_frame) : -1;
+    ga.scale_coef = plan->scale_coef;
+    ga.has_ineff = plan->has_ineff ? 1 : 0;
+    return ga;
+}
+
+// + find_peaks! inside the contraction (gemm3_epilogue_fused): the image in the row order of sphere642_fused.inc, the peak outputs, the
+// redo list
+void add_scan_args(GemmArgs &ga, const fib_odf_plan *plan, float *const peak[3], float *const qa[3]) {
+    ga.At3 = plan->At3f.p; ga.Aextra = plan->Aextraf.p;
+    for (int k = 0; k < 3; k++) { ga.peak[k] = peak[k]; ga.qa[k] = qa[k]; }
+    ga.verts = plan->verts.p; ga.maxenc = plan->maxenc.p; ga.mean_hi = plan->mean_hi.p;
+    ga.redo_count = plan->live_counts.p + 3; ga.redo_list = plan->redo_list.p; ga.redo_cap = (int)std::min<int64_t>(ga.nvox, INT32_MAX);
+    { const char *pa = fib::ab_env("FIBERS_ODF_ANTI"); ga.anti = pa ? atoi(pa) : 3; }   // bit 0: anti-phase wave halves, bit 1: s_setprio around the MFMA block (default both; 0 = neither)
+}
+
+// + odf_dsi2_kernel: the pdf tile's image, two tiles per voxel group, the split of an XCD's workgroups between them
+void add_dsi2_args(GemmArgs &ga, const fib_odf_plan *plan) {
+    ga.At3b = plan->At3b.p;
+    ga.ntile_m = 2;
+    const int nslot = (int)persistent_grid(plan, ga, 16) / 8;
+    // share of the ODF tile's cost per voxel group (tools/dsi_na_sweep.py, 140^3 x 515: 68 us per ODF item, 59.7 per pdf item of 9
+    // blocks; ~4.5 us per block): 17 of 32 workgroups per XCD for the 515-point lattice
+    const double ca = 68.0, cb = 19.0 + 4.5 * plan->MBB;
+    int na = (int)(nslot * ca / (ca + cb) + 0.5);
+    // The pdf-tile workgroups follow the ODF-tile ones through the XCD's voxel groups (see gemm3_body: a bounded wait on the
+    // partner's item counter), so the samples are fetched from HBM once and the second reader finds them in the XCD's L2 --
+    // [r4] for any split, not only 16 | 16 (FIBERS_DSI_NA=<n> sets the split, FIBERS_DSI_PAIR=0 switches the waiting off:
+    // tools/dsi_na_sweep.py).
+    const char *ena = fib::ab_env("FIBERS_DSI_NA");
+    if (ena) na = atoi(ena);
+    ga.dsi_na = std::max(1, std::min(nslot - 1, na));
+    const char *epair = fib::ab_env("FIBERS_DSI_PAIR");
+    if (plan->pair_flags.p && nslot <= 32 && !(epair && epair[0] == '0')) ga.pair_flags = plan->pair_flags.p;   // (the counters were cleared by mask_compact_kernel)
+}
+
+// ---- launch 2: the contraction ----
+template <int MB, int NX, bool H2>
+void launch_split(const OdfRoute &r, const GemmArgs &ga, unsigned pg, hipStream_t st) {
+    if (r.fold_fused) {
+        if constexpr (MB <= FOLD_MB_MAX) hipLaunchKernelGGL((odf_gemm3_kernel<MB, NX, 8, true, false, H2>), dim3(pg), dim3(512), 0, st, ga);
+        return;
+    }
+    if constexpr (MB == 10 && NX == 1) {
+        if (r.fused) { hipLaunchKernelGGL((odf_gemm3_kernel<10, 1, 8, false, true, H2>), dim3(pg), dim3(512), 0, st, ga); return; }
+    }
+    hipLaunchKernelGGL((odf_gemm3_kernel<MB, NX, 8, false, false, H2>), dim3(pg), dim3(512), 0, st, ga);
+}
+
+template <int MBB>
+void launch_dsi2(const GemmArgs &ga, unsigned pg, hipStream_t st) {
+    hipLaunchKernelGGL((ga.h2 ? odf_dsi2_kernel<MBB, true> : odf_dsi2_kernel<MBB, false>), dim3(pg), dim3(512), 0, st, ga);
+}
+
+// the M tiles the kernels are built for (finish_plan picks among them): MB 32-row MFMA blocks + NX VALU rows
+template <int MB_, int NX_> struct Tile { static constexpr int MB = MB_, NX = NX_; };
+template <typename... T> struct Tiles {};
+using GemmTiles = Tiles<Tile<5, 0>, Tile<6, 0>, Tile<7, 0>, Tile<8, 0>, Tile<9, 0>, Tile<10, 0>, Tile<11, 0>,
+                        Tile<5, 1>, Tile<6, 1>, Tile<7, 1>, Tile<8, 1>, Tile<9, 1>, Tile<10, 1>>;
+
+template <typename T>
+bool launch_tile(const fib_odf_plan *plan, const OdfRoute &r, const GemmArgs &ga, hipStream_t st) {
+    if (plan->MB != T::MB || plan->NX != T::NX) return false;
+    if (!r.split)
+        hipLaunchKernelGGL((odf_gemm_kernel<T::MB, T::NX>), dim3((unsigned)(fib::cdiv(ga.nvox, WG_VOX) * plan->ntile_m)), dim3(256), 0, st, ga);
+    else (ga.h2 ? launch_split<T::MB, T::NX, true> : launch_split<T::MB, T::NX, false>)(r, ga, persistent_grid(plan, ga, 8), st);
+    return true;
+}
+template <typename... T>
+bool launch_tiles(Tiles<T...>, const fib_odf_plan *plan, const OdfRoute &r, const GemmArgs &ga, hipStream_t st) {
+    return (launch_tile<T>(plan, r, ga, st) || ...);
+}
+
+// odf_dsi2_kernel<MBB, H2>, odf_gemm3_kernel<MB, NX, ..> or odf_gemm_kernel<MB, NX> on the finished arguments
+int launch_contraction(const fib_odf_plan *plan, const OdfRoute &r, const GemmArgs &ga, const char *label, hipStream_t st) {
+    fib::ProfScope prof(label, st);
+    if (r.dsi2) {
+        const unsigned pg = persistent_grid(plan, ga, 16);
+        switch (plan->MBB) {
+            case 5:  launch_dsi2<5>(ga, pg, st); break;
+            case 7:  launch_dsi2<7>(ga, pg, st); break;
+            default: launch_dsi2<9>(ga, pg, st); break;
+        }
+    } else if (!launch_tiles(GemmTiles{}, plan, r, ga, st))
+        return fib::fail(FIB_ERR_INVALID, "internal: no GEMM variant for MB=%d NX=%d", plan->MB, plan->NX);
+    FIB_HIP(hipGetLastError());
+    return FIB_OK;
 }
 
 size_t peaks_smem(const fib_odf_plan *p) {
     return ((size_t)(p->rows_pad + 1) * PV + (size_t)PG * PV * PREC) * sizeof(float);
 }
 
-template <int DEG, bool EXACT>
-int launch_peaks_t(const PeakArgs &pa, size_t smem, unsigned grid, hipStream_t st) {
-    FIB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(odf_peaks_kernel<DEG, EXACT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL((odf_peaks_kernel<DEG, EXACT>), dim3(grid), dim3(PW * 64), smem, st, pa);
+// a peak finder's launch: its dynamic LDS size is allowed first
+template <typename... K, typename... A>
+int launch_lds(void (*kernel)(K...), unsigned grid, unsigned block, size_t smem, hipStream_t st, const A &...args) {
+    FIB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, st, args...);
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 }
 
-template <int DEG, bool EXACT>
-int launch_peaks64_t(const PeakArgs &pa, size_t smem, int64_t ntiles, unsigned grid, hipStream_t st) {
-    FIB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(odf_peaks64_kernel<DEG, EXACT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL((odf_peaks64_kernel<DEG, EXACT>), dim3(grid), dim3(P64_T), smem, st, pa, ntiles);
-    FIB_HIP(hipGetLastError());
-    return FIB_OK;
+// the two generic peak finders, each a launcher of its <DEG, EXACT> instance
+struct Peaks32 {                                        // odf_peaks_kernel: 32-voxel tiles
+    const PeakArgs &pa; size_t smem; unsigned grid; hipStream_t st;
+    template <int DEG, bool EXACT> int launch() const { return launch_lds(odf_peaks_kernel<DEG, EXACT>, grid, PW * 64, smem, st, pa); }
+};
+struct Peaks64 {                                        // odf_peaks64_kernel: 64-voxel tiles, persistent
+    const PeakArgs &pa; size_t smem; int64_t ntiles; unsigned grid; hipStream_t st;
+    template <int DEG, bool EXACT> int launch() const { return launch_lds(odf_peaks64_kernel<DEG, EXACT>, grid, P64_T, smem, st, pa, ntiles); }
+};
+
+// the one degree / exactness dispatch: f.launch<DEG, EXACT>() for the plan's padded degree (6, 8, else 16)
+template <typename F>
+int launch_degree(int deg_pad, bool exact, const F &f) {
+    if (deg_pad == 6) return exact ? f.template launch<6, true>() : f.template launch<6, false>();
+    if (deg_pad == 8) return exact ? f.template launch<8, true>() : f.template launch<8, false>();
+    return exact ? f.template launch<16, true>() : f.template launch<16, false>();
 }
 
 int launch_peaks(const fib_odf_plan *plan, const float *odf, int64_t nvox, int64_t stride, float *const peak[3], float *const qa[3],
@@ -506,34 +650,29 @@ int launch_peaks(const fib_odf_plan *plan, const float *odf, int64_t nvox, int64
     fib::ProfScope prof("odf_peaks", st);
     const size_t smem64 = ((size_t)(plan->nvert + 1) * 64 + (size_t)P64_W * 64 * PREC + (size_t)plan->nvert * (plan->deg_pad + 3)) * sizeof(float);
     if (!small_tiles && plan->nvert * 16 <= P64_NI * P64_T && smem64 <= 160 * 1024) {
-        int ncu = 256;
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, plan->device);
         const int64_t ntiles = fib::cdiv(nvox, 64);
-        const unsigned g64 = (unsigned)std::min<int64_t>(ntiles, ncu);
+        const unsigned g64 = (unsigned)std::min<int64_t>(ntiles, plan->ncu);
         if (plan->is_s642 && !exact) {
             const size_t smem642 = ((size_t)(FIB_S642_NVERT + 1) * 64 + (size_t)PQ_CAP * 64 * 2 + 128 + 2 * P64_W * 64 + 2 * 8 * 64 +
                                     (size_t)FIB_S642_NVERT * 3) * sizeof(float);
-            FIB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(odf_peaks642_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem642));
-            hipLaunchKernelGGL(odf_peaks642_kernel, dim3(g64), dim3(P64_T), smem642, st, pa, ntiles);
-            FIB_HIP(hipGetLastError());
-            return FIB_OK;
+            return launch_lds(odf_peaks642_kernel, g64, P64_T, smem642, st, pa, ntiles);
         }
-        switch (plan->deg_pad) {
-            case 6:  return exact ? launch_peaks64_t<6, true>(pa, smem64, ntiles, g64, st) : launch_peaks64_t<6, false>(pa, smem64, ntiles, g64, st);
-            case 8:  return exact ? launch_peaks64_t<8, true>(pa, smem64, ntiles, g64, st) : launch_peaks64_t<8, false>(pa, smem64, ntiles, g64, st);
-            default: return exact ? launch_peaks64_t<16, true>(pa, smem64, ntiles, g64, st) : launch_peaks64_t<16, false>(pa, smem64, ntiles, g64, st);
-        }
+        return launch_degree(plan->deg_pad, exact, Peaks64{pa, smem64, ntiles, g64, st});
     }
-    switch (plan->deg_pad) {
-        case 6:  return exact ? launch_peaks_t<6, true>(pa, smem, grid, st) : launch_peaks_t<6, false>(pa, smem, grid, st);
-        case 8:  return exact ? launch_peaks_t<8, true>(pa, smem, grid, st) : launch_peaks_t<8, false>(pa, smem, grid, st);
-        default: return exact ? launch_peaks_t<16, true>(pa, smem, grid, st) : launch_peaks_t<16, false>(pa, smem, grid, st);
-    }
+    return launch_degree(plan->deg_pad, exact, Peaks32{pa, smem, grid, st});
 }
 
-}  // namespace
+// ---- launch 1: mask compaction and clearing ----
+// a buffer of the compaction's state: allocated once (or grown) and cleared on the call's stream -- fresh granules carry epoch 0 =
+// "never written"
+template <typename T>
+int fresh_zeroed(fib::DevBuf<T> &buf, size_t n, hipStream_t st) {
+    if (buf.p && buf.n >= n) return FIB_OK;
+    FIB_RC(buf.alloc(n));
+    FIB_HIP(hipMemsetAsync(buf.p, 0, n * sizeof(T), st));
+    return FIB_OK;
+}
 
-namespace {
 // the one-launch mask compaction (mask_compact_kernel) on the plan's scratch; z != NULL: also clear those outputs outside the mask
 int launch_mask_compact(const fib_odf_plan *plan, const uint8_t *mask, int64_t nvox, unsigned *maxenc, const ZeroArgs *z, hipStream_t st) {
     // at most 256 chunks (one ticket each: returning atomics on one address are served at ~90 per microsecond), all resident at once
@@ -541,24 +680,13 @@ int launch_mask_compact(const fib_odf_plan *plan, const uint8_t *mask, int64_t n
     if (iters > CB_ITERS_MAX) iters = CB_ITERS_MAX;
     const int nchunks = (int)fib::cdiv(nvox, (int64_t)CB * iters);                      // <= 1024 (2^27 voxels)
     FIB_CHECK(nchunks <= 1024, FIB_ERR_UNSUPPORTED, "volume too large for the mask compaction");
-    int rc;
-    if ((rc = plan->live_vox.ensure((size_t)nvox)) != FIB_OK) return rc;
-    if ((rc = plan->live_tiles.ensure((size_t)fib::cdiv(nvox, 64))) != FIB_OK) return rc;
-    if (!plan->compact_state.p) {                                                       // fresh granules carry epoch 0 = "never written"
-        if ((rc = plan->compact_state.alloc(1024)) != FIB_OK) return rc;
-        FIB_HIP(hipMemsetAsync(plan->compact_state.p, 0, 1024 * sizeof(unsigned long long), st));
-    }
-    if (!plan->compact_state2.p) {
-        if ((rc = plan->compact_state2.alloc(1024)) != FIB_OK) return rc;
-        FIB_HIP(hipMemsetAsync(plan->compact_state2.p, 0, 1024 * sizeof(unsigned long long), st));
-        if ((rc = plan->compact_mode.alloc(2)) != FIB_OK) return rc;
+    FIB_RC(fresh_zeroed(plan->compact_state, 1024, st));
+    FIB_RC(fresh_zeroed(plan->compact_state2, 1024, st));
+    if (!plan->compact_mode.p) {
+        FIB_RC(plan->compact_mode.alloc(2));
         FIB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(plan->compact_mode.p), 1, 2, st));   // octets until a call's counts say otherwise
     }
-    const size_t nsub = (size_t)fib::cdiv(nvox, CB);
-    if (z && plan->compact_sub.n < nsub) {
-        if ((rc = plan->compact_sub.alloc(nsub)) != FIB_OK) return rc;
-        FIB_HIP(hipMemsetAsync(plan->compact_sub.p, 0, nsub * sizeof(unsigned long long), st));
-    }
+    if (z) FIB_RC(fresh_zeroed(plan->compact_sub, (size_t)fib::cdiv(nvox, CB), st));
     if (++plan->compact_epoch == 0u) plan->compact_epoch = 1u;
     CompactArgs c{};
     c.mask = mask; c.nvox = nvox; c.vidx = plan->live_vox.p; c.tiles = plan->live_tiles.p; c.state = plan->compact_state.p;
@@ -570,10 +698,7 @@ int launch_mask_compact(const fib_odf_plan *plan, const uint8_t *mask, int64_t n
     c.state2 = plan->compact_state2.p; c.mode = plan->compact_mode.p;
     const size_t noct = (size_t)fib::cdiv(nvox, 1024);
     if (z && noct * sizeof(unsigned) <= 48 * 1024) {           // (the clearing workgroups keep the bits in LDS: volumes up to 12.5 M voxels)
-        if (plan->compact_oct.n < noct) {
-            if ((rc = plan->compact_oct.alloc(noct)) != FIB_OK) return rc;
-            FIB_HIP(hipMemsetAsync(plan->compact_oct.p, 0, noct * sizeof(unsigned long long), st));
-        }
+        FIB_RC(fresh_zeroed(plan->compact_oct, noct, st));
         c.oct_bits = plan->compact_oct.p; c.oct_words = (int)noct;
     }
     { const char *e = fib::ab_env("FIBERS_COMPACT_UNKNOWN"); c.dbg_unknown = e ? atoi(e) : 0; }
@@ -582,6 +707,48 @@ int launch_mask_compact(const fib_odf_plan *plan, const uint8_t *mask, int64_t n
     // with outputs to clear: helpers behind the compacting workgroups, so that a volume that is mostly outside the mask is cleared by the whole chip
     const int grid = nchunks + (z ? 256 : 0);
     hipLaunchKernelGGL(mask_compact_kernel, dim3(grid), dim3(1024), c.oct_words * sizeof(unsigned), st, c);
+    FIB_HIP(hipGetLastError());
+    return FIB_OK;
+}
+
+// the fold pre-pass of a folded plan whose contraction does not fold (format f32, volumes past the fold-span limit)
+void launch_fold(const fib_odf_plan *plan, const OdfRoute &r, const float *dwi, const uint8_t *mask, int64_t nvox, hipStream_t st) {
+    fib::ProfScope prof("dsi_fold", st);
+    const unsigned grid = (unsigned)fib::cdiv(r.fold4 ? nvox / 4 : nvox, 256);          // (dsi_fold4_kernel: four voxels per thread)
+    hipLaunchKernelGGL(r.fold4 ? dsi_fold4_kernel : dsi_fold_kernel, dim3(grid), dim3(256), 0, st, dwi, mask, plan->foldA.p, plan->foldB.p,
+                       plan->gK, nvox, plan->folded_dwi.p);
+}
+
+// the contraction's arguments for a reconstruction call (after odf_scratch: the lists exist)
+GemmArgs odf_gemm_args(const fib_odf_plan *plan, const OdfRoute &r, const float *dwi, const uint8_t *mask, float *pdf, float *odf,
+                       float *const peak[3], float *const qa[3], int64_t nvox) {
+    GemmArgs ga = gemm_args(plan, r, r.fold_pre ? plan->folded_dwi.p : dwi, mask, pdf, odf, nvox);
+#ifdef FIB_CLOCK_STAMP
+    { const char *pi = fib::ab_env("FIBERS_PHASE_ITEM"); ga.phase_item = pi ? atoi(pi) : 2; }
+    { const char *pw = fib::ab_env("FIBERS_PHASE_WG"); ga.phase_wg = pw ? atoi(pw) : 8; }        // (odf_dsi2_kernel: 8 = an ODF-tile workgroup, 136 = a pdf-tile one)
+#endif
+    if (r.inf_fix) { ga.fix_count = plan->live_counts.p + 2; ga.fix_list = plan->inf_list.p; ga.fix_cap = (int)std::min<int64_t>(nvox, INT32_MAX); }
+    if (r.scan()) add_scan_args(ga, plan, peak, qa);
+    if (r.dsi2) add_dsi2_args(ga, plan);
+    return ga;
+}
+
+// launch 3: redo list (+ column repair), exact odfmax, its two floats, with FIB_ODF_NORMALIZE qa ./= odfmax
+int launch_post(const fib_odf_plan *plan, const OdfRoute &r, const GemmArgs &ga, const float *dwi, float *odf, float *const peak[3],
+                float *const qa[3], int64_t nvox, float *odfmax, int flags, hipStream_t st) {
+    fib::ProfScope prof("odf_post", st);
+    PostArgs pa{};
+    pa.redo = RedoArgs{odf, nvox, ga.redo_count, ga.redo_list, ga.redo_cap, plan->verts.p, {peak[0], peak[1], peak[2]}, {qa[0], qa[1], qa[2]}, plan->maxenc.p};
+    pa.G = (r.scan() && r.inf_fix) ? plan->Gdev.p : nullptr; pa.S = dwi; pa.out = odf; pa.M = plan->gM; pa.K = plan->gK;
+    pa.refine = RefineArgs{odf, nvox, nvox, plan->nvert, plan->live_vox.p, plan->live_counts.p, plan->mean_hi.p, plan->maxenc.p};
+    pa.arrive = plan->tickets.p + 1; pa.odfmax = odfmax; pa.raw = (flags & FIB_ODF_RAW_ODFMAX) ? 1 : 0;
+    pa.selctr = plan->selctr.p; pa.sellist = plan->sellist.p; pa.selcap = POST_SELCAP; pa.epoch = plan->compact_epoch;
+    if (flags & FIB_ODF_NORMALIZE) {                    // [r6] qa ./= odfmax in the same launch (gqi.jl:166-168)
+        for (int k = 0; k < 3; k++) pa.nq[k] = qa[k];
+        pa.nq_n = nvox; pa.done = reinterpret_cast<unsigned long long *>(plan->tickets.p + 2);
+    }
+    { const char *e = fib::ab_env("FIBERS_POST_SKIP"); pa.dbg = e ? atoi(e) : 0; }
+    hipLaunchKernelGGL(odf_post_kernel, dim3(POST_GRID), dim3(256), 0, st, pa);
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 }
@@ -595,154 +762,32 @@ extern "C" int fibd_odf_rec(const fib_odf_plan *plan, const float *dwi, const ui
     FIB_CHECK(nvox <= ((int64_t)1 << 27), FIB_ERR_UNSUPPORTED, "volumes of more than 2^27 voxels are not supported (32-bit lane offsets)");
     FIB_CHECK(plan->nrow0 == 0 || pdf != nullptr, FIB_ERR_INVALID, "DSI plans need a pdf output volume");
     for (int k = 0; k < 3; k++) FIB_CHECK(peak[k] && qa[k], FIB_ERR_INVALID, "NULL peak/qa output volume");
+    FIB_CHECK(fib::cdiv(nvox, WG_VOX) * plan->ntile_m < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "volume too large for one launch");
     fib::DeviceGuard guard;
     FIB_HIP(hipSetDevice(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    GemmArgs ga{};
-    // launch 1: compact the mask -- voxel list for the GEMM, 64-voxel tile list for the peak finder (counts stay on the device) -- and
-    // clear the outputs outside it
-    {
-        ZeroArgs z{};
-        z.out0 = pdf; z.out1 = odf; z.n0 = plan->nrow0; z.n1 = plan->nrows - plan->nrow0; z.nvox = nvox; z.stride = nvox;
-        for (int k = 0; k < 3; k++) { z.peak[k] = peak[k]; z.qa[k] = qa[k]; }
-        int rcc = launch_mask_compact(plan, mask, nvox, plan->maxenc.p, !(flags & FIB_ODF_PREZEROED) ? &z : nullptr, st);
-        if (rcc != FIB_OK) return rcc;
-    }
-    ga.At = plan->At.p; ga.At3 = (plan->split_bf16 && nvox <= ((int64_t)1 << 26)) ? plan->At3.p : nullptr; ga.S = dwi;
-    ga.Aextra = plan->Aextra.p; ga.h2 = plan->h2 ? 1 : 0; ga.h2_inv_sa = 1.0f / plan->h2_sa;
-#ifdef FIB_CLOCK_STAMP
-    { const char *pi = fib::ab_env("FIBERS_PHASE_ITEM"); ga.phase_item = pi ? atoi(pi) : 2; }
-    { const char *pw = fib::ab_env("FIBERS_PHASE_WG"); ga.phase_wg = pw ? atoi(pw) : 8; }        // (odf_dsi2_kernel: 8 = an ODF-tile workgroup, 136 = a pdf-tile one)
-#endif
-    ga.vec_ok = (nvox % 4 == 0 && ((uintptr_t)odf & 15) == 0 && (pdf == nullptr || ((uintptr_t)pdf & 15) == 0)) ? 1 : 0; ga.vidx = plan->live_vox.p; ga.nlive = plan->live_counts.p; ga.mask = mask; ga.effbits = plan->effbits.p;
-    ga.out0 = pdf; ga.out1 = odf; ga.nvox = nvox;
-    if (ga.At3 && plan->Gdev.p) {                        // GQI: voxels with a +Inf sample are listed and recomputed (no cap: the list holds every voxel)
-        int rci = plan->inf_list.ensure((size_t)nvox);
-        if (rci != FIB_OK) return rci;
-        ga.fix_count = plan->live_counts.p + 2; ga.fix_list = plan->inf_list.p; ga.fix_cap = (int)std::min<int64_t>(nvox, INT32_MAX);
-    }
-    // sphere_642 GQI plans: find_peaks! runs on the contraction kernel's accumulators (gemm3_epilogue_fused)
-    const bool sep = (flags & FIB_ODF_SEPARATE_PEAKS) != 0;
-    const bool fuse = plan->fused && ga.At3 != nullptr && ga.vec_ok && !sep;
-    {
-        int rcm = plan->mean_hi.ensure((size_t)nvox + 4);
-        if (rcm != FIB_OK) return rcm;
-    }
-    auto setup_fused = [&]() -> int {                   // the arguments of gemm3_epilogue_fused
-        int rcf = plan->redo_list.ensure((size_t)nvox);
-        if (rcf != FIB_OK) return rcf;
-        ga.At3 = plan->At3f.p; ga.Aextra = plan->Aextraf.p;
-        for (int k = 0; k < 3; k++) { ga.peak[k] = peak[k]; ga.qa[k] = qa[k]; }
-        ga.verts = plan->verts.p; ga.maxenc = plan->maxenc.p; ga.mean_hi = plan->mean_hi.p;
-        ga.redo_count = plan->live_counts.p + 3; ga.redo_list = plan->redo_list.p; ga.redo_cap = (int)std::min<int64_t>(nvox, INT32_MAX);
-        { const char *pa = fib::ab_env("FIBERS_ODF_ANTI"); ga.anti = pa ? atoi(pa) : 3; }   // bit 0: anti-phase wave halves, bit 1: s_setprio around the MFMA block (default both; 0 = neither)
-        return FIB_OK;
-    };
-    if (fuse) { int rcf = setup_fused(); if (rcf != FIB_OK) return rcf; }
-    ga.K = plan->gK; ga.Kpad = plan->Kpad; ga.M = plan->gM; ga.nrow0 = plan->gRow0; ga.ntile_m = plan->ntile_m;
-    const bool fold_ok = plan->folded && ga.At3 != nullptr && plan->Kpad <= FKMAX && plan->scale_frame_raw >= 0 &&
-                         (int64_t)plan->fold_span_max * nvox * 4 < (int64_t)0xE0000000ll;
-    const bool fuse_fold = fold_ok && plan->MB <= FOLD_MB_MAX;
-    // folded DSI on sphere_642: one launch of odf_dsi2_kernel does contraction, scale, ODF / pdf rows and find_peaks!
-    const bool dsi2 = plan->dsi2 && fold_ok && ga.vec_ok && !sep;
-    if (dsi2) {
-        int rcf = setup_fused();
-        if (rcf != FIB_OK) return rcf;
-        ga.At3b = plan->At3b.p;
-        ga.ntile_m = 2;
-    }
-    if (fuse_fold || dsi2) {
-        ga.fold = 1;
-        ga.rowA = plan->foldA.p; ga.rowB = plan->foldB.p;
-    } else if (plan->folded) {
-        int rcf = plan->folded_dwi.ensure((size_t)plan->gK * nvox);
-        if (rcf != FIB_OK) return rcf;
-        fib::ProfScope prof("dsi_fold", st);
-        if (nvox % 4 == 0 && ((uintptr_t)dwi & 15) == 0 && ((uintptr_t)mask & 3) == 0)
-            hipLaunchKernelGGL(dsi_fold4_kernel, dim3((unsigned)fib::cdiv(nvox / 4, 256)), dim3(256), 0, st, dwi, mask, plan->foldA.p, plan->foldB.p,
-                               plan->gK, nvox, plan->folded_dwi.p);
-        else
-            hipLaunchKernelGGL(dsi_fold_kernel, dim3((unsigned)fib::cdiv(nvox, 256)), dim3(256), 0, st, dwi, mask, plan->foldA.p, plan->foldB.p,
-                               plan->gK, nvox, plan->folded_dwi.p);
-        ga.S = plan->folded_dwi.p;
-        ga.rowA = plan->foldA.p; ga.rowB = plan->foldB.p;
-    }
-    ga.scale_frame = plan->nrow0 > 0 ? ((fuse_fold || dsi2) ? plan->scale_frame_raw : plan->scale_frame) : -1;
-    ga.scale_coef = plan->scale_coef;
-    ga.stride = nvox;
-    ga.has_ineff = plan->has_ineff ? 1 : 0;
-    FIB_CHECK(fib::cdiv(nvox, WG_VOX) * plan->ntile_m < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "volume too large for one launch");
-
-    auto run_gemm = [&](GemmArgs g, hipStream_t s) -> int {
-        const unsigned grid = (unsigned)(fib::cdiv(g.nvox, WG_VOX) * plan->ntile_m);
-        fib::ProfScope prof("odf_gemm", s);
-        if (dsi2) {                                      // persistent grid, an even number of workgroups per XCD (ODF tile | pdf tile)
-            int ncu = 256;
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, plan->device);
-            const int64_t items = fib::cdiv(g.nvox, 8 * 32) * 2;
-            unsigned pg = (unsigned)std::min<int64_t>((int64_t)ncu, items);
-            pg = (pg + 15) / 16 * 16;
-            const int nslot = (int)pg / 8;
-            // share of the ODF tile's cost per voxel group (tools/dsi_na_sweep.py, 140^3 x 515: 68 us per ODF item, 59.7 per pdf item of 9
-            // blocks; ~4.5 us per block): 17 of 32 workgroups per XCD for the 515-point lattice
-            const double ca = 68.0, cb = 19.0 + 4.5 * plan->MBB;
-            int na = (int)(nslot * ca / (ca + cb) + 0.5);
-            // The pdf-tile workgroups follow the ODF-tile ones through the XCD's voxel groups (see gemm3_body: a bounded wait on the
-            // partner's item counter), so the samples are fetched from HBM once and the second reader finds them in the XCD's L2 --
-            // [r4] for any split, not only 16 | 16 (FIBERS_DSI_NA=<n> sets the split, FIBERS_DSI_PAIR=0 switches the waiting off:
-            // tools/dsi_na_sweep.py).
-            const char *ena = fib::ab_env("FIBERS_DSI_NA");
-            if (ena) na = atoi(ena);
-            g.dsi_na = std::max(1, std::min(nslot - 1, na));
-            const char *epair = fib::ab_env("FIBERS_DSI_PAIR");
-            if (plan->pair_flags.p && nslot <= 32 && !(epair && epair[0] == '0')) g.pair_flags = plan->pair_flags.p;   // (the counters were cleared by mask_compact_kernel)
-            switch (plan->MBB) {
-                case 5: if (g.h2) hipLaunchKernelGGL((odf_dsi2_kernel<5, true>), dim3(pg), dim3(512), 0, s, g); else hipLaunchKernelGGL((odf_dsi2_kernel<5, false>), dim3(pg), dim3(512), 0, s, g); break;
-                case 7: if (g.h2) hipLaunchKernelGGL((odf_dsi2_kernel<7, true>), dim3(pg), dim3(512), 0, s, g); else hipLaunchKernelGGL((odf_dsi2_kernel<7, false>), dim3(pg), dim3(512), 0, s, g); break;
-                default: if (g.h2) hipLaunchKernelGGL((odf_dsi2_kernel<9, true>), dim3(pg), dim3(512), 0, s, g); else hipLaunchKernelGGL((odf_dsi2_kernel<9, false>), dim3(pg), dim3(512), 0, s, g); break;
-            }
-            FIB_HIP(hipGetLastError());
-            return FIB_OK;
-        }
-#define FIB_GEMM_CASE(MBV, NXV) if (plan->MB == MBV && plan->NX == NXV) { launch_gemm<MBV, NXV>(g, grid, s); launched = true; }
-        bool launched = false;
-        FIB_GEMM_CASE(5, 0) FIB_GEMM_CASE(6, 0) FIB_GEMM_CASE(7, 0) FIB_GEMM_CASE(8, 0) FIB_GEMM_CASE(9, 0) FIB_GEMM_CASE(10, 0) FIB_GEMM_CASE(11, 0)
-        FIB_GEMM_CASE(5, 1) FIB_GEMM_CASE(6, 1) FIB_GEMM_CASE(7, 1) FIB_GEMM_CASE(8, 1) FIB_GEMM_CASE(9, 1) FIB_GEMM_CASE(10, 1)
-#undef FIB_GEMM_CASE
-        if (!launched) return fib::fail(FIB_ERR_INVALID, "internal: no GEMM variant for MB=%d NX=%d", plan->MB, plan->NX);
-        FIB_HIP(hipGetLastError());
-        return FIB_OK;
-    };
-
-    int rc = run_gemm(ga, st);                           // launch 2
-    if (rc != FIB_OK) return rc;
-    const bool fused_scan = fuse || dsi2;
-    if (!fused_scan) {                                  // separate peak finder on the stored ODF (other tessellations, unaligned pieces, FIB_ODF_SEPARATE_PEAKS)
-        if (ga.fix_list) {
+    const bool out16 = nvox % 4 == 0 && ((uintptr_t)odf & 15) == 0 && (pdf == nullptr || ((uintptr_t)pdf & 15) == 0);
+    const bool in16 = nvox % 4 == 0 && ((uintptr_t)dwi & 15) == 0 && ((uintptr_t)mask & 3) == 0;
+    const OdfRoute route = odf_route(plan, nvox, out16, in16, flags);
+    FIB_RC(odf_scratch(plan, route, nvox));
+    // launch 1: compact the mask -- voxel list for the contraction, 64-voxel tile list for the peak finder (counts stay on the device) --
+    // and clear the outputs outside it
+    ZeroArgs z{};
+    z.out0 = pdf; z.out1 = odf; z.n0 = plan->nrow0; z.n1 = plan->nrows - plan->nrow0; z.nvox = nvox; z.stride = nvox;
+    for (int k = 0; k < 3; k++) { z.peak[k] = peak[k]; z.qa[k] = qa[k]; }
+    FIB_RC(launch_mask_compact(plan, mask, nvox, plan->maxenc.p, !(flags & FIB_ODF_PREZEROED) ? &z : nullptr, st));
+    if (route.fold_pre) launch_fold(plan, route, dwi, mask, nvox, st);
+    // launch 2: the contraction; sphere_642 plans find the peaks on its accumulators
+    const GemmArgs ga = odf_gemm_args(plan, route, dwi, mask, pdf, odf, peak, qa, nvox);
+    FIB_RC(launch_contraction(plan, route, ga, "odf_gemm", st));
+    if (route.peaks) {
+        if (route.inf_fix) {
             InfFixArgs fx{plan->Gdev.p, dwi, odf, ga.fix_count, ga.fix_list, ga.fix_cap, plan->gM, plan->gK, nvox};
             hipLaunchKernelGGL(odf_inf_fix_kernel, dim3(64), dim3(256), 0, st, fx);
         }
-        rc = launch_peaks(plan, odf, nvox, nvox, peak, qa, nullptr, nullptr, true, st, false, plan->live_tiles.p, plan->live_counts.p + 1);
-        if (rc != FIB_OK) return rc;
+        FIB_RC(launch_peaks(plan, odf, nvox, nvox, peak, qa, nullptr, nullptr, true, st, false, plan->live_tiles.p, plan->live_counts.p + 1));
     }
-    float *om = odfmax_dev ? odfmax_dev : plan->odfmax.p;
-    {                                                   // launch 3: redo list (+ column repair), exact odfmax, its two floats
-        fib::ProfScope prof("odf_post", st);
-        PostArgs pa{};
-        pa.redo = RedoArgs{odf, nvox, fused_scan ? ga.redo_count : nullptr, ga.redo_list, ga.redo_cap, plan->verts.p, {peak[0], peak[1], peak[2]}, {qa[0], qa[1], qa[2]}, plan->maxenc.p};
-        pa.G = (fused_scan && ga.fix_list) ? plan->Gdev.p : nullptr; pa.S = dwi; pa.out = odf; pa.M = plan->gM; pa.K = plan->gK;
-        pa.refine = RefineArgs{odf, nvox, nvox, plan->nvert, plan->live_vox.p, plan->live_counts.p, plan->mean_hi.p, plan->maxenc.p};
-        pa.arrive = plan->tickets.p + 1; pa.odfmax = om; pa.raw = (flags & FIB_ODF_RAW_ODFMAX) ? 1 : 0;
-        pa.selctr = plan->selctr.p; pa.sellist = plan->sellist.p; pa.selcap = POST_SELCAP; pa.epoch = plan->compact_epoch;
-        if (flags & FIB_ODF_NORMALIZE) {                // [r6] qa ./= odfmax in the same launch (gqi.jl:166-168)
-            for (int k = 0; k < 3; k++) pa.nq[k] = qa[k];
-            pa.nq_n = nvox; pa.done = reinterpret_cast<unsigned long long *>(plan->tickets.p + 2); pa.epoch = plan->compact_epoch;
-        }
-        { const char *e = fib::ab_env("FIBERS_POST_SKIP"); pa.dbg = e ? atoi(e) : 0; }
-        hipLaunchKernelGGL(odf_post_kernel, dim3(384), dim3(256), 0, st, pa);
-        FIB_HIP(hipGetLastError());
-    }
-    return FIB_OK;
+    return launch_post(plan, route, ga, dwi, odf, peak, qa, nvox, odfmax_dev ? odfmax_dev : plan->odfmax.p, flags, st);   // launch 3
 } FIB_API_CATCH
 
 // ---- plain use of the contraction kernels: O[M x n] = A[M x K] * max(S[K x n], 0) (row N4, RUMBA-SD) -----------------
@@ -771,50 +816,38 @@ int fib::matrix_plan_run(const fib_odf_plan *plan, const float *S, const uint8_t
     FIB_CHECK(plan && S && ones && out && n > 0, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(n <= ((int64_t)1 << 26), FIB_ERR_UNSUPPORTED, "more than 2^26 columns");
     hipStream_t st = (hipStream_t)stream;
-    if (recompact) {                                    // the column list of an all-ones mask: kept in the plan between calls
-        int rcc = launch_mask_compact(plan, ones, n, nullptr, nullptr, st);
-        if (rcc != FIB_OK) return rcc;
-    }
-    GemmArgs ga{};
-    ga.At = plan->At.p; ga.At3 = plan->split_bf16 ? plan->At3.p : nullptr; ga.S = S;
-    ga.Aextra = plan->Aextra.p; ga.h2 = plan->h2 ? 1 : 0; ga.h2_inv_sa = 1.0f / plan->h2_sa;
-    ga.vec_ok = (n % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
-    ga.vidx = plan->live_vox.p; ga.nlive = plan->live_counts.p; ga.mask = ones; ga.effbits = plan->effbits.p;
-    ga.out0 = nullptr; ga.out1 = out; ga.nvox = n;
-    ga.K = plan->gK; ga.Kpad = plan->Kpad; ga.M = plan->gM; ga.nrow0 = 0; ga.ntile_m = plan->ntile_m;
-    ga.scale_frame = -1; ga.scale_coef = 0.0f; ga.stride = n; ga.has_ineff = 0;
-    const unsigned grid = (unsigned)(fib::cdiv(n, WG_VOX) * plan->ntile_m);
-    fib::ProfScope prof("matrix_gemm", st);
-#define FIB_GEMM_CASE(MBV, NXV) if (plan->MB == MBV && plan->NX == NXV) { launch_gemm<MBV, NXV>(ga, grid, st); launched = true; }
-    bool launched = false;
-    FIB_GEMM_CASE(5, 0) FIB_GEMM_CASE(6, 0) FIB_GEMM_CASE(7, 0) FIB_GEMM_CASE(8, 0) FIB_GEMM_CASE(9, 0) FIB_GEMM_CASE(10, 0) FIB_GEMM_CASE(11, 0)
-    FIB_GEMM_CASE(5, 1) FIB_GEMM_CASE(6, 1) FIB_GEMM_CASE(7, 1) FIB_GEMM_CASE(8, 1) FIB_GEMM_CASE(9, 1) FIB_GEMM_CASE(10, 1)
-#undef FIB_GEMM_CASE
-    if (!launched) return fib::fail(FIB_ERR_INVALID, "internal: no GEMM variant for MB=%d NX=%d", plan->MB, plan->NX);
+    // the trivial route: the contraction alone, on the column list of an all-ones mask that the plan keeps between calls
+    OdfRoute route;
+    route.compact = recompact;
+    route.split = plan->split_bf16;
+    route.vec_ok = n % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    FIB_RC(odf_scratch(plan, route, n));
+    if (route.compact) FIB_RC(launch_mask_compact(plan, ones, n, nullptr, nullptr, st));
+    return launch_contraction(plan, route, gemm_args(plan, route, S, ones, nullptr, out, n), "matrix_gemm", st);
+}
+
+namespace {
+// qa ./= the divisor: a host scalar (dev == NULL), the first float at dev, or -- pair -- the pair {maximum, NaN flag} at dev
+int qa_normalize(float *const qa[3], int64_t nvox, float *dev, float host, int pair, void *stream) {
+    hipLaunchKernelGGL(qa_normalize_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, qa[0], qa[1], qa[2], nvox, dev, host, pair);
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 }
+}  // namespace
 
 extern "C" int fibd_qa_normalize(float *const qa[3], int64_t nvox, float odfmax, void *stream) try {
     FIB_CHECK(qa && qa[0] && qa[1] && qa[2] && nvox > 0, FIB_ERR_INVALID, "NULL argument");
-    hipLaunchKernelGGL(qa_normalize_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, qa[0], qa[1], qa[2], nvox,
-                       (float *)nullptr, odfmax, 0);
-    FIB_HIP(hipGetLastError());
-    return FIB_OK;
+    return qa_normalize(qa, nvox, nullptr, odfmax, 0, stream);
 } FIB_API_CATCH
 
 extern "C" int fibd_qa_normalize_dev(float *const qa[3], int64_t nvox, const float *odfmax_dev, void *stream) try {
     FIB_CHECK(qa && qa[0] && qa[1] && qa[2] && odfmax_dev && nvox > 0, FIB_ERR_INVALID, "NULL argument");
-    hipLaunchKernelGGL(qa_normalize_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, qa[0], qa[1], qa[2], nvox, const_cast<float *>(odfmax_dev), 0.0f, 0);
-    FIB_HIP(hipGetLastError());
-    return FIB_OK;
+    return qa_normalize(qa, nvox, const_cast<float *>(odfmax_dev), 0.0f, 0, stream);
 } FIB_API_CATCH
 
 extern "C" int fibd_qa_normalize_pair(float *const qa[3], int64_t nvox, float *odfmax_pair_dev, void *stream) try {
     FIB_CHECK(qa && qa[0] && qa[1] && qa[2] && odfmax_pair_dev && nvox > 0, FIB_ERR_INVALID, "NULL argument");
-    hipLaunchKernelGGL(qa_normalize_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, qa[0], qa[1], qa[2], nvox, odfmax_pair_dev, 0.0f, 1);
-    FIB_HIP(hipGetLastError());
-    return FIB_OK;
+    return qa_normalize(qa, nvox, odfmax_pair_dev, 0.0f, 1, stream);
 } FIB_API_CATCH
 
 extern "C" int fibd_find_peaks(const fib_odf_plan *plan, const float *odf, int64_t nvox,

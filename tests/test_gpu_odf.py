@@ -466,6 +466,72 @@ def test_dsi_fold_inside_the_kernel_and_fold_prepass_agree(fj):
         assert bool((res["fused"]["odf"][:, 10] == 0).all())
 
 
+# (kind, sphere, directions per shell x shells after one b0, format asked, volume, extra) -> (dsi_fold launches, odf_peaks launches,
+# plan.format).  What each case runs follows from the plan (finish_plan) and the call: KT = 16 frames per stage, so 1 + 40 frames are
+# three stages (the fused scan's minimum), 1 + 20 two (the split kernel's minimum), 1 + 12 one (the plan falls back to f32); 321
+# half-sphere vertices are one tile of 10 blocks + 1 row (the fused scan's shape), sphere_362's 181 are not; the fused scan and
+# odf_dsi2_kernel need a voxel count that is a multiple of 4, 16-byte aligned outputs and no FIB_ODF_SEPARATE_PEAKS.
+_ROUTE_CASES = [
+    ("gqi", "sphere_642", (20, 2), "fp16x2", (8, 8, 8), None,        (0, 0, "fp16x2")),   # fused scan
+    ("gqi", "sphere_642", (20, 2), "bf16x3", (8, 8, 8), None,        (0, 0, "bf16x3")),
+    ("gqi", "sphere_642", (20, 2), "fp16x2", (8, 8, 8), "separate",  (0, 1, "fp16x2")),   # the flag turns the fused scan off
+    ("gqi", "sphere_642", (20, 2), "fp16x2", (9, 7, 5), None,        (0, 1, "fp16x2")),   # 315 voxels: not a multiple of 4
+    ("gqi", "sphere_642", (20, 2), "fp16x2", (8, 8, 8), "unaligned", (0, 1, "fp16x2")),   # odf four bytes off a 16-byte boundary
+    ("gqi", "sphere_642", (20, 2), "f32",    (8, 8, 8), None,        (0, 1, "f32")),      # f32 kernel + peak finder
+    ("gqi", "sphere_642", (20, 1), "fp16x2", (8, 8, 8), None,        (0, 1, "fp16x2")),   # two stages: split kernel, not the fused shape
+    ("gqi", "sphere_642", (12, 1), "fp16x2", (8, 8, 8), None,        (0, 1, "f32")),      # one stage: the plan falls back to f32
+    ("gqi", "sphere_362", (20, 2), "fp16x2", (8, 8, 8), None,        (0, 1, "fp16x2")),   # other tessellation
+    ("dsi", "sphere_642", None,    "fp16x2", (8, 8, 8), None,        (0, 0, "fp16x2")),   # odf_dsi2_kernel
+    ("dsi", "sphere_642", None,    "fp16x2", (8, 8, 8), "separate",  (0, 1, "fp16x2")),   # fold in the kernel, separate peaks
+    ("dsi", "sphere_642", None,    "fp16x2", (9, 7, 5), None,        (0, 1, "fp16x2")),
+    ("dsi", "sphere_642", None,    "f32",    (8, 8, 8), None,        (1, 1, "f32")),      # fold pre-pass
+    ("dsi", "sphere_362", None,    "fp16x2", (8, 8, 8), None,        (0, 1, "fp16x2")),   # fold in the kernel, separate peaks
+]
+
+
+@pytest.mark.parametrize("kind,sphere,frames,fmt,shape,extra,want", _ROUTE_CASES,
+                         ids=["-".join(str(x) for x in (c[0], c[1][7:], c[2] and "1+%d" % (c[2][0] * c[2][1]), c[3], "%dx%dx%d" % c[4], c[5]) if x)
+                              for c in _ROUTE_CASES])
+def test_which_kernels_a_configuration_runs(fj, kind, sphere, frames, fmt, shape, extra, want):
+    """The launches of one reconstruction call, counted by the profile hook: mask_compact, odf_gemm and odf_post exactly once, the fold
+    pre-pass (dsi_fold) and the separate peak finder (odf_peaks) once or not at all.  The fused scan (sphere_642 GQI) and odf_dsi2_kernel
+    (folded DSI on sphere_642) find the peaks inside the contraction: they show as odf_peaks == 0."""
+    import ctypes as C
+    import torch
+    from fibers_jl_amd import phantom
+    dev = torch.device("cuda", 0)
+    L = fj.lib()
+    sph = getattr(fj, sphere)
+    nvox = int(np.prod(shape))
+    bval, bvec = phantom.scheme_dsi() if kind == "dsi" else phantom.scheme_gqi(1, frames[0], (1000.0, 2000.0)[:frames[1]], 3)
+    dwi, _ = phantom.make_dwi_torch(shape, bval, bvec, seed=9, device=dev)
+    mask = torch.ones(nvox, dtype=torch.uint8, device=dev)
+    plan = fj.OdfPlan(kind, bval, bvec, sph, hann_width=32, format=fmt)
+    try:
+        assert plan.format == want[2]
+        out = None
+        if extra == "unaligned":
+            big = torch.zeros(sph.nvert * nvox + 4, dtype=torch.float32, device=dev)
+            out = dict(odf=big[1:1 + sph.nvert * nvox].view(sph.nvert, nvox), peak=[torch.empty((3, nvox), device=dev) for _ in range(3)],
+                       qa=[torch.empty(nvox, device=dev) for _ in range(3)], odfmax=torch.empty(2, device=dev))
+            assert out["odf"].data_ptr() % 16 == 4
+        L.fib_profile_filter(None)
+        L.fib_profile_enable(1); L.fib_profile_reset()
+        out = fj.odf_rec_device(plan, dwi, mask, out=out, separate_peaks=extra == "separate")
+        torch.cuda.synchronize()
+        got = {}
+        for k in ("mask_compact", "dsi_fold", "odf_gemm", "odf_peaks", "odf_post"):
+            ms, cnt = C.c_double(0), C.c_int64(0)
+            L.fib_profile_get(k.encode(), C.byref(ms), C.byref(cnt))
+            got[k] = cnt.value
+        assert got == dict(mask_compact=1, dsi_fold=want[0], odf_gemm=1, odf_peaks=want[1], odf_post=1)
+        assert bool(torch.isfinite(out["odf"]).all()) and float(out["odf"].abs().max()) > 0
+    finally:
+        L.fib_profile_enable(0)
+        L.fib_profile_reset()
+        plan.close()
+
+
 @pytest.mark.parametrize("sphere", ["sphere_362", "sphere_642", "sphere_724"])
 def test_find_peaks_randomised_against_the_oracle(fj, orc, sphere):
     """find_peaks! (gqi.jl:180-201) on adversarial ODFs: heavy ties (values on a coarse grid), plateaus, negative values,
