@@ -18,8 +18,9 @@
 // tm_walk_lines, in the chunks that fibh::next_line_chunk cuts (host_tier.h), and keep a body per chunk.
 // The volume, warp, structure-tensor, RUMBA and peak-finder forms keep nothing between calls: their buffers are local.  The two frame
 // resamplers share frame_checks / frame_chunks, the peak finders find_peaks_host; the sizes taken from the free memory are host_tier.h's.
+// The tracking forms (fib_stream, fib_stream_lcm, fib_prob_stream) return through one owner, fibh::TractArrays, and one download path,
+// d2h_pipelined on the worker's output ring; their seed list, the seed share of a device set and the merge of its shards are host_tier.h's.
 #include <sched.h>
-#include <sys/mman.h>
 
 #include <atomic>
 #include <chrono>
@@ -98,16 +99,6 @@ struct HostTimer {
     explicit HostTimer(const char *n) : name(n), t0(std::chrono::steady_clock::now()) {}
     ~HostTimer() { if (fib::profiling_on()) fib::profile_add_ms(name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
 };
-
-// Result arrays the library hands to the caller (fib_tract_free releases them with free()): large ones are 2-MB aligned and advised for
-// transparent huge pages -- C4 returns 1.5 GB of points, i.e. 377 000 first-touch faults of 4-KB pages inside the call otherwise.
-void *alloc_result(size_t bytes) {
-    if (bytes < ((size_t)32 << 20)) return malloc(bytes ? bytes : 1);
-    void *p = nullptr;
-    if (posix_memalign(&p, (size_t)2 << 20, bytes) != 0) return nullptr;
-    (void)madvise(p, bytes, MADV_HUGEPAGE);
-    return p;
-}
 
 // ---- per-device state of the host tier -----------------------------------------------------------------------------------
 struct PinBuf {                                          // grow-only pinned host buffer
@@ -1335,7 +1326,7 @@ extern "C" int fib_rumba_rec(int device, const float *dwi, int nx, int ny, int n
     DevLease lease;
     fib_rumba_plan *p = nullptr;                             // the constructor's refusals come first, the device index among them (FIB_DEVICE_ALL too)
     RC(fib_rumba_plan_create(device, bval, bvec, nvol, verts, nverts, lam_para, lam_perp, lam_csf, lam_gm, &p));
-    struct PlanDel { fib_rumba_plan *p; ~PlanDel() { fib_rumba_plan_destroy(p); } } del{p};
+    fib::Scoped<fib_rumba_plan, fib_rumba_plan_destroy> del(p);
     RC(lease.take(device, nullptr));
     const int64_t nvox = (int64_t)nx * ny * nz;
     const int nvert = nverts / 2;
@@ -1378,7 +1369,7 @@ int find_peaks_host(int device, const float *odf, int64_t nvox, const float *ver
     DevLease lease;
     fib_odf_plan *plan = nullptr;
     RC(fib::peaks_plan_create(device, verts, nverts, faces, nfaces, &plan));
-    struct PlanDel { fib_odf_plan *p; ~PlanDel() { fib_odf_plan_destroy(p); } } del{plan};
+    fib::Scoped<fib_odf_plan, fib_odf_plan_destroy> del(plan);
     RC(lease.take(device, nullptr));
     const size_t nv = (size_t)nvox, n = nv * (nverts / 2);
     fib::DevBuf<float> d_odf;
@@ -1426,17 +1417,11 @@ struct StreamIn {
     const fib_stream_params *prm; const float *const *ovec; const float *const *f; float f_thresh; const float *fa; float fa_thresh;
     const float *sublist; int32_t nsub; const float *lcms; float lcm_thresh; uint64_t rng_seed; int strd0, strd1;
 };
-// what one worker traced: lines in (seed, sub) order of ITS seed shard; seed_index counts seeds of the whole list.  The arrays are
-// malloc'ed and never zero-filled ([r5]: C4 returns 1.5 GB of points -- a std::vector's value-initialisation and a second copy into the
-// result cost more than the PCIe transfer); with one worker they ARE the result (fib_tract_free releases them with free()).
-struct Shard {
-    int64_t nl = 0, np = 0;
-    int32_t *npts = nullptr; int64_t *sidx = nullptr; float *xyz = nullptr; uint8_t *flags = nullptr;
-    Shard() = default;
-    Shard(const Shard &) = delete;
-    Shard &operator=(const Shard &) = delete;
-    ~Shard() { free(npts); free(sidx); free(xyz); free(flags); }
-};
+// what a tracking form returns, or one worker of a device set traced (host_tier.h); with one worker its arrays ARE the result
+using fibh::TractArrays;
+int tract_alloc(TractArrays &t, int64_t nl, int64_t np, bool with_flags) {
+    return t.alloc(nl, np, with_flags) ? FIB_OK : fib::fail(FIB_ERR_NOMEM, "out of host memory");
+}
 
 // device -> pageable host memory, pipelined: pieces of up to 64 MB come down into two slots of the worker's pinned output ring while the
 // scatter pool copies the previous piece to its destination (a plain hipMemcpy into pageable memory stages through a small driver buffer
@@ -1471,9 +1456,9 @@ int d2h_pipelined(DevState &d, void *dst, const void *src, size_t bytes, hipStre
     return drain(np - 1);
 }
 
-// seeds[i], i = w, w + nw, ... (round-robin: balances line length; the reference's contiguous chunks, stream.jl:757-759, do not)
+// worker w of nw on its share of the seeds (fibh::seed_share)
 int stream_worker(DevState &d, int w, int nw, const StreamIn &in, const std::vector<uint8_t> *m8, const std::vector<int64_t> &seeds,
-                  std::vector<uint8_t> *seed_mask_out, Shard &sh) {
+                  std::vector<uint8_t> *seed_mask_out, TractArrays &sh) {
     const fib_stream_params &prm0 = *in.prm;
     const int nvec = prm0.nvec;
     const int64_t nvox = (int64_t)prm0.nx * prm0.ny * prm0.nz;
@@ -1509,7 +1494,7 @@ int stream_worker(DevState &d, int w, int nw, const StreamIn &in, const std::vec
     }
     tm.reset(new HostTimer("stream_host_seeds_trace"));
     std::vector<int64_t> mine;
-    for (size_t i = (size_t)w; i < seeds.size(); i += (size_t)nw) mine.push_back(seeds[i]);
+    fibh::seed_share(seeds, w, nw, mine);
     auto &d_seeds = sb.seeds;
     RC(d_seeds.ensure(mine.size()));
     if (!mine.empty()) RC(h2d(d_seeds.p, mine.data(), sizeof(int64_t) * mine.size()));
@@ -1529,14 +1514,9 @@ int stream_worker(DevState &d, int w, int nw, const StreamIn &in, const std::vec
     } else {
         RC(fibd_stream_trace(&prm, d_field.p, d_seeds.p, (int64_t)mine.size(), d_sub.p, in.nsub, st, &job, &nl, &np));
     }
-    struct JobGuard { fib_stream_job *j; ~JobGuard() { fib_stream_job_destroy(j); } } jg{job};
+    fib::Scoped<fib_stream_job, fib_stream_job_destroy> jg(job);
     tm.reset(new HostTimer("stream_host_results"));
-    sh.nl = nl; sh.np = np;
-    sh.npts = (int32_t *)alloc_result(sizeof(int32_t) * (size_t)std::max<int64_t>(nl, 1));
-    sh.sidx = (int64_t *)alloc_result(sizeof(int64_t) * (size_t)std::max<int64_t>(nl, 1));
-    sh.xyz = (float *)alloc_result(sizeof(float) * 3 * (size_t)std::max<int64_t>(np, 1));
-    if (in.lcms) sh.flags = (uint8_t *)alloc_result((size_t)std::max<int64_t>(np, 1));
-    if (!sh.npts || !sh.sidx || !sh.xyz || (in.lcms && !sh.flags)) return fib::fail(FIB_ERR_NOMEM, "out of host memory");
+    RC(tract_alloc(sh, nl, np, in.lcms != nullptr));
     if (nl > 0) {
         auto &d_npts = sb.npts; auto &d_sidx = sb.sidx; auto &d_xyz = sb.xyz; auto &d_flags = sb.flags;
         RC(d_npts.ensure((size_t)nl));
@@ -1548,8 +1528,7 @@ int stream_worker(DevState &d, int w, int nw, const StreamIn &in, const std::vec
         RC(d2h_pipelined(d, sh.npts, d_npts.p, sizeof(int32_t) * (size_t)nl, st));
         RC(d2h_pipelined(d, sh.sidx, d_sidx.p, sizeof(int64_t) * (size_t)nl, st));
         if (in.lcms) RC(d2h_pipelined(d, sh.flags, d_flags.p, (size_t)np, st));
-        // seed_index = local seed * nsub + sub  ->  global: seed (w + nw * local) of the whole list
-        if (nw > 1) for (int64_t i = 0; i < nl; i++) { const int64_t s = sh.sidx[i], ls = s / in.nsub, sub = s % in.nsub; sh.sidx[i] = ((int64_t)w + (int64_t)nw * ls) * in.nsub + sub; }
+        if (nw > 1) for (int64_t i = 0; i < nl; i++) sh.sidx[i] = fibh::global_seed_index(sh.sidx[i], w, nw, in.nsub);
     }
     return FIB_OK;
 }
@@ -1589,44 +1568,24 @@ int stream_host(int device, const fib_stream_params *prm, const float *const *ov
     // seed voxels: findall(W.mask) (stream.jl:744) or findall(seed.vol .> 0) (stream.jl:751), column-major order
     if (seed) RC(mask_convert(seed, seed_dtype, nvox, true, s8));
     else {
-        Shard none;
+        TractArrays none;
         std::vector<int64_t> noseeds;
         RC(for_each_worker({ws[0]}, [&](int, DevState &d) { return stream_worker(d, 0, 1, in, mask ? &m8 : nullptr, noseeds, &s8, none); }));
     }
     tm.reset(new HostTimer("stream_host_seed_list"));
     std::vector<int64_t> seeds;
-    for (int64_t i = 0; i < nvox; i++) if (s8[i]) seeds.push_back(i);
+    fibh::seed_voxels(s8.data(), nvox, seeds);
     tm.reset();
     const int nw = (int)ws.size();
-    std::vector<Shard> shards((size_t)nw);
+    std::vector<TractArrays> shards((size_t)nw);
     RC(for_each_worker(ws, [&](int w, DevState &d) { return stream_worker(d, w, nw, in, mask ? &m8 : nullptr, seeds, nullptr, shards[w]); }));
-    // merge in (seed, sub) order == the reference's order under static scheduling (stream.jl:757-787)
+    if (nw == 1) { shards[0].give(out); return FIB_OK; }   // one worker: its arrays are the result
     int64_t nl = 0, np = 0;
     for (auto &s : shards) { nl += s.nl; np += s.np; }
-    out->nlines = nl; out->npoints = np;
-    if (nw == 1) {                                       // one worker: its arrays are the result
-        Shard &s = shards[0];
-        out->npts = s.npts; out->seed_index = s.sidx; out->xyz = s.xyz; out->flags = s.flags;
-        s.npts = nullptr; s.sidx = nullptr; s.xyz = nullptr; s.flags = nullptr;
-        return FIB_OK;
-    }
-    out->npts = (int32_t *)alloc_result(sizeof(int32_t) * (size_t)(nl > 0 ? nl : 1));
-    out->seed_index = (int64_t *)alloc_result(sizeof(int64_t) * (size_t)(nl > 0 ? nl : 1));
-    out->xyz = (float *)alloc_result(sizeof(float) * 3 * (size_t)(np > 0 ? np : 1));
-    if (lcms) out->flags = (uint8_t *)alloc_result((size_t)(np > 0 ? np : 1));
-    if (!out->npts || !out->seed_index || !out->xyz || (lcms && !out->flags)) { fib_tract_free(out); return fib::fail(FIB_ERR_NOMEM, "out of host memory"); }
-    std::vector<int64_t> li((size_t)nw, 0), pi((size_t)nw, 0);
-    int64_t ol = 0, op = 0;
-    while (ol < nl) {
-        int best = -1;
-        for (int w = 0; w < nw; w++)
-            if (li[w] < shards[w].nl && (best < 0 || shards[w].sidx[li[w]] < shards[best].sidx[li[best]])) best = w;
-        Shard &s = shards[best];
-        const int32_t n = s.npts[li[best]];
-        out->npts[ol] = n; out->seed_index[ol] = s.sidx[li[best]];
-        memcpy(out->xyz + 3 * op, s.xyz + 3 * pi[best], sizeof(float) * 3 * n);
-        ol++; op += n; li[best]++; pi[best] += n;
-    }
+    TractArrays merged;
+    RC(tract_alloc(merged, nl, np, false));              // (no flags: an LCM run has one worker)
+    fibh::merge_lines(shards.data(), nw, merged);
+    merged.give(out);
     return FIB_OK;
 }
 
@@ -1646,4 +1605,70 @@ extern "C" int fib_stream_lcm(int device, const fib_stream_params *prm, const fl
     FIB_CHECK(lcms != nullptr, FIB_ERR_INVALID, "NULL lcms volume");
     return stream_host(device, prm, ovec, f, f_thresh, fa, fa_thresh, mask, mask_dtype, seed, seed_dtype, sublist, nsub,
                        lcms, lcm_thresh, rng_seed, out);
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// prob_stream: probabilistic ODF tracking (probtrack.hip), host buffers.  One device.
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_prob_stream(int device, int nx, int ny, int nz, const float *odf, int nvert, const float *vertices, const uint8_t *mask,
+                               const uint8_t *seed, const float *sublist, int32_t nsub, int32_t len_min, int32_t len_max, float cosang_thresh,
+                               float step_size, float pmf_thresh, int32_t subtract_min, uint64_t rng_seed, fib_tract_out *out) try {
+    FIB_CHECK(out, FIB_ERR_INVALID, "NULL out");
+    memset(out, 0, sizeof *out);
+    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "prob_stream runs on one device (FIB_DEVICE_ALL is not supported)");
+    FIB_CHECK(odf && vertices && sublist, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
+    FIB_CHECK(nsub >= 1, FIB_ERR_INVALID, "sublist must hold at least one offset");
+    DevLease lease;
+    RC(lease.take(device, nullptr));
+    DevState &d = *lease.wk;
+    RC(d.init(copy_threads(1)));                         // (the download below runs on the worker's output ring)
+    fib_prob_plan *plan_raw = nullptr;
+    RC(fib_prob_plan_create(device, vertices, nvert, cosang_thresh, &plan_raw));
+    fib::Scoped<fib_prob_plan, fib_prob_plan_destroy> plan(plan_raw);
+    const int64_t nvox = (int64_t)nx * ny * nz;
+    const int pitch = fib_prob_row_pitch(nvert);
+    // the table, from voxel chunks of the host ODF: the float ODF is never whole on the device
+    fib::DevBuf<uint16_t> d_table;
+    fib::DevBuf<float> d_odf;
+    fib::DevBuf<uint8_t> d_mask;
+    const int64_t chunk = std::min<int64_t>(nvox, (int64_t)1 << 18);
+    RC(d_table.alloc((size_t)nvox * pitch));
+    RC(d_odf.alloc((size_t)chunk * nvert));
+    if (mask) RC(d_mask.alloc((size_t)chunk));
+    for (int64_t v0 = 0; v0 < nvox; v0 += chunk) {
+        const int64_t n = std::min(chunk, nvox - v0);
+        FIB_HIP(hipMemcpy2D(d_odf.p, sizeof(float) * (size_t)n, odf + v0, sizeof(float) * (size_t)nvox, sizeof(float) * (size_t)n, (size_t)nvert,
+                            hipMemcpyHostToDevice));
+        if (mask) RC(h2d(d_mask.p, mask + v0, (size_t)n));
+        RC(fibd_prob_table(d_odf.p, mask ? d_mask.p : nullptr, n, nvert, subtract_min, pmf_thresh, d_table.p + (size_t)v0 * pitch, nullptr));
+        FIB_HIP(hipStreamSynchronize(nullptr));                // (the chunk buffers are written again)
+    }
+    d_odf.release(); d_mask.release();
+    // seeds: the seed volume, else the mask, else every voxel
+    std::vector<int64_t> seeds;
+    fibh::seed_voxels(seed ? seed : mask, nvox, seeds);
+    const int64_t nseed = (int64_t)seeds.size();
+    fib::DevBuf<int64_t> d_seeds, d_sidx, d_work;
+    fib::DevBuf<float> d_sub, d_xyz;
+    fib::DevBuf<int32_t> d_npts;
+    RC(fib::upload(d_seeds, seeds));
+    RC(fib::upload(d_sub, sublist, (size_t)3 * nsub));
+    const size_t wb = fib::prob_work_bytes(nseed * nsub);
+    RC(d_work.alloc(wb / 8));
+    const fib::ProbRun r{plan_raw, nx, ny, nz, len_min, len_max, nsub, step_size, d_table.p, d_seeds.p, nseed, d_sub.p, rng_seed};
+    hipStream_t st = d.s_cmp;                            // (the table is complete: every chunk waited for the NULL stream)
+    int64_t nl = 0, np = 0;
+    RC(fib::prob_count(r, d_work.p, wb, st, &nl, &np));
+    RC(d_npts.alloc((size_t)nl));
+    RC(d_sidx.alloc((size_t)nl));
+    RC(d_xyz.alloc((size_t)3 * np));
+    RC(fib::prob_emit(r, d_work.p, d_npts.p, d_sidx.p, d_xyz.p, st));
+    TractArrays res;
+    RC(tract_alloc(res, nl, np, false));
+    RC(d2h_pipelined(d, res.xyz, d_xyz.p, sizeof(float) * 3 * (size_t)np, st));     // (stream order: behind the emit kernel)
+    RC(d2h_pipelined(d, res.npts, d_npts.p, sizeof(int32_t) * (size_t)nl, st));
+    RC(d2h_pipelined(d, res.sidx, d_sidx.p, sizeof(int64_t) * (size_t)nl, st));
+    res.give(out);
+    return FIB_OK;
 } FIB_API_CATCH

@@ -97,6 +97,12 @@ void plan_destroy(Plan *plan) {
     delete plan;
 }
 
+// "destroy this when the scope ends": Scoped<fib_odf_plan, fib_odf_plan_destroy> plan(raw);
+template <typename T, void (*Destroy)(T *)>
+struct DestroyWith { void operator()(T *p) const { Destroy(p); } };
+template <typename T, void (*Destroy)(T *)>
+using Scoped = std::unique_ptr<T, DestroyWith<T, Destroy>>;
+
 // the b-table refusals, in the reference's words
 static inline int check_tables(const float *bval, const float *bvec, int nvol, bool need_bvec = true) {
     FIB_CHECK(bval != nullptr && nvol > 0, FIB_ERR_MISSING_BVAL, "Missing b-value table from input DWI structure");
@@ -170,5 +176,22 @@ int matrix_plan_create(int device, const float *A, int nrows, int ncols, fib_odf
 // the plan fib_find_peaks* and CSD hand to the peak finder: fib_gqi_plan_create on one dummy frame, with its refusals
 int peaks_plan_create(int device, const float *verts, int nverts, const int32_t *faces, int nfaces, fib_odf_plan **plan);
 int matrix_plan_run(const fib_odf_plan *plan, const float *S, const uint8_t *ones, int64_t n, float *out, bool recompact, void *stream);
+
+// The probabilistic tracer in its two phases (probtrack.hip), for fibd_prob_run and fib_prob_stream: all pointers of a run on the device.
+struct ProbRun {
+    const fib_prob_plan *plan;
+    int nx, ny, nz, len_min, len_max, nsub;
+    float step;
+    const uint16_t *table;
+    const int64_t *seeds;
+    int64_t nseed;
+    const float *sublist;
+    uint64_t rng_seed;
+};
+size_t prob_work_bytes(int64_t nlines);                  // the work area of a run of nlines = nseed * nsub lines (fibd_prob_work_size)
+// the run's refusals, pass 1, len_min, the offsets; waits for the stream and returns the totals
+int prob_count(const ProbRun &run, void *work, size_t work_bytes, hipStream_t stream, int64_t *nlines, int64_t *npoints);
+// pass 2: the kept lines replayed into npts / seed_index / xyz (which hold at least the totals prob_count returned); asynchronous
+int prob_emit(const ProbRun &run, void *work, int32_t *npts, int64_t *seed_index, float *xyz, hipStream_t stream);
 
 }  // namespace fib

@@ -7,14 +7,17 @@
 // the chunk schedule are read by tools, not only by reviewers.
 //
 // Contents: mask element-type conversion; CPU binding; the copy pool; LiveMap (the runs of a mask) + the piece list of a chunk;
-// row gather / scatter; chunk size, chunk schedule, slabs; the line-chunk schedule of the tractogram host forms; the chunk sizes
+// row gather / scatter; chunk size, chunk schedule, slabs; the line-chunk schedule of the tractogram host forms; the result of a tracking
+// form (its arrays and their owner, the seed list, the round-robin seed share of a device set and the merge of its shards); the chunk sizes
 // the frame resamplers and fib_st_recon take from the free device memory; run_chunks<Dev> -- the three-stage pipeline over voxel chunks.
 #pragma once
 #include <emmintrin.h>
 #include <sched.h>
+#include <sys/mman.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <condition_variable>
 #include <cstdint>
@@ -294,6 +297,85 @@ inline LineChunk next_line_chunk(const int32_t *npts, int64_t nlines, int64_t l0
     int64_t l = l0, n = 0;
     while (l < nlines && (l == l0 || (l - l0 < max_lines && n + npts[l] <= max_points))) n += npts[l++];
     return {l, n};
+}
+
+// ---- the result of a tracking form (fib_stream, fib_stream_lcm, fib_prob_stream) ---------------------------------------------------
+// Result arrays the library hands to the caller (fib_tract_free releases them with free()): large ones are 2-MB aligned and advised for
+// transparent huge pages -- C4 returns 1.5 GB of points, i.e. 377 000 first-touch faults of 4-KB pages inside the call otherwise.
+constexpr size_t RESULT_HUGE_BYTES = (size_t)32 << 20, RESULT_HUGE_ALIGN = (size_t)2 << 20;
+inline void *alloc_result(size_t bytes) {
+    if (bytes < RESULT_HUGE_BYTES) return malloc(bytes ? bytes : 1);
+    void *p = nullptr;
+    if (posix_memalign(&p, RESULT_HUGE_ALIGN, bytes) != 0) return nullptr;
+    (void)madvise(p, bytes, MADV_HUGEPAGE);
+    return p;
+}
+// The one owner of such a result until it is handed over: what a form traced, or what one worker of a device set traced (lines in
+// (seed, sub) order of ITS seed share).  The arrays are malloc'ed and never zero-filled ([r5]: a std::vector's value-initialisation and
+// a second copy into the result cost more than the PCIe transfer); each holds max(n, 1) elements, so none is NULL after alloc.
+struct TractArrays {
+    int64_t nl = 0, np = 0;
+    int32_t *npts = nullptr; int64_t *sidx = nullptr; float *xyz = nullptr; uint8_t *flags = nullptr;
+    TractArrays() = default;
+    TractArrays(const TractArrays &) = delete;
+    TractArrays &operator=(const TractArrays &) = delete;
+    ~TractArrays() { reset(); }
+    void reset() {
+        free(npts); free(sidx); free(xyz); free(flags);
+        npts = nullptr; sidx = nullptr; xyz = nullptr; flags = nullptr; nl = np = 0;
+    }
+    // arrays for nl lines of np points; false (and empty): out of host memory
+    bool alloc(int64_t nlines, int64_t npoints, bool with_flags) {
+        reset();
+        const size_t l = (size_t)std::max<int64_t>(nlines, 1), p = (size_t)std::max<int64_t>(npoints, 1);
+        npts = (int32_t *)alloc_result(sizeof(int32_t) * l);
+        sidx = (int64_t *)alloc_result(sizeof(int64_t) * l);
+        xyz = (float *)alloc_result(sizeof(float) * 3 * p);
+        if (with_flags) flags = (uint8_t *)alloc_result(p);
+        if (!npts || !sidx || !xyz || (with_flags && !flags)) { reset(); return false; }
+        nl = nlines; np = npoints;
+        return true;
+    }
+    void give(fib_tract_out *out) {                      // the arrays become the caller's; the owner is empty afterwards
+        out->nlines = nl; out->npoints = np;
+        out->npts = npts; out->seed_index = sidx; out->xyz = xyz; out->flags = flags;
+        npts = nullptr; sidx = nullptr; xyz = nullptr; flags = nullptr; nl = np = 0;
+    }
+};
+
+// seed voxels in column-major order: those where sv is set; sv == NULL: every voxel
+inline void seed_voxels(const uint8_t *sv, int64_t nvox, std::vector<int64_t> &out) {
+    out.clear();
+    for (int64_t i = 0; i < nvox; i++) if (!sv || sv[i]) out.push_back(i);
+}
+// A device set deals the seeds round-robin (balances line length; the reference's contiguous chunks, stream.jl:757-759, do not):
+// worker w of nw traces seeds w, w + nw, ...  A line's seed_index = seed * nsub + sub counts seeds of the worker's share;
+// global_seed_index turns it into the one that counts seeds of the whole list.
+inline void seed_share(const std::vector<int64_t> &seeds, int w, int nw, std::vector<int64_t> &mine) {
+    mine.clear();
+    for (size_t i = (size_t)w; i < seeds.size(); i += (size_t)nw) mine.push_back(seeds[i]);
+}
+inline int64_t global_seed_index(int64_t s, int w, int nw, int nsub) { return ((int64_t)w + (int64_t)nw * (s / nsub)) * nsub + s % nsub; }
+// The shards of a device set merged by ascending (global) seed_index == the reference's (seed, sub) order under static scheduling
+// (stream.jl:757-787); between shards the lower one goes first.  `out` holds arrays for the shards' totals.  Flags are not merged:
+// an LCM run has one worker, whose arrays are the result.
+inline void merge_lines(const TractArrays *shards, int nw, TractArrays &out) {
+    int64_t nl = 0, np = 0;
+    for (int w = 0; w < nw; w++) { assert(!shards[w].flags); nl += shards[w].nl; np += shards[w].np; }
+    assert(out.nl == nl && out.np == np && !out.flags);
+    std::vector<int64_t> li((size_t)nw, 0), pi((size_t)nw, 0);
+    int64_t ol = 0, op = 0;
+    while (ol < nl) {
+        int best = -1;
+        for (int w = 0; w < nw; w++)
+            if (li[w] < shards[w].nl && (best < 0 || shards[w].sidx[li[w]] < shards[best].sidx[li[best]])) best = w;
+        const TractArrays &s = shards[best];
+        const int32_t n = s.npts[li[best]];
+        out.npts[ol] = n; out.sidx[ol] = s.sidx[li[best]];
+        memcpy(out.xyz + 3 * op, s.xyz + 3 * pi[best], sizeof(float) * 3 * n);
+        ol++; op += n; li[best]++; pi[best] += n;
+    }
+    (void)np;
 }
 
 // ---- chunk sizes from half the device's free memory; 0: not even one fits (the form refuses with FIB_ERR_NOMEM) -------------------

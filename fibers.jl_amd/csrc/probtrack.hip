@@ -341,18 +341,7 @@ void pb_trace_launch(bool emit, const PbArgs &a, hipStream_t st) {
     }
 }
 
-struct PbRun {
-    const fib_prob_plan *plan;
-    int nx, ny, nz, len_min, len_max, nsub;
-    float step;
-    const uint16_t *table;
-    const int64_t *seeds;
-    int64_t nseed;
-    const float *sublist;
-    uint64_t rng_seed;
-};
-
-int pb_check(const PbRun &r, void *work, size_t work_bytes) {
+int pb_check(const fib::ProbRun &r, void *work, size_t work_bytes) {
     FIB_CHECK(r.plan && r.table && r.sublist, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(r.nx > 0 && r.ny > 0 && r.nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
     FIB_CHECK(r.nx <= (1 << 24) && r.ny <= (1 << 24) && r.nz <= (1 << 24), FIB_ERR_UNSUPPORTED, "a volume dimension above 2^24");
@@ -367,7 +356,7 @@ int pb_check(const PbRun &r, void *work, size_t work_bytes) {
     return ls_check_work(work, work_bytes, pb_work_bytes(nlines), "fibd_prob_work_size");
 }
 
-PbArgs pb_args(const PbRun &r, const PbWork &w) {
+PbArgs pb_args(const fib::ProbRun &r, const PbWork &w) {
     PbArgs a{};
     a.nx = r.nx; a.ny = r.ny; a.nz = r.nz; a.nvert = r.plan->nvert; a.nchunk = r.plan->nchunk; a.len_max = r.len_max; a.nsub = r.nsub;
     a.step = r.step; a.rng_seed = r.rng_seed; a.nlines = r.nseed * r.nsub; a.nvox = (int64_t)r.nx * r.ny * r.nz;
@@ -376,9 +365,14 @@ PbArgs pb_args(const PbRun &r, const PbWork &w) {
     return a;
 }
 
-// pass 1, len_min, the offsets; waits for the stream and returns the totals
-int pb_count(const PbRun &r, const PbWork &w, hipStream_t st, int64_t *nlines_out, int64_t *npoints_out) {
+}  // namespace
+
+size_t fib::prob_work_bytes(int64_t nlines) { return pb_work_bytes(nlines); }
+
+int fib::prob_count(const ProbRun &r, void *work, size_t work_bytes, hipStream_t st, int64_t *nlines_out, int64_t *npoints_out) {
+    FIB_RC(pb_check(r, work, work_bytes));
     const int64_t nlines = r.nseed * r.nsub;
+    const PbWork w = pb_work(work, nlines);
     if (nlines > 0) {
         fib::ProfScope prof("prob_trace_count", st);
         pb_trace_launch(false, pb_args(r, w), st);
@@ -392,18 +386,15 @@ int pb_count(const PbRun &r, const PbWork &w, hipStream_t st, int64_t *nlines_ou
     return FIB_OK;
 }
 
-// pass 2: the kept lines replayed into npts / seed_index / xyz (which hold at least the totals pb_count returned)
-int pb_emit(const PbRun &r, const PbWork &w, int32_t *npts, int64_t *seed_index, float *xyz, hipStream_t st) {
+int fib::prob_emit(const ProbRun &r, void *work, int32_t *npts, int64_t *seed_index, float *xyz, hipStream_t st) {
     if (r.nseed * r.nsub == 0) return FIB_OK;
-    PbArgs a = pb_args(r, w);
+    PbArgs a = pb_args(r, pb_work(work, r.nseed * r.nsub));
     a.npts = npts; a.seed_index = seed_index; a.xyz = xyz;
     fib::ProfScope prof("prob_trace_emit", st);
     pb_trace_launch(true, a, st);
     FIB_HIP(hipGetLastError());
     return FIB_OK;
 }
-
-}  // namespace
 
 extern "C" int fib_prob_row_pitch(int nvert) {
     return nvert >= 1 && nvert <= PB_NVERT_MAX ? 64 * ((nvert + 63) / 64) : 0;
@@ -459,7 +450,7 @@ extern "C" void fib_prob_plan_destroy(fib_prob_plan *plan) try { fib::plan_destr
 
 extern "C" int fibd_prob_work_size(int64_t nlines, size_t *bytes) try {
     FIB_CHECK(bytes && nlines >= 0, FIB_ERR_INVALID, "NULL bytes or negative nlines");
-    *bytes = pb_work_bytes(nlines);
+    *bytes = fib::prob_work_bytes(nlines);
     return FIB_OK;
 } FIB_API_CATCH
 
@@ -469,87 +460,16 @@ extern "C" int fibd_prob_run(const fib_prob_plan *plan, int nx, int ny, int nz, 
                              size_t work_bytes, void *stream) try {
     FIB_CHECK(nlines && npoints, FIB_ERR_INVALID, "NULL nlines / npoints");
     *nlines = 0; *npoints = 0;
-    const PbRun r{plan, nx, ny, nz, len_min, len_max, nsub, step_size, table, seeds, nseed, sublist, rng_seed};
-    FIB_RC(pb_check(r, work, work_bytes));
+    const fib::ProbRun r{plan, nx, ny, nz, len_min, len_max, nsub, step_size, table, seeds, nseed, sublist, rng_seed};
+    hipStream_t st = (hipStream_t)stream;
+    FIB_RC(fib::prob_count(r, work, work_bytes, st, nlines, npoints));
     FIB_CHECK(lines_cap >= 0 && points_cap >= 0, FIB_ERR_INVALID, "negative capacity");
     FIB_CHECK((lines_cap == 0 || (npts && seed_index)) && (points_cap == 0 || xyz), FIB_ERR_INVALID, "NULL output buffer");
     FIB_CHECK((reinterpret_cast<uintptr_t>(xyz) & 3) == 0, FIB_ERR_INVALID, "xyz must be 4-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const PbWork w = pb_work(work, nseed * nsub);
-    FIB_RC(pb_count(r, w, st, nlines, npoints));
     if (*nlines > lines_cap || *npoints > points_cap)
         return fib::fail(FIB_ERR_CAPACITY, "fibd_prob_run needs room for %lld lines and %lld points (capacities: %lld, %lld); nothing was written",
                          (long long)*nlines, (long long)*npoints, (long long)lines_cap, (long long)points_cap);
-    FIB_RC(pb_emit(r, w, npts, seed_index, xyz, st));
+    FIB_RC(fib::prob_emit(r, work, npts, seed_index, xyz, st));
     FIB_HIP(hipStreamSynchronize(st));
-    return FIB_OK;
-} FIB_API_CATCH
-
-extern "C" int fib_prob_stream(int device, int nx, int ny, int nz, const float *odf, int nvert, const float *vertices, const uint8_t *mask,
-                               const uint8_t *seed, const float *sublist, int32_t nsub, int32_t len_min, int32_t len_max, float cosang_thresh,
-                               float step_size, float pmf_thresh, int32_t subtract_min, uint64_t rng_seed, fib_tract_out *out) try {
-    FIB_CHECK(out, FIB_ERR_INVALID, "NULL out");
-    memset(out, 0, sizeof *out);
-    FIB_CHECK(device != FIB_DEVICE_ALL, FIB_ERR_UNSUPPORTED, "prob_stream runs on one device (FIB_DEVICE_ALL is not supported)");
-    FIB_CHECK(odf && vertices && sublist, FIB_ERR_INVALID, "NULL argument");
-    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
-    FIB_CHECK(nsub >= 1, FIB_ERR_INVALID, "sublist must hold at least one offset");
-    fib::DeviceGuard guard;
-    FIB_RC(fib::use_device(device));
-    fib_prob_plan *plan_raw = nullptr;
-    FIB_RC(fib_prob_plan_create(device, vertices, nvert, cosang_thresh, &plan_raw));
-    struct PlanGuard { fib_prob_plan *p; ~PlanGuard() { fib_prob_plan_destroy(p); } } pg{plan_raw};
-    const int64_t nvox = (int64_t)nx * ny * nz;
-    const int pitch = fib_prob_row_pitch(nvert);
-    // the table, from voxel chunks of the host ODF: the float ODF is never whole on the device
-    fib::DevBuf<uint16_t> d_table;
-    fib::DevBuf<float> d_odf;
-    fib::DevBuf<uint8_t> d_mask;
-    const int64_t chunk = std::min<int64_t>(nvox, (int64_t)1 << 18);
-    FIB_RC(d_table.alloc((size_t)nvox * pitch));
-    FIB_RC(d_odf.alloc((size_t)chunk * nvert));
-    if (mask) FIB_RC(d_mask.alloc((size_t)chunk));
-    for (int64_t v0 = 0; v0 < nvox; v0 += chunk) {
-        const int64_t n = std::min(chunk, nvox - v0);
-        FIB_HIP(hipMemcpy2D(d_odf.p, sizeof(float) * (size_t)n, odf + v0, sizeof(float) * (size_t)nvox, sizeof(float) * (size_t)n, (size_t)nvert,
-                            hipMemcpyHostToDevice));
-        if (mask) FIB_HIP(hipMemcpy(d_mask.p, mask + v0, (size_t)n, hipMemcpyHostToDevice));
-        FIB_RC(fibd_prob_table(d_odf.p, mask ? d_mask.p : nullptr, n, nvert, subtract_min, pmf_thresh, d_table.p + (size_t)v0 * pitch, nullptr));
-        FIB_HIP(hipStreamSynchronize(nullptr));                // (the chunk buffers are written again)
-    }
-    d_odf.release(); d_mask.release();
-    // seeds: the seed volume, else the mask, else every voxel; column-major order
-    const uint8_t *sv = seed ? seed : mask;
-    std::vector<int64_t> seeds;
-    for (int64_t i = 0; i < nvox; i++) if (!sv || sv[i]) seeds.push_back(i);
-    const int64_t nseed = (int64_t)seeds.size(), nall = nseed * nsub;
-    fib::DevBuf<int64_t> d_seeds, d_sidx, d_work;
-    fib::DevBuf<float> d_sub, d_xyz;
-    fib::DevBuf<int32_t> d_npts;
-    FIB_RC(d_seeds.alloc((size_t)nseed));
-    FIB_RC(d_sub.alloc((size_t)3 * nsub));
-    if (nseed) FIB_HIP(hipMemcpy(d_seeds.p, seeds.data(), sizeof(int64_t) * (size_t)nseed, hipMemcpyHostToDevice));
-    FIB_HIP(hipMemcpy(d_sub.p, sublist, sizeof(float) * 3 * nsub, hipMemcpyHostToDevice));
-    const size_t wb = pb_work_bytes(nall);
-    FIB_RC(d_work.alloc(wb / 8));
-    const PbRun r{plan_raw, nx, ny, nz, len_min, len_max, nsub, step_size, d_table.p, d_seeds.p, nseed, d_sub.p, rng_seed};
-    FIB_RC(pb_check(r, d_work.p, wb));
-    const PbWork w = pb_work(d_work.p, nall);
-    int64_t nl = 0, np = 0;
-    FIB_RC(pb_count(r, w, nullptr, &nl, &np));
-    FIB_RC(d_npts.alloc((size_t)nl));
-    FIB_RC(d_sidx.alloc((size_t)nl));
-    FIB_RC(d_xyz.alloc((size_t)3 * np));
-    FIB_RC(pb_emit(r, w, d_npts.p, d_sidx.p, d_xyz.p, nullptr));
-    out->npts = (int32_t *)malloc(sizeof(int32_t) * (size_t)std::max<int64_t>(nl, 1));
-    out->seed_index = (int64_t *)malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nl, 1));
-    out->xyz = (float *)malloc(sizeof(float) * 3 * (size_t)std::max<int64_t>(np, 1));
-    if (!out->npts || !out->seed_index || !out->xyz) { fib_tract_free(out); return fib::fail(FIB_ERR_NOMEM, "out of host memory"); }
-    hipError_t e = hipSuccess;
-    if (nl) e = hipMemcpy(out->npts, d_npts.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost);
-    if (nl && e == hipSuccess) e = hipMemcpy(out->seed_index, d_sidx.p, sizeof(int64_t) * (size_t)nl, hipMemcpyDeviceToHost);
-    if (np && e == hipSuccess) e = hipMemcpy(out->xyz, d_xyz.p, sizeof(float) * 3 * (size_t)np, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { fib_tract_free(out); return fib::fail(FIB_ERR_HIP, "download of the lines failed: %s", hipGetErrorString(e)); }
-    out->nlines = nl; out->npoints = np;
     return FIB_OK;
 } FIB_API_CATCH

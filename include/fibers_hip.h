@@ -856,8 +856,8 @@ int fibd_warp_invert(const void *packed, int nx, int ny, int nz, const float out
  * pipeline over voxel chunks (pinned staging ring: upload || kernels || download), and caches its plans and buffers
  * between calls; calls that share an entry are serialised, calls on different entries run concurrently.  A call that names one device
  * runs on that device's own entry.  Every host-buffer form holds its entry's lock from its first device buffer to its last copy, the
- * single-device forms (fib_st_eigen, fib_st_recon, fib_vol_xform, fib_warp_*, fib_rumba_rec, fib_find_peaks*, fib_str_*) included --
- * all of them but fib_prob_stream, which is not serialised against other calls and which fib_trim / fib_shutdown do not wait for.
+ * single-device forms (fib_st_eigen, fib_st_recon, fib_vol_xform, fib_warp_*, fib_rumba_rec, fib_find_peaks*, fib_str_*,
+ * fib_prob_stream) included; fib_trim / fib_shutdown wait for all of them.
  * (fib_rumba_rec and fib_find_peaks* build their plan, a few small tables on the device, before they take the lock.)
  * fib_init(ndev, devs): devs[i] may repeat (two pipelines on one GPU); ndev == 0 selects every visible device (also
  * the default of FIB_DEVICE_ALL without fib_init).  fib_shutdown releases every cached plan, stream and buffer.

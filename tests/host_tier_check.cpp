@@ -6,7 +6,8 @@
 // whose result is known in closed form.  What is checked: the results (every voxel of every output row, zero-filling outside the mask
 // included) and -- by ThreadSanitizer -- that no ring buffer is touched by two stages at once; plus the run arithmetic (LiveMap, piece
 // lists), the chunk schedule, slabs, chunk sizes, the mask element types and the line-chunk schedule of the tractogram host forms
-// against brute force.
+// against brute force; and what the tracking forms share: the owner of a result's arrays, the seed list, the round-robin seed share of a
+// device set with its inverse, the merge of the shards.
 #include <cmath>
 #include <cstdio>
 #include <deque>
@@ -278,8 +279,124 @@ static void units() {
     }
 }
 
+// ---- the result of a tracking form: the owner of its arrays, the seed list, the seed share of a device set, the merge of its shards ----
+static void tract_units() {
+    std::mt19937 rng(77);
+    // the seed list against a plain loop: no volume (every voxel), none set, all set, some set
+    for (int64_t nvox : {1ll, 7ll, 300ll})
+        for (int kind = 0; kind < 4; kind++) {
+            std::vector<uint8_t> sv((size_t)nvox);
+            for (auto &b : sv) b = kind == 1 ? 0 : (kind == 2 ? 1 : (uint8_t)(rng() % 3 == 0 ? rng() % 255 + 1 : 0));
+            std::vector<int64_t> got = {99, 98}, want;                                     // (what the vector held before does not stay)
+            seed_voxels(kind == 0 ? nullptr : sv.data(), nvox, got);
+            for (int64_t i = 0; i < nvox; i++) if (kind == 0 || sv[i]) want.push_back(i);
+            CHECK(got == want);
+            if (kind == 1) CHECK(got.empty());
+            if (kind == 0 || kind == 2) CHECK((int64_t)got.size() == nvox);
+        }
+    // the seed share of worker w of nw and its inverse on a line's seed_index: every (seed, sub) of the whole list exactly once, each
+    // shard's global indices ascending
+    for (int nw : {1, 2, 3, 5})
+        for (int nsub : {1, 3})
+            for (int nseed : {0, 1, 7}) {
+                std::vector<int64_t> seeds((size_t)nseed);
+                for (int i = 0; i < nseed; i++) seeds[i] = 1000 + 13 * i;                  // (voxel numbers: distinct, ascending)
+                std::vector<int> seen((size_t)nseed * nsub, 0);
+                size_t dealt = 0;
+                for (int w = 0; w < nw; w++) {
+                    std::vector<int64_t> mine = {5};
+                    seed_share(seeds, w, nw, mine);
+                    dealt += mine.size();
+                    int64_t prev = -1;
+                    for (size_t ls = 0; ls < mine.size(); ls++)
+                        for (int sub = 0; sub < nsub; sub++) {
+                            const int64_t g = global_seed_index((int64_t)ls * nsub + sub, w, nw, nsub);
+                            CHECK(g > prev && g >= 0 && g < (int64_t)nseed * nsub);
+                            prev = g;
+                            CHECK(seeds[(size_t)(g / nsub)] == mine[ls] && g % nsub == sub);      // the line's seed of the whole list is the worker's seed
+                            seen[(size_t)g]++;
+                        }
+                }
+                CHECK(dealt == (size_t)nseed);
+                for (int c : seen) CHECK(c == 1);
+            }
+    // the owner: alloc leaves no array NULL (one element each where there is no line), the hand-over leaves the owner empty and the
+    // arrays with the caller (free() releases them, as fib_tract_free does); a destroyed owner frees its arrays (the leak check)
+    for (bool with_flags : {false, true})
+        for (int64_t nl : {0ll, 5ll}) {
+            TractArrays t;
+            CHECK(t.alloc(nl, 3 * nl, with_flags));
+            CHECK(t.npts && t.sidx && t.xyz && (t.flags != nullptr) == with_flags && t.nl == nl && t.np == 3 * nl);
+            t.npts[0] = 1; t.sidx[0] = 2; t.xyz[2] = 3.0f;                                 // max(n, 1) elements are there
+            if (with_flags) t.flags[0] = 4;
+            fib_tract_out out;
+            memset(&out, 0xff, sizeof out);
+            int32_t *const p = t.npts; float *const x = t.xyz;
+            t.give(&out);
+            CHECK(!t.npts && !t.sidx && !t.xyz && !t.flags && t.nl == 0 && t.np == 0);
+            CHECK(out.nlines == nl && out.npoints == 3 * nl && out.npts == p && out.xyz == x && out.seed_index && (out.flags != nullptr) == with_flags);
+            CHECK(out.npts[0] == 1 && out.seed_index[0] == 2 && out.xyz[2] == 3.0f);
+            free(out.npts); free(out.seed_index); free(out.xyz); free(out.flags);
+        }
+    { TractArrays t; CHECK(t.alloc(100, 1000, true)); CHECK(t.alloc(3, 4, false) && !t.flags); }   // (a second alloc and the destructor release)
+    // a request at the threshold and above it is 2-MB aligned, one below it is a plain malloc
+    for (size_t bytes : {RESULT_HUGE_BYTES, RESULT_HUGE_BYTES + 12345}) {
+        char *p = (char *)alloc_result(bytes);
+        CHECK(p && ((uintptr_t)p & (RESULT_HUGE_ALIGN - 1)) == 0);
+        p[0] = 1; p[bytes - 1] = 2;
+        free(p);
+    }
+    CHECK(RESULT_HUGE_BYTES == (size_t)32 << 20 && RESULT_HUGE_ALIGN == (size_t)2 << 20);
+    { void *p = alloc_result(0); CHECK(p); free(p); }
+    { TractArrays t; CHECK(t.alloc(1, (int64_t)(RESULT_HUGE_BYTES / 12) + 1, false) && ((uintptr_t)t.xyz & (RESULT_HUGE_ALIGN - 1)) == 0); }
+    // the merge against brute force: concatenate the shards, stable-sort by seed_index.  1 to 4 shards of random line lengths, empty
+    // shards, zero-point lines, no line anywhere (the arrays are there all the same)
+    for (int trial = 0; trial < 60; trial++) {
+        const int nw = 1 + trial % 4;
+        const bool nothing = trial < 4;
+        std::vector<TractArrays> sh((size_t)nw);
+        struct Line { int64_t sidx; int32_t n; std::vector<float> xyz; };
+        std::vector<Line> all;
+        int64_t nl = 0, np = 0;
+        for (int w = 0; w < nw; w++) {
+            const int64_t l = nothing || rng() % 4 == 0 ? 0 : (int64_t)(rng() % 9);
+            std::vector<Line> mine((size_t)l);
+            int64_t p = 0, s = 0;
+            for (auto &ln : mine) {
+                s += rng() % 3;                                                            // ascending within a shard, equal ones within and between shards
+                ln.sidx = s; ln.n = rng() % 3 == 0 ? 0 : (int32_t)(rng() % 6);
+                for (int i = 0; i < 3 * ln.n; i++) ln.xyz.push_back((float)(rng() % 100000));
+                p += ln.n;
+            }
+            CHECK(sh[w].alloc(l, p, false));
+            int64_t o = 0;
+            for (int64_t i = 0; i < l; i++) {
+                sh[w].npts[i] = mine[i].n; sh[w].sidx[i] = mine[i].sidx;
+                if (mine[i].n) memcpy(sh[w].xyz + 3 * o, mine[i].xyz.data(), sizeof(float) * 3 * mine[i].n);
+                o += mine[i].n;
+            }
+            all.insert(all.end(), mine.begin(), mine.end());
+            nl += l; np += p;
+        }
+        std::stable_sort(all.begin(), all.end(), [](const Line &a, const Line &b) { return a.sidx < b.sidx; });
+        TractArrays out;
+        CHECK(out.alloc(nl, np, false));
+        merge_lines(sh.data(), nw, out);
+        CHECK(out.nl == nl && out.np == np && out.npts && out.sidx && out.xyz && !out.flags);
+        if (nothing) CHECK(nl == 0 && np == 0);
+        int64_t o = 0;
+        for (int64_t i = 0; i < nl; i++) {
+            CHECK(out.npts[i] == all[i].n && out.sidx[i] == all[i].sidx);
+            CHECK(all[i].n == 0 || !memcmp(out.xyz + 3 * o, all[i].xyz.data(), sizeof(float) * 3 * all[i].n));
+            o += all[i].n;
+        }
+        CHECK(o == np);
+    }
+}
+
 int main() {
     units();
+    tract_units();
     unsigned seed = 1;
     // whole rows (no packing): one chunk, exactly NBUF chunks, many more chunks than ring slots, a sub-range, every mask
     for (int mk : {0, 1, 2}) {

@@ -373,3 +373,92 @@ def test_host_form_walks_voxel_chunks(fj):
     assert want["npts"].size > 40 and want["npts"].max() == 32
     assert np.array_equal(tr.npts, want["npts"]) and np.array_equal(tr.seed_index, want["seed_index"])
     assert np.asarray(tr.xyz, F32).tobytes() == want["xyz"].tobytes()
+
+
+# ---- the host form on its worker: the lock, an empty result, what stays on the device ------------------------------------------------
+def _host_args(fj, odfs, mask, name="sphere_362", seed=None, **kw):
+    return dict(dict(odf=odfs[name][2], odf_dirs=getattr(fj, name), mask=fj.MRI(np.asfortranarray(mask.reshape(SHAPE, order="F"))), seed=seed,
+                     sublist=_sublist(2), len_min=3, ang_thresh=45, step_size=0.5, pmf_thresh=0.1, rng_seed=31), **kw)
+
+
+def _host_bytes(fj, args):
+    a = dict(args)
+    tr = fj.prob_stream(a.pop("odf"), a.pop("odf_dirs"), **a)
+    return tr.npts.tobytes(), tr.seed_index.tobytes(), np.asarray(tr.xyz, F32).tobytes()
+
+
+def test_host_form_calls_from_three_threads_with_trim_between_them(fj, odfs, mask):
+    """Three threads make the same prob_stream call on device 0 while a fourth calls trim() between its own short sleeps: every result
+    is byte-equal to that of a single call made before.  (The worker's lock cannot be seen from outside; this is what a caller sees.)"""
+    import threading
+    import time
+    args = _host_args(fj, odfs, mask)
+    want = _host_bytes(fj, args)
+    assert len(want[2]) > 12 * 1000
+    got, errors, done = [None] * 3, [], threading.Event()
+
+    def call(i):
+        try:
+            got[i] = [_host_bytes(fj, args) for _ in range(3)]
+        except Exception as e:                                                 # noqa: BLE001
+            errors.append(e)
+
+    def trimmer():
+        try:
+            while not done.is_set():
+                time.sleep(0.002)
+                fj.trim()
+        except Exception as e:                                                 # noqa: BLE001
+            errors.append(e)
+
+    th = [threading.Thread(target=call, args=(i,)) for i in range(3)]
+    tt = threading.Thread(target=trimmer)
+    tt.start()
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    done.set()
+    tt.join()
+    assert not errors, errors
+    assert all(r == want for rs in got for r in rs)
+
+
+def test_host_form_without_a_seed_returns_empty_arrays(fj, odfs, mask):
+    """an all-zero seed volume: nlines = npoints = 0, the three arrays are there all the same, fib_tract_free takes them"""
+    from fibers_jl_amd import _lib
+    name = "sphere_362"
+    U, _, odf_mri = odfs[name]
+    vol = np.asfortranarray(odf_mri.vol, dtype=F32)
+    m8 = np.ascontiguousarray(mask, np.uint8)
+    s8 = np.zeros(NVOX, np.uint8)
+    sub = _sublist(2)
+    out = _lib.TractOut()
+    L = fj.lib()
+    rc = L.fib_prob_stream(0, *SHAPE, vol.ctypes.data, U.shape[0], U.ctypes.data, m8.ctypes.data, s8.ctypes.data, sub.ctypes.data, 2, 3, 12,
+                           float(np.cos(np.deg2rad(F32(45)))), 0.5, 0.1, 1, 31, C.byref(out))
+    assert rc == 0, L.fib_last_error()
+    assert out.nlines == 0 and out.npoints == 0
+    assert out.npts and out.seed_index and out.xyz and not out.flags
+    L.fib_tract_free(C.byref(out))
+    assert not out.npts and not out.seed_index and not out.xyz and not out.flags and out.nlines == 0 and out.npoints == 0
+    tr = fj.prob_stream(odf_mri, getattr(fj, name), mask=fj.MRI(np.asfortranarray(mask.reshape(SHAPE, order="F"))),
+                        seed=fj.MRI(np.zeros(SHAPE, np.uint8, order="F")), sublist=sub)
+    assert tr.npts.size == 0 and tr.seed_index.size == 0 and tr.xyz.shape == (0, 3)
+
+
+def test_host_form_keeps_no_device_memory_past_trim(fj, odfs, mask):
+    """after a warm-up call and trim(), a call and trim() leave the free device memory where it was: the table, the result buffers and
+    the output ring's mirror all go back"""
+    import torch
+    args = _host_args(fj, odfs, mask)
+    _host_bytes(fj, args)
+    fj.trim()
+    torch.cuda.synchronize()
+    before = torch.cuda.mem_get_info()[0]
+    _host_bytes(fj, args)
+    fj.trim()
+    torch.cuda.synchronize()
+    after = torch.cuda.mem_get_info()[0]
+    print("free device memory before / after: %d / %d" % (before, after))
+    assert after == before

@@ -1,5 +1,6 @@
 """The argument refusals of the single-device host forms (csrc/api.hip: fib_st_eigen, fib_st_recon, fib_vol_xform, fib_warp_points,
-fib_warp_volume, fib_warp_invert, fib_rumba_rec, fib_find_peaks, fib_find_peaks_work) that come back before the call takes its device:
+fib_warp_volume, fib_warp_invert, fib_rumba_rec, fib_find_peaks, fib_find_peaks_work, fib_prob_stream) that come back before the call takes its
+device:
 one table, each row a call with one argument spoiled, its return code and a distinguishing piece of fib_last_error().  No GPU is
 needed: a row that reached the device would answer FIB_ERR_NO_DEVICE here, and on a machine with a GPU it would run."""
 import ctypes as C
@@ -28,6 +29,7 @@ S6_HOLE = (C.c_void_p * 6)(*[S6[k] if k != 3 else None for k in range(6)])
 EVEC, EVAL = _p(9 * 64), _p(3 * 64)
 ODF, VERTS, FACES, TOP, NVALID = _p(8 * 181), _p(3 * 362), _p(3 * 720, np.int32), _p(8 * 181, np.int32), _p(8, np.int32)
 DWI, MASK, BV, BVC = _p(8 * 4), _p(8, np.uint8), _p(4), _p(12)
+SUB = _p(3)
 
 # name -> (the arguments of a call that passes every check made before the device, by position)
 GOOD = {
@@ -40,6 +42,7 @@ GOOD = {
     "fib_rumba_rec": [0, DWI, 2, 2, 2, 4, MASK, 0, BV, BVC, VERTS, 362, 5, 1.7e-3, 0.2e-3, 3.0e-3, 0.8e-3, 1, 1, 1, 0, "out", None, None],
     "fib_find_peaks": [0, ODF, 8, VERTS, 362, FACES, 720, TOP, NVALID],
     "fib_find_peaks_work": [0, ODF, 8, VERTS, 362, FACES, 720, EVEC, TOP, NVALID],
+    "fib_prob_stream": [0, 2, 2, 2, ODF, 181, VERTS, None, None, SUB, 1, 3, 8, 0.7, 0.5, 0.1, 1, 0, "tract"],
 }
 
 NULLARG, DIMS, FDIMS = b"NULL argument", b"volume dimensions and nframes must be positive", b"the field's dimensions must be positive"
@@ -146,6 +149,22 @@ def _rows():
             for pos in ptrs:                                                                # a NULL pointer is named before a bad size
                 for change in ({2: 0}, {4: 0}, {4: 1}, {4: -1}, {6: 0}):
                     add(name, {0: dev, pos: None, **change}, INV, NULLARG)
+    # fib_prob_stream: out, the device set, the pointers, the dimensions, nsub -- in that order
+    one_dev = b"prob_stream runs on one device (FIB_DEVICE_ALL is not supported)"
+    add("fib_prob_stream", {18: None}, INV, b"NULL out")
+    add("fib_prob_stream", {18: None, 0: ALL, 4: None}, INV, b"NULL out")
+    add("fib_prob_stream", {0: ALL}, UNS, one_dev)
+    add("fib_prob_stream", {0: ALL, 4: None}, UNS, one_dev)                                  # the device set is refused before a NULL odf
+    add("fib_prob_stream", {0: ALL, 1: 0, 10: 0}, UNS, one_dev)
+    for pos in (4, 6, 9):
+        add("fib_prob_stream", {pos: None}, INV, NULLARG)
+        add("fib_prob_stream", {pos: None, 2: 0, 10: 0}, INV, NULLARG)                       # a NULL pointer is named before a bad size
+    for pos in (1, 2, 3):
+        for n in (0, -1):
+            add("fib_prob_stream", {pos: n}, INV, b"volume dimensions must be positive")
+    add("fib_prob_stream", {3: 0, 10: 0}, INV, b"volume dimensions must be positive")
+    for n in (0, -1):
+        add("fib_prob_stream", {10: n}, INV, b"sublist must hold at least one offset")
     return t
 
 
@@ -162,18 +181,24 @@ def rumba_out(fj):
     return out
 
 
+@pytest.fixture(scope="module")
+def tract_out(fj):
+    from fibers_jl_amd import _lib
+    return _lib.TractOut()
+
+
 def test_every_entry_has_rows():
-    assert {r[0] for r in ROWS} == set(GOOD) and len(GOOD) == 9
+    assert {r[0] for r in ROWS} == set(GOOD) and len(GOOD) == 10
 
 
 @pytest.mark.parametrize("name", sorted(GOOD))
-def test_refusals_before_the_device(fj, rumba_out, name):
+def test_refusals_before_the_device(fj, rumba_out, tract_out, name):
     L = fj.lib()
     fn = getattr(L, name)
     rows = [r for r in ROWS if r[0] == name]
     assert rows
     for _, change, code, msg in rows:
-        args = [C.byref(rumba_out) if isinstance(a, str) else a for a in GOOD[name]]
+        args = [C.byref({"out": rumba_out, "tract": tract_out}[a]) if isinstance(a, str) else a for a in GOOD[name]]
         for pos, v in change.items():
             args[pos] = v
         rc = fn(*args)
@@ -181,3 +206,4 @@ def test_refusals_before_the_device(fj, rumba_out, name):
         assert rc == code and msg in err, (name, change, rc, err)
     # nothing was written
     assert not any(a.any() for a in _keep)
+    assert not any(bytes(tract_out))

@@ -5,7 +5,10 @@ on the GQI ODF (sphere_642: 321 directions) of the 140^3 x 270-frame phantom:
   prob      fibd_prob_run on the seeds of the ball mask with one sub-voxel offset (the deterministic tracer's benchmark seeds): total
             steps, points, ms; the two passes separately (the library's profile brackets: the count pass alone is what a tracer with
             scratch rows would run, the emit pass is the price of the replay); the row-gather rate steps x pitch x 2 B per pass;
-  stream    fibd_stream_run on the same volume's three GQI peaks, the same seeds: the deterministic tracer as it was before this tool.
+  stream    fibd_stream_run on the same volume's three GQI peaks, the same seeds: the deterministic tracer as it was before this tool;
+  host_form fib_prob_stream on the same ODF, mask and offset in pageable host arrays: the wall time of the call (table from chunks of the
+            host ODF, both passes, the lines down into arrays the library allocates; fib_tract_free is outside).  --host-form-only
+            runs this row alone and writes host_form.json.
 With the diagnostic build of the library (`make stamp`, FIBERS_HIP_LIB) both lane mappings run: FIBERS_PROB_LANES=64 selects a wave per
 line instead of 16 lanes per line.  Writes timings.json (timings_diagnostic.json under the diagnostic build) into --out (default
 profiles/prob_stream); the README.md beside them is written by hand from the two."""
@@ -15,6 +18,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -47,12 +51,38 @@ def prof_get(name):
     return ms.value / max(n.value, 1)
 
 
+def host_form(odf, bm, shape, sph, sub):
+    """fib_prob_stream on host copies of the device operands; ms = the median wall time of RUNS calls after WARM"""
+    import numpy as np
+    from fibers_jl_amd import _lib
+    L = fj.lib()
+    vol = np.ascontiguousarray(odf.cpu().numpy())                          # [nvert, nvox] planar == MRI.vol memory
+    m8 = np.ascontiguousarray(bm.reshape(-1).to(torch.uint8).cpu().numpy())
+    U = np.ascontiguousarray(sph.vertices[: sph.nvert], np.float32)
+    s = np.ascontiguousarray(sub.cpu().numpy())
+    cosang = fj.ProbPlan(sph, 45, 0).cosang_thresh
+    ms, res = [], {}
+    for i in range(WARM + RUNS):
+        out = _lib.TractOut()
+        t0 = time.perf_counter()
+        rc = L.fib_prob_stream(0, shape[0], shape[1], shape[2], vol.ctypes.data, U.shape[0], U.ctypes.data, m8.ctypes.data, None, s.ctypes.data,
+                               s.shape[0], 3, max(shape), cosang, 0.5, 0.1, 1, 1, C.byref(out))
+        t = (time.perf_counter() - t0) * 1e3
+        _lib.check(rc)
+        res = dict(lines=int(out.nlines), points=int(out.npoints))
+        L.fib_tract_free(C.byref(out))
+        if i >= WARM:
+            ms.append(t)
+    return dict(ms=statistics.median(ms), all_ms=ms, bytes_in=vol.nbytes + m8.nbytes, bytes_out=12 * res["points"] + 12 * res["lines"], **res)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "prob_stream"))
     ap.add_argument("--size", type=int, default=140)
     ap.add_argument("--runs", type=int, default=RUNS, help="timed runs per figure (1 with --warm 0: a short run to collect counters over)")
     ap.add_argument("--warm", type=int, default=WARM)
+    ap.add_argument("--host-form-only", action="store_true", help="the host_form row alone, into host_form.json")
     a = ap.parse_args()
     globals().update(RUNS=a.runs, WARM=a.warm)
     dev = torch.device("cuda", 0)
@@ -69,6 +99,16 @@ def main():
     res = dict(device=torch.cuda.get_device_name(0), lib=os.path.basename(fj.LIB_PATH), runs=RUNS, warmups=WARM, shape=list(shape), nvert=nvert,
                pitch=pitch)
 
+    sub = torch.tensor([[0.1, -0.2, 0.3]], dtype=torch.float32, device=dev)
+    if a.host_form_only:
+        res["host_form"] = host_form(o["odf"], bm, shape, sph, sub)
+        print("host_form", json.dumps(res["host_form"]), flush=True)
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "host_form.json"), "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
+
     # ---- table
     table = torch.empty((nvox, pitch), dtype=torch.uint16, device=dev)
     t_tab = timed(lambda: fj.probtrack.prob_table_device(o["odf"], bm, out=table))
@@ -83,7 +123,6 @@ def main():
 
     # ---- the deterministic tracer on the three peaks (the code path of the commit before probtrack.hip)
     seeds = torch.nonzero(bm).flatten()
-    sub = torch.tensor([[0.1, -0.2, 0.3]], dtype=torch.float32, device=dev)
     field, mout = fj.stream_field_device(o["peak"], f=o["qa"], f_thresh=0.03, mask=bm)
     sbuf = fj.StreamBuffers(dev)
     r = {}
@@ -94,6 +133,7 @@ def main():
     res["stream_run_3peaks"] = dict(ms=t_det, seeds=int(seeds.numel()), lines=int(r["r"]["npts"].numel()), points=int(r["r"]["xyz"].shape[0]),
                                     mpoints_per_s=int(r["r"]["xyz"].shape[0]) / t_det / 1e3)
     print("stream_run", json.dumps(res["stream_run_3peaks"]), flush=True)
+    odf = o["odf"]
     del field, mout, sbuf, o
     r.clear()
 
@@ -133,6 +173,10 @@ def main():
                                       row_gather_tbs_emit_pass=steps2 * pitch * 2 / emit_ms / 1e9 if emit_ms else None)
         print(label, json.dumps(res["prob_run"][label]), flush=True)
     os.environ.pop("FIBERS_PROB_LANES", None)
+    del table, pbuf, work, r
+
+    res["host_form"] = host_form(odf, bm, shape, sph, sub)
+    print("host_form", json.dumps(res["host_form"]), flush=True)
 
     os.makedirs(a.out, exist_ok=True)
     name = "timings_diagnostic" if diagnostic else "timings"
