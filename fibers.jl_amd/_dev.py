@@ -4,8 +4,6 @@ caller's outputs alike), launches inside `Launch` and takes its scratch from `wo
 launch."""
 import ctypes as C
 
-import numpy as np
-
 from . import _lib
 
 
@@ -16,11 +14,6 @@ class ArgError(ValueError, TypeError):
 def float3(v):
     """the `const float[3]` argument of the C ABI (voxel sizes)"""
     return (C.c_float * 3)(*[float(x) for x in v])
-
-
-def packed(tr):
-    """a Tract's points and counts as the fib_str_* entries take them: float32 [npoints, 3], int32 [nlines]"""
-    return np.ascontiguousarray(np.asarray(tr.xyz, np.float32).reshape(-1, 3)), np.ascontiguousarray(tr.npts, dtype=np.int32)
 
 
 def _index(ref):
@@ -65,6 +58,28 @@ def tensor(t, dtype, what, ref=None, n=None, unit=None, shape=None, bool_ok=Fals
             if isinstance(t, torch.Tensor) else type(t).__name__
         raise ArgError("%s must be a contiguous%s, not %s" % (what, "".join(want), got))
     return t
+
+
+def fit_args(plan, dwi, mask):
+    """the inputs of a plan's fit: dwi float32 [plan.nvol, nvox], mask uint8 [nvox], both on the plan's device -> nvox"""
+    import torch
+    nvox = tensor(mask, torch.uint8, "mask", ref=plan).numel()
+    tensor(dwi, torch.float32, "dwi [nvol, nvox]", ref=plan, n=nvox * plan.nvol)
+    return nvox
+
+
+def points(xyz, what="xyz", ref=None):
+    """float32 [npoints, 3] (on the device of `ref`) -> npoints"""
+    import torch
+    if tensor(xyz, torch.float32, what, ref=ref).numel() % 3:
+        raise ArgError("%s must hold whole points [npoints, 3], not %d coordinates" % (what, xyz.numel()))
+    return xyz.numel() // 3
+
+
+def lines(xyz, npts):
+    """the checks every tract tool starts with: xyz float32 [npoints, 3], npts int32 [nlines] on its device -> (npoints, nlines)"""
+    import torch
+    return points(xyz), tensor(npts, torch.int32, "npts", ref=xyz).numel()
 
 
 def stream_ptr(stream):

@@ -13,8 +13,9 @@ import numpy as np
 
 from . import _lib
 from .tract import Tract
-from ._dev import ArgError, Launch, float3 as _res, packed as _packed, tensor, work as _work
-from .tractmap import _lines, str_sample, str_work_size
+from ._dev import ArgError, Launch, float3 as _res, lines as _lines, tensor, work as _work
+from ._host import packed as _packed
+from .tractmap import str_sample, str_work_size
 
 
 @dataclass

@@ -11,10 +11,8 @@ from typing import List
 
 import numpy as np
 
-from . import _lib
-from ._dev import ArgError, Launch, Plan, tensor
-from .dti import _check_tables, _table_args, _dwi_arg, _fit_args, _mask_arg, _mask_checked
-from .gqi import _odf_args, _p3
+from . import _host, _lib
+from ._dev import ArgError, Launch, Plan, fit_args, tensor
 from .mri import MRI
 from .nifti import csd_write  # noqa: F401
 from .odf import ODF, sphere_724
@@ -47,7 +45,7 @@ def _params(response, lmax, b0_thresh, shell, b_tol, lam, tau, niter):
 def csd_response(dti, mask, fa_thresh: float = 0.7):
     """The single-fibre response from a tensor fit: (mean eigval1, mean (eigval2 + eigval3) / 2, mean s0) over the voxels inside the
     mask whose fa exceeds fa_thresh, summed in float64 on the host.  Raises when no voxel qualifies."""
-    m, _ = _mask_arg(mask)
+    m, _ = _host.mask(mask)
     fa = dti.fa.vol[..., 0] if dti.fa.vol.ndim == 4 else dti.fa.vol
     sel = (m != 0) & (fa > fa_thresh)
     if not sel.any():
@@ -64,9 +62,9 @@ def csd_design(bval, bvec, response, odf_dirs: ODF = sphere_724, lmax: int = DEF
     """The reconstruction's tables, built on the host in float64 and rounded once: dict(frames int32 [nshell] (0-based), R float32
     [lmax / 2 + 1], X [nshell, n], B [nreg, n], Y [nreg, n], rank).  response = (lambda_para, lambda_perp, s0).  A shell of fewer than n
     frames, or one whose kernel matrix has a rank below n, raises FibersError (code -1)."""
-    bval, bv = _table_args(bval, bvec)
+    bval, bv = _host.table_args(bval, bvec)
     nvol, n, nreg = int(bval.shape[0]), ncoef(lmax), odf_dirs.nvert
-    v, _ = _odf_args(odf_dirs)
+    v = _host.directions(odf_dirs)
     p = _params(response, lmax, b0_thresh, shell, b_tol, lam, DEFAULTS["tau"], DEFAULTS["niter"])
     frames = np.zeros(nvol, np.int32)
     R = np.zeros(5, np.float32)
@@ -86,19 +84,16 @@ def csd_rec(dwi: MRI, mask: MRI, response, odf_dirs: ODF = sphere_724, lmax: int
             tau: float = DEFAULTS["tau"], niter: int = DEFAULTS["niter"], device: int = 0) -> CSD:
     """Constrained spherical deconvolution of one shell of `dwi` and return a `CSD` structure.  response = (lambda_para, lambda_perp,
     s0), e.g. from `csd_response`.  device: a GPU index, or _lib.DEVICE_ALL for the device set declared with fibers_jl_amd.init()."""
-    bval, bvec = _check_tables(dwi)
-    vol = _dwi_arg(dwi)
+    bval, bvec = _host.check_tables(dwi)
+    vol, m, mdt = _host.fit_inputs(dwi, mask)
     nx, ny, nz, nvol = vol.shape
-    m, mdt = _mask_checked(mask, (nx, ny, nz))
-    v, fc = _odf_args(odf_dirs)
+    v, fc = _host.directions(odf_dirs, faces=True)
     p = _params(response, lmax, b0_thresh, shell, b_tol, lam, tau, niter)
     if int(lmax) not in (2, 4, 6, 8):
         raise ValueError("lmax must be 2, 4, 6 or 8")
-    ref = mask if isinstance(mask, MRI) else dwi
-    sh, odf, nit = MRI.like(ref, ncoef(lmax)), MRI.like(ref, odf_dirs.nvert), MRI.like(ref, 1)
-    peak = [MRI.like(ref, 3) for _ in range(3)]
-    f = [MRI.like(ref, 1) for _ in range(3)]
-    o = _lib.CsdOut(sh.vol.ctypes.data, odf.vol.ctypes.data, nit.vol.ctypes.data, _p3(peak), _p3(f))
+    sh, odf, nit, *pf = _host.fit_outputs(dwi, mask, [ncoef(lmax), odf_dirs.nvert, 1, 3, 3, 3, 1, 1, 1])
+    peak, f = pf[:3], pf[3:]
+    o = _lib.CsdOut(sh.vol.ctypes.data, odf.vol.ctypes.data, nit.vol.ctypes.data, _host.pointers(peak), _host.pointers(f))
     _lib.check(_lib.lib().fib_csd_rec(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
                                       bval.ctypes.data, bvec.ctypes.data, v.ctypes.data, v.shape[0], fc.ctypes.data, fc.shape[0],
                                       C.byref(p), C.byref(o)))
@@ -113,9 +108,9 @@ class CsdPlan(Plan):
                  b0_thresh: float = DEFAULTS["b0_thresh"], shell=DEFAULTS["shell"], b_tol: float = DEFAULTS["b_tol"],
                  lam: float = DEFAULTS["lam"], tau: float = DEFAULTS["tau"], niter: int = DEFAULTS["niter"], device: int = 0):
         Plan.__init__(self, device)
-        bval, bv = _table_args(bval, bvec)
+        bval, bv = _host.table_args(bval, bvec)
         self.nvol, self.lmax, self.n, self.nreg = int(bval.shape[0]), int(lmax), ncoef(lmax), odf_dirs.nvert
-        v, fc = _odf_args(odf_dirs)
+        v, fc = _host.directions(odf_dirs, faces=True)
         p = _params(response, lmax, b0_thresh, shell, b_tol, lam, tau, niter)
         _lib.check(_lib.lib().fib_csd_plan_create(device, bval.ctypes.data, bv.ctypes.data, self.nvol, v.ctypes.data, v.shape[0],
                                                   fc.ctypes.data, fc.shape[0], C.byref(p), C.byref(self._h)))
@@ -139,7 +134,7 @@ def csd_rec_device(plan: CsdPlan, dwi, mask, out=None, stream=None):
     """dwi: float32 CUDA tensor [nvol, nvox] (planar, every frame of the scheme), mask: uint8 CUDA tensor [nvox].  Returns a dict of
     tensors: sh [n, nvox], odf [nreg, nvox], niter [nvox], peak [3][3, nvox], f [3][nvox] (`out`: such a dict to write into)."""
     import torch
-    nvox = _fit_args(plan, dwi, mask)
+    nvox = fit_args(plan, dwi, mask)
     with Launch(dwi, stream) as L:
         if out is None:
             out = dict(sh=L.empty((plan.n, nvox), torch.float32), odf=L.empty((plan.nreg, nvox), torch.float32),

@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, tensor, work as _work
 from .mri import MRI
 
@@ -43,17 +43,12 @@ def dwi_denoise(dwi, mask=None, patch=5, estimator="exp2", device=0) -> Denoised
     in (3, 5, 7), and return a `Denoised` structure.  estimator: "exp1" (Veraart 2016) or "exp2" (Cordero-Grande 2019)."""
     est = _estimator(estimator)
     src = dwi if isinstance(dwi, MRI) else MRI(np.asarray(dwi))
-    vol = np.asfortranarray(src.vol, dtype=np.float32)
+    vol = _host.volume(src, dtype=np.float32, series=True)
     nx, ny, nz, nvol = vol.shape
     if mask is None:
         m = np.ones((nx, ny, nz), np.uint8, order="F")
     else:
-        m = mask.vol if isinstance(mask, MRI) else np.asarray(mask)
-        if m.ndim == 4 and m.shape[3] == 1:
-            m = m[..., 0]
-        if m.shape != (nx, ny, nz):
-            raise ValueError("mask of shape %s for a volume of %s" % (m.shape, (nx, ny, nz)))
-        m = np.asfortranarray(m != 0, dtype=np.uint8)
+        m, _ = _host.mask(mask, (nx, ny, nz), "!= 0", frame0=False, refuse="mask of shape %s for a volume of %s")
     out = MRI(np.zeros(vol.shape, np.float32, order="F"), bval=src.bval, bvec=src.bvec, volres=src.volres, vox2ras=src.vox2ras.copy(), tr=src.tr)
     sigma, rank = MRI.like(src, 1), MRI.like(src, 1)
     _lib.check(_lib.lib().fib_dwi_denoise(int(device), vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, int(patch), est,

@@ -7,9 +7,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._dev import Launch, Plan, tensor
-from .dti import DTI_FIELDS, _check_tables, _table_args, _dwi_arg, _fit_args, _mask_checked
+from . import _host, _lib
+from ._dev import Launch, Plan, fit_args, tensor
+from .dti import DTI_FIELDS
 from .mri import MRI
 from .odf import ODF, sphere_642
 
@@ -40,22 +40,22 @@ class DKI:
     kt: MRI
 
 
-def _nframes(k):
+def nframes(k):
+    """frames of the output field `k` (of DKI_FIELDS)"""
     return 3 if "vec" in k else (15 if k == "kt" else 1)
+
+
+_nframes = nframes      # the name tests/test_gpu_device_args.py, written before the rename, builds its rows with
 
 
 def _params(min_signal, min_diffusivity, min_kurtosis, max_kurtosis):
     return _lib.DkiParams(min_signal, min_diffusivity, min_kurtosis, max_kurtosis)
 
 
-def _verts(odf_dirs: ODF):
-    return np.asfortranarray(odf_dirs.vertices, dtype=np.float32)
-
-
 def dki_design(bval, bvec):
     """The fit's tables, built on the host in float64 and rounded once: (A [nvol, 22] with b in ms/um^2, pA [22, nvol] scaled to
     mm^2/s and mm^4/s^2, rank).  A scheme whose design has a rank below 22 raises FibersError (code -1)."""
-    bval, bv = _table_args(bval, bvec)
+    bval, bv = _host.table_args(bval, bvec)
     nvol = int(bval.shape[0])
     A = np.zeros((nvol, 22), np.float32, order="F")
     pA = np.zeros((22, nvol), np.float32, order="F")
@@ -70,17 +70,15 @@ def dki_fit(dwi: MRI, mask: MRI, odf_dirs: ODF = sphere_642, min_signal: float =
     """Fit the diffusion and kurtosis tensors to multi-shell DWIs and return a `DKI` structure.  mk is the mean of the apparent
     kurtosis over the half sphere of `odf_dirs`.  device: a GPU index, or _lib.DEVICE_ALL for the device set declared with
     fibers_jl_amd.init() (z-slab sharding, as dti_fit)."""
-    bval, bvec = _check_tables(dwi)
-    L = _lib.lib()
-    vol = _dwi_arg(dwi)
+    bval, bvec = _host.check_tables(dwi)
+    vol, m, mdt = _host.fit_inputs(dwi, mask)
     nx, ny, nz, nvol = vol.shape
-    m, mdt = _mask_checked(mask, (nx, ny, nz))
-    v = _verts(odf_dirs)
-    outs = {k: MRI.like(mask if isinstance(mask, MRI) else dwi, _nframes(k)) for k in DKI_FIELDS}
+    v = _host.directions(odf_dirs)
+    outs = dict(zip(DKI_FIELDS, _host.fit_outputs(dwi, mask, [nframes(k) for k in DKI_FIELDS])))
     o = _lib.DkiOut(*[outs[k].vol.ctypes.data for k in DKI_FIELDS])
     p = _params(min_signal, min_diffusivity, min_kurtosis, max_kurtosis)
-    _lib.check(L.fib_dki_fit(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
-                             bval.ctypes.data, bvec.ctypes.data, v.ctypes.data, v.shape[0], C.byref(p), C.byref(o)))
+    _lib.check(_lib.lib().fib_dki_fit(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
+                                      bval.ctypes.data, bvec.ctypes.data, v.ctypes.data, v.shape[0], C.byref(p), C.byref(o)))
     return DKI(**outs)
 
 
@@ -92,9 +90,9 @@ class DkiPlan(Plan):
                  min_diffusivity: float = DEFAULTS["min_diffusivity"], min_kurtosis: float = DEFAULTS["min_kurtosis"],
                  max_kurtosis: float = DEFAULTS["max_kurtosis"], device: int = 0):
         Plan.__init__(self, device)
-        bval, bv = _table_args(bval, bvec)
+        bval, bv = _host.table_args(bval, bvec)
         self.nvol = int(bval.shape[0])
-        v = _verts(odf_dirs)
+        v = _host.directions(odf_dirs)
         self.ndir = odf_dirs.nvert
         p = _params(min_signal, min_diffusivity, min_kurtosis, max_kurtosis)
         _lib.check(_lib.lib().fib_dki_plan_create(device, bval.ctypes.data, bv.ctypes.data, self.nvol, v.ctypes.data, v.shape[0],
@@ -114,14 +112,14 @@ def dki_fit_device(plan: DkiPlan, dwi, mask, out=None, stream=None, kt=True):
     eigenvectors [3, nvox], kt [15, nvox].  `out` without a "kt" entry (or kt=False when the outputs are allocated here) skips
     the kurtosis tensor."""
     import torch
-    nvox = _fit_args(plan, dwi, mask)
+    nvox = fit_args(plan, dwi, mask)
     with Launch(dwi, stream) as L:
         if out is None:
-            out = {k: L.empty((_nframes(k), nvox) if _nframes(k) > 1 else (nvox,), torch.float32) for k in DKI_FIELDS if kt or k != "kt"}
+            out = {k: L.empty((nframes(k), nvox) if nframes(k) > 1 else (nvox,), torch.float32) for k in DKI_FIELDS if kt or k != "kt"}
         else:
             for k in DKI_FIELDS:
                 if k in out:
-                    tensor(out[k], torch.float32, "out[%r]" % k, ref=plan, n=_nframes(k) * nvox)
+                    tensor(out[k], torch.float32, "out[%r]" % k, ref=plan, n=nframes(k) * nvox)
         o = _lib.DkiOut(*[out[k].data_ptr() if k in out else None for k in DKI_FIELDS])
         _lib.check(_lib.lib().fibd_dki_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, C.byref(o), L.sp))
     return out

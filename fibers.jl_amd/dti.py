@@ -8,8 +8,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._dev import Launch, Plan, stream_ptr as _stream_ptr, tensor
+from . import _host, _lib
+from ._dev import Launch, Plan, fit_args, stream_ptr as _stream_ptr, tensor
 from .mri import MRI
 
 DTI_FIELDS = ("s0", "eigval1", "eigval2", "eigval3", "eigvec1", "eigvec2", "eigvec3", "rd", "md", "fa")
@@ -30,91 +30,27 @@ class DTI:
     fa: MRI
 
 
-def _mask_arg(mask):
-    m = mask.vol if isinstance(mask, MRI) else np.asarray(mask)
-    if m.ndim == 4:
-        m = m[..., 0]
-    m = np.asfortranarray(m)
-    name = m.dtype.name
-    if name not in _lib.DTYPES:
-        m = np.asfortranarray(m.astype(np.float64))
-        name = "float64"
-    return m, _lib.DTYPES[name]
-
-
-def _dwi_arg(dwi):
-    if dwi.vol.dtype != np.float32:
-        # the reference's per-voxel methods dispatch on Vector{Float32} (dti.jl:286): other eltypes are a MethodError
-        raise TypeError("dwi.vol must be float32 (the reference dispatches on Float32 only)")
-    return dwi.vol if dwi.vol.flags.f_contiguous else np.asfortranarray(dwi.vol)
-
-
-def _table_args(bval, bvec, need_bvec=True):
-    """A b-table as the C ABI reads it: (bval float32 contiguous [nvol], bvec float32 Fortran-ordered [nvol, 3], or None where
-    the form needs no gradient table).  A gradient table of another row count would be read past its end: ValueError."""
-    bval = np.ascontiguousarray(bval, np.float32).reshape(-1)
-    if not need_bvec:
-        return bval, None
-    bvec = np.asfortranarray(np.asarray(bvec, np.float32).reshape(-1, 3))
-    if bvec.shape[0] != bval.shape[0]:
-        raise ValueError("gradient table must be [%d x 3], got %s" % (bval.shape[0], bvec.shape))
-    return bval, bvec
-
-
-def _check_tables(dwi, need_bvec=True):
-    """The reference's table checks (dti.jl:166-168, 223-229) plus the shapes the C ABI relies on.  Returns
-    (bval float32 contiguous [nframes], bvec float32 Fortran-ordered [nframes, 3] or None): the arrays whose pointers go
-    to the library — `dwi.bvec` itself may have been assigned in any memory order after the MRI was built."""
-    if dwi.bval is None or len(dwi.bval) == 0:
-        raise RuntimeError("Missing b-value table from input DWI structure")        # dti.jl:167,224
-    if need_bvec and (dwi.bvec is None or len(dwi.bvec) == 0):
-        raise RuntimeError("Missing gradient table from input DWI structure")       # dti.jl:228
-    bval = np.ascontiguousarray(dwi.bval, np.float32).reshape(-1)
-    if bval.shape[0] != dwi.nframes:
-        raise ValueError("b-value table length %d does not match %d frames" % (bval.shape[0], dwi.nframes))
-    bvec = None
-    if need_bvec:
-        bvec = np.asarray(dwi.bvec, np.float32)
-        if bvec.shape != (dwi.nframes, 3):
-            raise ValueError("gradient table must be [%d x 3], got %s" % (dwi.nframes, bvec.shape))
-        bvec = np.asfortranarray(bvec)
-    return bval, bvec
-
-
-def _mask_checked(mask, shape3):
-    """_mask_arg + the shape check every host wrapper needs (a mismatch would be an out-of-bounds read in the library)"""
-    m, mdt = _mask_arg(mask)
-    if m.shape != tuple(shape3):
-        raise ValueError("mask shape %s does not match DWI volume %s" % (m.shape, tuple(shape3)))
-    return m, mdt
-
-
 def dti_fit(dwi: MRI, mask: MRI, device: int = 0) -> DTI:
     """Fit tensors to DWIs and return a `DTI` structure (dti.jl:221).  device: a GPU index, or _lib.DEVICE_ALL for the
     device set declared with fibers_jl_amd.init() (z-slab sharding, dti.jl:258)."""
-    bval, bvec = _check_tables(dwi)
-    L = _lib.lib()
-    vol = _dwi_arg(dwi)
+    bval, bvec = _host.check_tables(dwi)
+    vol, m, mdt = _host.fit_inputs(dwi, mask)
     nx, ny, nz, nvol = vol.shape
-    m, mdt = _mask_checked(mask, (nx, ny, nz))
-    outs = {k: MRI.like(mask if isinstance(mask, MRI) else dwi, 3 if "vec" in k else 1) for k in DTI_FIELDS}
+    outs = dict(zip(DTI_FIELDS, _host.fit_outputs(dwi, mask, [3 if "vec" in k else 1 for k in DTI_FIELDS])))
     o = _lib.DtiOut(*[outs[k].vol.ctypes.data for k in DTI_FIELDS])
-    _lib.check(L.fib_dti_fit(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
-                             bval.ctypes.data, bvec.ctypes.data, C.byref(o)))
+    _lib.check(_lib.lib().fib_dti_fit(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
+                                      bval.ctypes.data, bvec.ctypes.data, C.byref(o)))
     return DTI(**outs)
 
 
 def adc_fit(dwi: MRI, mask: MRI, device: int = 0):
     """Fit the apparent diffusion coefficient; returns (adc, s0) (dti.jl:164)."""
-    bval, _ = _check_tables(dwi, need_bvec=False)
-    L = _lib.lib()
-    vol = _dwi_arg(dwi)
+    bval, _ = _host.check_tables(dwi, need_bvec=False)
+    vol, m, mdt = _host.fit_inputs(dwi, mask)
     nx, ny, nz, nvol = vol.shape
-    m, mdt = _mask_checked(mask, (nx, ny, nz))
-    ref = mask if isinstance(mask, MRI) else dwi
-    adc, s0 = MRI.like(ref, 1), MRI.like(ref, 1)
-    _lib.check(L.fib_adc_fit(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
-                             bval.ctypes.data, adc.vol.ctypes.data, s0.vol.ctypes.data))
+    adc, s0 = _host.fit_outputs(dwi, mask, [1, 1])
+    _lib.check(_lib.lib().fib_adc_fit(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
+                                      bval.ctypes.data, adc.vol.ctypes.data, s0.vol.ctypes.data))
     return adc, s0
 
 
@@ -127,7 +63,7 @@ class DtiPlan(Plan):
 
     def __init__(self, bval, bvec=None, device: int = 0):
         Plan.__init__(self, device)
-        bval, bv = _table_args(bval, bvec, need_bvec=bvec is not None)
+        bval, bv = _host.table_args(bval, bvec, need_bvec=bvec is not None)
         self.nvol = int(bval.shape[0])
         _lib.check(_lib.lib().fib_dti_plan_create(device, bval.ctypes.data, None if bv is None else bv.ctypes.data,
                                                   self.nvol, C.byref(self._h)))
@@ -146,19 +82,11 @@ class DtiPlan(Plan):
         return int(c.value)
 
 
-def _fit_args(plan, dwi, mask):
-    """the inputs of a plan's fit: dwi float32 [plan.nvol, nvox], mask uint8 [nvox], both on the plan's device -> nvox"""
-    import torch
-    nvox = tensor(mask, torch.uint8, "mask", ref=plan).numel()
-    tensor(dwi, torch.float32, "dwi [nvol, nvox]", ref=plan, n=nvox * plan.nvol)
-    return nvox
-
-
 def dti_fit_device(plan: DtiPlan, dwi, mask, out=None, stream=None):
     """dwi: float32 CUDA tensor [nvol, nvox] (planar: frame slowest == MRI.vol memory order);
     mask: uint8 CUDA tensor [nvox].  Returns dict of tensors: scalars [nvox], eigvecs [3, nvox] (`out`: such a dict to write into)."""
     import torch
-    nvox = _fit_args(plan, dwi, mask)
+    nvox = fit_args(plan, dwi, mask)
     with Launch(dwi, stream) as L:
         if out is None:
             out = {k: L.empty((3, nvox) if "vec" in k else (nvox,), torch.float32) for k in DTI_FIELDS}
@@ -172,7 +100,7 @@ def dti_fit_device(plan: DtiPlan, dwi, mask, out=None, stream=None):
 
 def adc_fit_device(plan: DtiPlan, dwi, mask, stream=None):
     import torch
-    nvox = _fit_args(plan, dwi, mask)
+    nvox = fit_args(plan, dwi, mask)
     with Launch(dwi, stream) as L:
         adc, s0 = L.empty(nvox, torch.float32), L.empty(nvox, torch.float32)
         _lib.check(_lib.lib().fibd_adc_fit(plan._h, dwi.data_ptr(), mask.data_ptr(), nvox, adc.data_ptr(), s0.data_ptr(), L.sp))

@@ -6,9 +6,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _lib
-from ._dev import ArgError, Launch, Plan, stream_ptr, tensor
-from .dti import _check_tables, _table_args, _dwi_arg, _fit_args, _mask_arg, _mask_checked
+from . import _host, _lib
+from ._dev import ArgError, Launch, Plan, fit_args, stream_ptr, tensor
 from .mri import MRI
 from .odf import ODF, sphere_642
 
@@ -30,65 +29,53 @@ class DSI:
     qa: List[MRI]
 
 
-def _odf_args(odf_dirs: ODF):
-    v = np.asfortranarray(odf_dirs.vertices, dtype=np.float32)
-    f = np.asfortranarray(odf_dirs.faces, dtype=np.int32)
-    return v, f
-
-
-def _p3(arrs):
-    return _lib.P3(*[a.vol.ctypes.data if isinstance(a, MRI) else a for a in arrs])
-
-
 def gqi_rec(dwi: MRI, mask: MRI, odf_dirs: ODF = sphere_642, sigma: float = 1.25, device: int = 0) -> GQI:
     """Generalized q-sampling imaging reconstruction (gqi.jl:109)."""
-    bval, bvec = _check_tables(dwi)
-    vol = _dwi_arg(dwi)
+    bval, bvec = _host.check_tables(dwi)
+    vol, m, mdt = _host.fit_inputs(dwi, mask)
     nx, ny, nz, nvol = vol.shape
-    m, mdt = _mask_checked(mask, (nx, ny, nz))
-    v, f = _odf_args(odf_dirs)
-    ref = mask if isinstance(mask, MRI) else dwi
-    odf = MRI.like(ref, odf_dirs.nvert)
-    peak = [MRI.like(ref, 3) for _ in range(3)]
-    qa = [MRI.like(ref, 1) for _ in range(3)]
+    v, f = _host.directions(odf_dirs, faces=True)
+    odf, *pq = _host.fit_outputs(dwi, mask, [odf_dirs.nvert, 3, 3, 3, 1, 1, 1])
+    peak, qa = pq[:3], pq[3:]
     _lib.check(_lib.lib().fib_gqi_rec(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
                                       bval.ctypes.data, bvec.ctypes.data,
                                       v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], float(sigma),
-                                      odf.vol.ctypes.data, _p3(peak), _p3(qa)))
+                                      odf.vol.ctypes.data, _host.pointers(peak), _host.pointers(qa)))
     return GQI(odf, peak, qa)
 
 
 def dsi_rec(dwi: MRI, mask: MRI, odf_dirs: ODF = sphere_642, hann_width: int = 32, device: int = 0) -> DSI:
     """Diffusion spectrum imaging reconstruction (dsi.jl:171)."""
-    bval, bvec = _check_tables(dwi)
-    vol = _dwi_arg(dwi)
+    bval, bvec = _host.check_tables(dwi)
+    vol, m, mdt = _host.fit_inputs(dwi, mask)
     nx, ny, nz, nvol = vol.shape
-    m, mdt = _mask_checked(mask, (nx, ny, nz))
-    v, f = _odf_args(odf_dirs)
-    ref = mask if isinstance(mask, MRI) else dwi
-    pdf = MRI.like(ref, nvol)
-    odf = MRI.like(ref, odf_dirs.nvert)
-    peak = [MRI.like(ref, 3) for _ in range(3)]
-    qa = [MRI.like(ref, 1) for _ in range(3)]
+    v, f = _host.directions(odf_dirs, faces=True)
+    pdf, odf, *pq = _host.fit_outputs(dwi, mask, [nvol, odf_dirs.nvert, 3, 3, 3, 1, 1, 1])
+    peak, qa = pq[:3], pq[3:]
     _lib.check(_lib.lib().fib_dsi_rec(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt | _lib.FIB_MASK_OUTPUTS_ZEROED,
                                       bval.ctypes.data, bvec.ctypes.data,
                                       v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], int(hann_width),
-                                      pdf.vol.ctypes.data, odf.vol.ctypes.data, _p3(peak), _p3(qa)))
+                                      pdf.vol.ctypes.data, odf.vol.ctypes.data, _host.pointers(peak), _host.pointers(qa)))
     return DSI(pdf, odf, peak, qa)
 
 
-def find_peaks(odf, odf_dirs: ODF = sphere_642, device: int = 0):
-    """find_peaks!(W) (gqi.jl:180-201) on host ODFs.  odf: [..., nvert] amplitudes on the half sphere (any leading
-    shape, e.g. `GQI.odf.vol`); returns (isort_top int32 [..., 3]: the first three entries of `isort`, 0-based
-    first-half vertex rows, -1 beyond the tessellation; nvalid int32 [...] = count(odf_peak .> 0))."""
+def _planar_odf(odf, odf_dirs):
+    """the front end of the two peak finders: odf [..., nvert] -> (its leading shape, nvox, planar float32 [nvert, nvox], the
+    tessellation's vertices and faces)"""
     o = np.asarray(odf, dtype=np.float32)
     nvert = odf_dirs.nvert
     if o.shape[-1] != nvert:
         raise ValueError("last axis of odf must be the %d half-sphere vertices" % nvert)
     lead = o.shape[:-1]
     nvox = int(np.prod(lead)) if lead else 1
-    planar = np.ascontiguousarray(o.reshape(nvox, nvert).T)             # [nvert, nvox]
-    v, f = _odf_args(odf_dirs)
+    return (lead, nvox, np.ascontiguousarray(o.reshape(nvox, nvert).T)) + _host.directions(odf_dirs, faces=True)
+
+
+def find_peaks(odf, odf_dirs: ODF = sphere_642, device: int = 0):
+    """find_peaks!(W) (gqi.jl:180-201) on host ODFs.  odf: [..., nvert] amplitudes on the half sphere (any leading
+    shape, e.g. `GQI.odf.vol`); returns (isort_top int32 [..., 3]: the first three entries of `isort`, 0-based
+    first-half vertex rows, -1 beyond the tessellation; nvalid int32 [...] = count(odf_peak .> 0))."""
+    lead, nvox, planar, v, f = _planar_odf(odf, odf_dirs)
     top = np.empty((3, nvox), np.int32)
     nvalid = np.empty(nvox, np.int32)
     _lib.check(_lib.lib().fib_find_peaks(device, planar.ctypes.data, nvox, v.ctypes.data, v.shape[0], f.ctypes.data,
@@ -100,14 +87,8 @@ def find_peaks_work(odf, odf_dirs: ODF = sphere_642, device: int = 0):
     """find_peaks!(W) (gqi.jl:180-201) with every output the reference's work struct receives.  odf: [..., nvert]; returns
     (odf_peak float32 [..., nvert]: W.odf_peak, the amplitudes of the local peaks and 0 elsewhere; isort int32 [..., nvert]:
     W.isort = sortperm(odf_peak, rev=true), 0-based; nvalid int32 [...]: the function's return value)."""
-    o = np.asarray(odf, dtype=np.float32)
+    lead, nvox, planar, v, f = _planar_odf(odf, odf_dirs)
     nvert = odf_dirs.nvert
-    if o.shape[-1] != nvert:
-        raise ValueError("last axis of odf must be the %d half-sphere vertices" % nvert)
-    lead = o.shape[:-1]
-    nvox = int(np.prod(lead)) if lead else 1
-    planar = np.ascontiguousarray(o.reshape(nvox, nvert).T)             # [nvert, nvox]
-    v, f = _odf_args(odf_dirs)
     pk = np.empty((nvert, nvox), np.float32)
     isort = np.empty((nvert, nvox), np.int32)
     nvalid = np.empty(nvox, np.int32)
@@ -135,8 +116,8 @@ class OdfPlan(Plan):
         fmt = ODF_FORMATS[format]
         Plan.__init__(self, device)
         self.kind = kind
-        bval, bvec = _table_args(bval, bvec)
-        v, f = _odf_args(odf_dirs)
+        bval, bvec = _host.table_args(bval, bvec)
+        v, f = _host.directions(odf_dirs, faces=True)
         L = _lib.lib()
         self.nvol, self.nvert = int(bval.shape[0]), odf_dirs.nvert
         if kind == "gqi":
@@ -181,7 +162,7 @@ def odf_rec_device(plan: OdfPlan, dwi, mask, out: Optional[dict] = None, normali
     voxel count is not a multiple of 4 (such a piece cannot run the fused peak scan, and the two forms differ at rounding level).
     raw_odfmax = FIB_ODF_RAW_ODFMAX: odfmax = {maximum of the means that are not NaN, NaN flag}, the form a MAX all-reduce takes."""
     import torch
-    nvox = _fit_args(plan, dwi, mask)
+    nvox = fit_args(plan, dwi, mask)
     dsi = plan.kind == "dsi"
     with Launch(dwi, stream) as L:
         if out is None:

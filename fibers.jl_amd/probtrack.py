@@ -12,11 +12,11 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, Plan, tensor, work as _work
 from .mri import MRI
 from .odf import ODF, sphere_642
-from .stream import StreamBuffers, _buffers_on, _vol3, cosd32, make_sublist
+from .stream import StreamBuffers, buffers_on, cosd32, make_sublist
 from .tract import Tract
 
 
@@ -35,11 +35,6 @@ def prob_work_size(nlines: int) -> int:
     return int(n.value)
 
 
-def _half(odf_dirs):
-    v = odf_dirs.vertices[: odf_dirs.nvert] if isinstance(odf_dirs, ODF) else np.asarray(odf_dirs)
-    return np.ascontiguousarray(v, np.float32).reshape(-1, 3)
-
-
 class ProbPlan(Plan):
     """The directions U (the first half of `odf_dirs`' vertices, or a float32 [nvert, 3] array) and the cone's bit tables for
     `ang_thresh` degrees (below 90), resident on one GPU.  cosang_thresh, if given, is taken as it is instead of cosd(ang_thresh)."""
@@ -47,7 +42,7 @@ class ProbPlan(Plan):
 
     def __init__(self, odf_dirs=sphere_642, ang_thresh: float = 45, device: int = 0, cosang_thresh: Optional[float] = None):
         Plan.__init__(self, int(device))
-        U = _half(odf_dirs)
+        U = _host.directions(odf_dirs, half=True)
         self.nvert, self.pitch = U.shape[0], prob_row_pitch(U.shape[0])
         self.cosang_thresh = float(cosd32(ang_thresh) if cosang_thresh is None else np.float32(cosang_thresh))
         _lib.check(_lib.lib().fib_prob_plan_create(self.device, U.ctypes.data, self.nvert, self.cosang_thresh, C.byref(self._h)))
@@ -91,7 +86,7 @@ def prob_stream_device(plan: ProbPlan, table, shape, seeds, sublist, len_min=3, 
         w, wb = _work(L, work, prob_work_size, "fibd_prob_work_size(nseed * nsub)", nl_max)
         if buffers is None:
             buffers = StreamBuffers(table.device)
-        _buffers_on(buffers, table)
+        buffers_on(buffers, table)
         if buffers.npts is None or buffers.npts.numel() == 0:
             buffers.reserve(nl_max, 32 * nl_max)                    # a first guess; the call below says what is needed
         for attempt in range(2):
@@ -118,20 +113,14 @@ def prob_stream(odf, odf_dirs: ODF = sphere_642, *, mask: Optional[MRI] = None, 
     half-angle of the cone the next direction is drawn from; amplitudes below pmf_thresh of a voxel's maximum (after subtract_min)
     are never drawn.  The same arguments and rng_seed give the same bytes."""
     o = getattr(odf, "odf", odf)
-    vol = o.vol if isinstance(o, MRI) else np.asarray(o)
-    U = _half(odf_dirs)
+    vol = _host.volume(o, dtype=np.float32, series=True)
+    U = _host.directions(odf_dirs, half=True)
     if vol.ndim != 4 or vol.shape[3] != U.shape[0]:
         raise ValueError("odf must be [nx, ny, nz, %d] (one frame per direction), not %s" % (U.shape[0], vol.shape))
-    vol = np.asfortranarray(vol, dtype=np.float32)
     shape = vol.shape[:3]
 
     def bytes_of(m, what):
-        if m is None:
-            return None
-        a = _vol3(m, what)
-        if a.shape != shape:
-            raise ValueError("%s shape %s does not match the ODF volume %s" % (what, a.shape, shape))
-        return np.asfortranarray(a > 0, dtype=np.uint8)
+        return None if m is None else _host.mask(m, shape, "> 0", refuse=what + " shape %s does not match the ODF volume %s")[0]
 
     m8, s8 = bytes_of(mask, "mask"), bytes_of(seed, "seed")
     sub = make_sublist(nsub, rng) if sublist is None else np.ascontiguousarray(sublist, np.float32).reshape(-1, 3)
@@ -142,13 +131,7 @@ def prob_stream(odf, odf_dirs: ODF = sphere_642, *, mask: Optional[MRI] = None, 
                                  int(len_min), int(len_max if len_max is not None else max(shape)), float(cosd32(ang_thresh)),
                                  float(np.float32(step_size)), float(np.float32(pmf_thresh)), int(bool(subtract_min)),
                                  int(rng_seed) & (2 ** 64 - 1), C.byref(out)))
-    try:
-        nl, npnt = int(out.nlines), int(out.npoints)
-        npts = np.ctypeslib.as_array(out.npts, shape=(max(nl, 1),))[:nl].copy()
-        sidx = np.ctypeslib.as_array(out.seed_index, shape=(max(nl, 1),))[:nl].copy()
-        xyz = np.ctypeslib.as_array(out.xyz, shape=(max(npnt, 1) * 3,))[: npnt * 3].copy().reshape(-1, 3)
-    finally:
-        L.fib_tract_free(C.byref(out))
+    npts, sidx, xyz, _ = _host.tract_arrays(out)
     ref = next((x for x in (mask, o) if isinstance(x, MRI)), None)
     return Tract(xyz=xyz, npts=npts, seed_index=sidx, volsize=shape,
                  volres=tuple(ref.volres) if ref is not None else (1.0, 1.0, 1.0),

@@ -5,9 +5,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, Plan, tensor
-from .dti import _check_tables, _table_args, _dwi_arg, _mask_checked
 from .mri import MRI
 from .odf import ODF, sphere_724
 
@@ -37,19 +36,16 @@ def rumba_rec(dwi: MRI, mask: MRI, odf_dirs: ODF = sphere_724, niter: int = 600,
               lam_perp: float = 0.2e-3, lam_csf: float = 3.0e-3, lam_gm: float = 0.8e-4, ncoils: int = 1,
               coil_combine: str = "SMF-SENSE", ipat_factor: int = 1, use_tv: bool = True, device: int = 0) -> RUMBASD:
     """Robust and unbiased model-based spherical deconvolution (rusd.jl:419)."""
-    bval, bvec = _check_tables(dwi)
+    bval, bvec = _host.check_tables(dwi)
     sos = _coil_mode(coil_combine)
     if ipat_factor < 1:
         raise ValueError("iPAT factor must be a positive integer")             # rusd.jl:437
-    vol = _dwi_arg(dwi)
+    vol, m, mdt = _host.fit_inputs(dwi, mask)
     nx, ny, nz, nvol = vol.shape
-    m, mdt = _mask_checked(mask, vol.shape[:3])
-    v = np.asfortranarray(odf_dirs.vertices, dtype=np.float32)
-    ref = mask if isinstance(mask, MRI) else dwi
-    fodf = MRI.like(ref, odf_dirs.nvert)
-    sc = [MRI.like(ref, 1) for _ in range(4)]
-    peak = [MRI.like(ref, 3) for _ in range(5)]
-    out = _lib.RumbaOut(fodf.vol.ctypes.data, *[s.vol.ctypes.data for s in sc], (C.c_void_p * 5)(*[p.vol.ctypes.data for p in peak]))
+    v = _host.directions(odf_dirs)
+    fodf, *rest = _host.fit_outputs(dwi, mask, [odf_dirs.nvert] + [1] * 4 + [3] * 5)
+    sc, peak = rest[:4], rest[4:]
+    out = _lib.RumbaOut(fodf.vol.ctypes.data, *[s.vol.ctypes.data for s in sc], _host.pointers(peak))
     sm, ss = C.c_float(0), C.c_float(0)
     _lib.check(_lib.lib().fib_rumba_rec(device, vol.ctypes.data, nx, ny, nz, nvol, m.ctypes.data, mdt,
                                         bval.ctypes.data, bvec.ctypes.data, v.ctypes.data, v.shape[0], int(niter),
@@ -65,8 +61,8 @@ class RumbaPlan(Plan):
     def __init__(self, bval, bvec, odf_dirs: ODF = sphere_724, lam_para=1.7e-3, lam_perp=0.2e-3, lam_csf=3.0e-3,
                  lam_gm=0.8e-4, device: int = 0):
         Plan.__init__(self, device)
-        bval, bvec = _table_args(bval, bvec)
-        v = np.asfortranarray(odf_dirs.vertices, dtype=np.float32)
+        bval, bvec = _host.table_args(bval, bvec)
+        v = _host.directions(odf_dirs)
         self.nvert, self.nvol = odf_dirs.nvert, int(bval.shape[0])
         _lib.check(_lib.lib().fib_rumba_plan_create(device, bval.ctypes.data, bvec.ctypes.data, self.nvol, v.ctypes.data,
                                                     v.shape[0], float(lam_para), float(lam_perp), float(lam_csf),

@@ -6,9 +6,8 @@ from typing import List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, sync as _sync, tensor
-from .dti import _mask_arg
 from .mri import MRI
 from .tract import Tract
 
@@ -69,21 +68,6 @@ def make_sublist(nsub: int, rng=None) -> np.ndarray:
     return rng.uniform(-0.5 + _EPS, 0.5 - _EPS, size=(nsub, 3)).astype(np.float32)
 
 
-def _as_list(x):
-    if x is None:
-        return None
-    return [x] if isinstance(x, (MRI, np.ndarray)) else list(x)
-
-
-def _vol3(m, what):
-    a = m.vol if isinstance(m, MRI) else np.asarray(m)
-    if a.ndim == 4:
-        a = a[..., 0]
-    if a.ndim != 3:
-        raise ValueError("%s must be a 3-D volume" % what)
-    return a
-
-
 class StreamWorkspace:
     """Caller-owned scratch arena of the tracer on one device (fibd_stream_ws_create): keeps the multi-GB point scratch
     between calls.  One job at a time takes it; concurrent jobs fall back to their own allocation."""
@@ -131,10 +115,11 @@ def _interp_code(interp, integrator):
     return _INTEGRATORS[integrator]
 
 
-def _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist=0, search_ang=10, ws=None, interp="nearest",
-            search_flat_axis=0, integrator="euler"):
-    """search_dist > 0 selects the microscopy regime (stream.jl:83, 547-619); interp: "nearest" (the reference) or "trilinear",
-    integrator: "euler", or "rk2" / "rk4" on the trilinear field (fib_stream_params.interp in include/fibers_hip.h);
+def params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist=0, search_ang=10, ws=None, interp="nearest",
+           search_flat_axis=0, integrator="euler"):
+    """The fib_stream_params of a tracer call on a volume of `shape` with `nvec` vectors per voxel (len_max None: the largest extent;
+    ws: a StreamWorkspace or None).  search_dist > 0 selects the microscopy regime (stream.jl:83, 547-619); interp: "nearest" (the
+    reference) or "trilinear", integrator: "euler", or "rk2" / "rk4" on the trilinear field (fib_stream_params.interp in include/fibers_hip.h);
     search_flat_axis 1..3: that axis is searched over one voxel only (the through-plane axis of 2-D angle inputs, stream.jl:153-155)"""
     code = _interp_code(interp, integrator)
     nx, ny, nz = shape
@@ -142,6 +127,9 @@ def _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff, 
                              float(cosd32(ang_thresh)), float(np.float32(step_size)), float(np.float32(smooth_coeff)),
                              int(search_dist), float(cosd32(search_ang)), ws._h if ws is not None else None, code,
                              int(search_flat_axis))
+
+
+_params = params        # the name the GPU tests written before the rename reach through the module (smod._params)
 
 
 def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, fa: Optional[MRI] = None,
@@ -158,8 +146,8 @@ def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, f
     `lcms` [nx,ny,nz,10] switches to LCM-guided tracking (stream.jl:380-495); the reference samples from Julia's global
     RNG there, this back end from the counter-based stream defined in include/fibers_hip.h (`rng_seed`); the returned
     Tract then carries the per-point method-difference indicator as `scalars`."""
-    ovecs = _as_list(ovec)
-    fs = _as_list(f)
+    ovecs = _host.as_list(ovec)
+    fs = None if f is None else _host.as_list(f)
     if mask is None:
         raise ValueError("mask is required (the reference builds the Tract header from it, stream.jl:784)")
     vols = []
@@ -175,6 +163,10 @@ def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, f
         else:
             raise ValueError("Input orientations should be 3D vectors or angles in [-90, 90]")
     shape = vols[0].shape[:3]
+    for k, v in enumerate(vols):                                # every volume below is read as nx * ny * nz voxels
+        if v.shape[:3] != shape:
+            raise ValueError("ovec[%d] shape %s does not match the orientation volume %s of ovec[0]" % (k, v.shape[:3], shape))
+    m, mdt = _host.mask(mask, shape, refuse="mask shape %s does not match orientation volume %s")
     # Is this in the microscopy regime (min voxel size under 50 um)?  (stream.jl:83)
     domicro = min(ovecs[0].volres if isinstance(ovecs[0], MRI) else (1, 1, 1)) <= 0.05
     # scale-dependent defaults when `nothing` is passed (stream.jl:89-92)
@@ -187,32 +179,26 @@ def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, f
     if fs is not None:
         if len(fs) != nvec:
             raise ValueError("need one amplitude volume per orientation volume")
-        fvols = [np.asfortranarray(_vol3(x, "f"), dtype=np.float32) for x in fs]
-        _warn_thresh("f_thresh", f_thresh, fvols[0], _vol3(mask, "mask") > 0)           # stream.jl:121-127
+        fvols = [_host.volume(x, shape, np.float32, frame0=True, refuse="f[%d]" % k + " shape %s does not match the orientation volume %s")
+                 for k, x in enumerate(fs)]
+        _warn_thresh("f_thresh", f_thresh, fvols[0], m > 0)                             # stream.jl:121-127
     favol = None
     if fa is not None:
-        favol = np.asfortranarray(_vol3(fa, "fa"), dtype=np.float32)
-        _warn_thresh("fa_thresh", fa_thresh, favol, _vol3(mask, "mask") > 0)            # stream.jl:107-113
-    m, mdt = _mask_arg(mask)
-    if m.shape != shape:
-        raise ValueError("mask shape %s does not match orientation volume %s" % (m.shape, shape))
+        favol = _host.volume(fa, shape, np.float32, frame0=True, refuse="fa shape %s does not match the orientation volume %s")
+        _warn_thresh("fa_thresh", fa_thresh, favol, m > 0)                              # stream.jl:107-113
     sptr, sdt = None, 0
     if seed is not None:
-        sv = _vol3(seed, "seed")
-        if sv.shape != m.shape:
-            raise RuntimeError("Dimension mismatch between seed mask %s and brain mask %s"
-                               % (sv.shape, m.shape))                                 # stream.jl:746-749
-        sarr, sdt = _mask_arg(seed)
+        sarr, sdt = _host.mask(seed, shape, refuse="Dimension mismatch between seed mask %s and brain mask %s",
+                               error=RuntimeError)                                    # stream.jl:746-749
         sptr = sarr.ctypes.data
     sub = make_sublist(nsub, rng) if sublist is None else np.ascontiguousarray(sublist, np.float32).reshape(-1, 3)
-    prm = _params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff,
-                  int(search_dist) if domicro else 0, search_ang, interp=interp, integrator=integrator,
-                  search_flat_axis=flat_axis if domicro else 0)                 # micro_search_dist[thrudim] = 0 (stream.jl:153-155)
-    ov = (C.c_void_p * nvec)(*[v.ctypes.data for v in vols])
-    fv = None if fvols is None else (C.c_void_p * nvec)(*[v.ctypes.data for v in fvols])
+    prm = params(shape, nvec, len_min, len_max, ang_thresh, step_size, smooth_coeff,
+                 int(search_dist) if domicro else 0, search_ang, interp=interp, integrator=integrator,
+                 search_flat_axis=flat_axis if domicro else 0)                  # micro_search_dist[thrudim] = 0 (stream.jl:153-155)
+    ov = _host.pointers(vols)
+    fv = None if fvols is None else _host.pointers(fvols)
     out = _lib.TractOut()
     L = _lib.lib()
-    scal = None
     if lcms is None:
         _lib.check(L.fib_stream(device, C.byref(prm), ov, fv, float(np.float32(f_thresh)),
                                 None if favol is None else favol.ctypes.data, float(np.float32(fa_thresh)),
@@ -226,10 +212,9 @@ def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, f
             # the through-plane dimension is the third
             raise ValueError("LCM-guided tracking on 2-D angle inputs needs the through-plane dimension to be the third "
                              "(largest voxel size along z): the reference pairs the LCM edges with dimensions (1, 2) there")
-        lv = lcms.vol if isinstance(lcms, MRI) else np.asarray(lcms)
+        lv = _host.volume(lcms, dtype=np.float32, series=True)
         if lv.shape != shape + (10,):
             raise ValueError("lcms must be [nx,ny,nz,10] (vectorised 4x4 symmetric local connection matrices)")
-        lv = np.asfortranarray(lv, dtype=np.float32)
         if lcm_thresh > float(lv.max()):                                      # stream.jl:210-215
             print("WARNING: The value of lcm_thresh (%s) is greater than the maximum value in the lcms volume (%s)"
                   % (lcm_thresh, float(lv.max())))
@@ -237,15 +222,7 @@ def stream(ovec: Union[MRI, Sequence[MRI]], *, f=None, f_thresh: float = 0.03, f
                                     None if favol is None else favol.ctypes.data, float(np.float32(fa_thresh)),
                                     m.ctypes.data, mdt, sptr, sdt, sub.ctypes.data, sub.shape[0],
                                     lv.ctypes.data, float(np.float32(lcm_thresh)), int(rng_seed), C.byref(out)))
-    try:
-        nl, npnt = int(out.nlines), int(out.npoints)
-        npts = np.ctypeslib.as_array(out.npts, shape=(max(nl, 1),))[:nl].copy()
-        sidx = np.ctypeslib.as_array(out.seed_index, shape=(max(nl, 1),))[:nl].copy()
-        xyz = np.ctypeslib.as_array(out.xyz, shape=(max(npnt, 1) * 3,))[: npnt * 3].copy().reshape(-1, 3)
-        if lcms is not None:
-            scal = np.ctypeslib.as_array(out.flags, shape=(max(npnt, 1),))[:npnt].astype(np.float32)
-    finally:
-        L.fib_tract_free(C.byref(out))
+    npts, sidx, xyz, scal = _host.tract_arrays(out, flags=lcms is not None)
     ref = mask if isinstance(mask, MRI) else None
     return Tract(xyz=xyz, npts=npts, seed_index=sidx, volsize=shape,
                  volres=tuple(ref.volres) if ref is not None else (1.0, 1.0, 1.0),
@@ -314,9 +291,9 @@ def stream_field_device(ovec: List, f: Optional[List] = None, f_thresh: float = 
     return field, mout
 
 
-def _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
-                   search_dist=0, search_ang=10, integrator="euler"):
-    """the preamble of the device-resident tracer calls: checks field / seeds / sublist, resolves `workspace` ("default": the host
+def device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                  search_dist=0, search_ang=10, integrator="euler"):
+    """The preamble of the device-resident tracer calls: checks field / seeds / sublist, resolves `workspace` ("default": the host
     mirror's arena for the field's device) and returns the fib_stream_params"""
     import torch
     nx, ny, nz = (int(v) for v in shape)
@@ -324,8 +301,8 @@ def _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, an
     tensor(seeds, torch.int64, "seeds", ref=field)
     tensor(sublist, torch.float32, "sublist", ref=field, shape=(None, 3))
     ws = default_workspace(field.device.index or 0) if isinstance(workspace, str) else workspace
-    return _params(shape, field.shape[1], len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist, search_ang, ws, interp,
-                   integrator=integrator)
+    return params(shape, field.shape[1], len_min, len_max, ang_thresh, step_size, smooth_coeff, search_dist, search_ang, ws, interp,
+                  integrator=integrator)
 
 
 def stream_device(field, shape, seeds, sublist, len_min=3, len_max=None, ang_thresh=45, step_size=0.5,
@@ -342,8 +319,8 @@ def stream_device(field, shape, seeds, sublist, len_min=3, len_max=None, ang_thr
     host mirror's arena for the field's device).  interp="trilinear": the non-reference option of fib_stream_params.interp.
     Returns dict(npts int32 [nlines], seed_index int64 [nlines], xyz float32 [npoints, 3])."""
     import torch
-    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
-                         search_dist, search_ang, integrator=integrator)
+    prm = device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                        search_dist, search_ang, integrator=integrator)
     if lcms is not None:
         tensor(lcms, torch.float32, "lcms [10, nvox]", ref=field, n=10 * field.shape[0])
     job = C.c_void_p()
@@ -399,8 +376,9 @@ class StreamBuffers:
             self.xyz = torch.empty((int(points), 3), dtype=torch.float32, device=self.device)
 
 
-def _buffers_on(buffers, field):
-    """a caller's StreamBuffers live on the field's device (they are made by `reserve`, which sizes the three alike)"""
+def buffers_on(buffers, field):
+    """Refuses a caller's StreamBuffers that are not on the device of `field` (the tracer's field, or prob_stream_device's table): a
+    caller's StreamBuffers live on the field's device (they are made by `reserve`, which sizes the three alike)"""
     if buffers.npts is not None and buffers.npts.device != field.device:
         raise ArgError("buffers are on %s, the field on %s" % (buffers.npts.device, field.device))
 
@@ -412,14 +390,14 @@ def stream_device_run(field, shape, seeds, sublist, buffers: StreamBuffers = Non
     behind a decoupled look-back; results go straight into `buffers` (grown and the call repeated when they are too small: a first
     call sizes them).  Same lines, order and layout as stream_device; macro-scale angle picking only.
     Returns dict(npts, seed_index, xyz) -- views of the buffers, valid until the next call with them."""
-    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
-                         integrator=integrator)
+    prm = device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                        integrator=integrator)
     nl_max = int(seeds.numel()) * int(sublist.shape[0])
     nl, npnt = C.c_int64(0), C.c_int64(0)
     with Launch(field, stream) as L:
         if buffers is None:
             buffers = StreamBuffers(field.device)
-        _buffers_on(buffers, field)
+        buffers_on(buffers, field)
         if buffers.npts is None or buffers.npts.numel() == 0:
             buffers.reserve(nl_max, 32 * nl_max)                    # a first guess; the call below says what is needed
         for attempt in range(2):
@@ -441,11 +419,11 @@ def stream_device_run_enqueue(field, shape, seeds, sublist, buffers: StreamBuffe
     None) receives {lines, points} from the stream -- read it after synchronising; values above the buffers' capacities mean that
     lines were dropped for lack of room.  Returns (buffers, counts)."""
     import torch
-    prm = _device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
-                         integrator=integrator)
+    prm = device_params(field, shape, seeds, sublist, workspace, len_min, len_max, ang_thresh, step_size, smooth_coeff, interp,
+                        integrator=integrator)
     if buffers is None or buffers.npts is None or buffers.npts.numel() == 0:
         raise ValueError("stream_device_run_enqueue needs sized buffers (call stream_device_run once)")
-    _buffers_on(buffers, field)
+    buffers_on(buffers, field)
     with Launch(field, stream) as L:
         counts = torch.zeros(2, dtype=torch.int64, device=field.device) if counts is None else tensor(counts, torch.int64, "counts", ref=field, n=2)
         _lib.check(_lib.lib().fibd_stream_run_enqueue(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sublist.data_ptr(),

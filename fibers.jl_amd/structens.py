@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, tensor, work as _work
 
 
@@ -22,7 +22,7 @@ def st_eigen(Sxx, Sxy, Sxz, Syy, Syz, Szz, device=0):
     nvox = int(np.prod(shape))
     eigvec = np.empty(shape + (3, 3), np.float32, order="F")
     eigval = np.empty(shape + (3,), np.float32, order="F")
-    ptrs = (C.c_void_p * 6)(*[v.ctypes.data for v in vols])
+    ptrs = _host.pointers(vols)
     _lib.check(_lib.lib().fib_st_eigen(int(device), ptrs, nvox, eigvec.ctypes.data, eigval.ctypes.data))
     return eigvec, eigval
 

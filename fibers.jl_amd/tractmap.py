@@ -12,7 +12,8 @@ from typing import Sequence, Union
 import numpy as np
 
 from . import _lib
-from ._dev import ArgError, Launch, float3, packed as _packed, tensor, work as _work
+from ._dev import Launch, float3, lines as _lines, points as _points, tensor, work as _work
+from ._host import packed as _packed
 from .mri import MRI
 from .tract import Tract
 
@@ -106,20 +107,6 @@ def str_work_size(nlines: int) -> int:
     b = C.c_uint64(0)
     _lib.check(_lib.lib().fibd_str_work_size(int(nlines), C.byref(b)))
     return int(b.value)
-
-
-def _points(xyz, what="xyz", ref=None):
-    """float32 [npoints, 3] (on the device of `ref`) -> npoints"""
-    import torch
-    if tensor(xyz, torch.float32, what, ref=ref).numel() % 3:
-        raise ArgError("%s must hold whole points [npoints, 3], not %d coordinates" % (what, xyz.numel()))
-    return xyz.numel() // 3
-
-
-def _lines(xyz, npts):
-    """the checks every tract tool starts with: xyz float32 [npoints, 3], npts int32 [nlines] on its device -> (npoints, nlines)"""
-    import torch
-    return _points(xyz), tensor(npts, torch.int32, "npts", ref=xyz).numel()
 
 
 def str_density_device(xyz, npts, shape, mode: str = "lines", out=None, n_outside=None, work=None, stream=None):

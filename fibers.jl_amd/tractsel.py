@@ -12,30 +12,13 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
-from .mri import MRI
+from . import _host, _lib
 from .tract import Tract
-from ._dev import ArgError, Launch, float3, packed as _packed, tensor, work as _work
-from .tractmap import _lines, _points
+from ._dev import ArgError, Launch, float3, lines as _lines, points as _points, tensor, work as _work
+from ._host import packed as _packed
 
 
-def _volume(v, shape, dtype, what):
-    """an MRI or an array with the tract's volume size -> contiguous [nvox] of `dtype`, x fastest"""
-    a = v.vol if isinstance(v, MRI) else np.asarray(v)
-    if a.ndim == 4 and a.shape[3] == 1:
-        a = a[..., 0]
-    if tuple(a.shape) != tuple(shape):
-        raise ValueError("%s has size %s, the tract's volume %s" % (what, tuple(a.shape), tuple(shape)))
-    if dtype == np.uint8:
-        a = a != 0
-    elif not np.issubdtype(a.dtype, np.integer):
-        if not np.array_equal(a, np.rint(a)):
-            raise ValueError("%s must hold integers" % what)
-    return np.ascontiguousarray(a.reshape(-1, order="F").astype(dtype))
-
-
-def _as_list(x):
-    return [x] if isinstance(x, (MRI, np.ndarray)) else list(x)
+_SIZE = " has size %s, the tract's volume %s"
 
 
 def _take(a, idx):
@@ -50,9 +33,9 @@ def str_select(tr: Tract, include=(), exclude=(), end_in=(), both_ends_in=(), mi
     or an array of the tract's volume size, non-zero inside; 32 regions in all.  The result has `hits` (uint32 [nkept, 3] = the
     OR of the regions' bits over the line, at its first and at its last point; bit r = the r-th region in the order include, exclude,
     end_in, both_ends_in) and `index` (int64 [nkept]: the line's index in `tr`) as attributes."""
-    groups = [_as_list(g) for g in (include, exclude, end_in, both_ends_in)]
-    shape = tuple(int(v) for v in tr.volsize)
-    rois = [_volume(r, shape, np.uint8, "a region") for g in groups for r in g]
+    groups = [_host.as_list(g) for g in (include, exclude, end_in, both_ends_in)]
+    shape = _host.dims(tr.volsize)
+    rois = [_host.mask(r, shape, "!= 0", frame0=False, refuse="a region" + _SIZE)[0] for g in groups for r in g]
     if len(rois) > 32:
         raise ValueError("%d regions: one call takes 32" % len(rois))
     masks, bit = [], 0
@@ -63,7 +46,7 @@ def str_select(tr: Tract, include=(), exclude=(), end_in=(), both_ends_in=(), mi
     keep = np.empty(npts.size, np.uint8)
     hits = np.empty((npts.size, 3), np.uint32)
     counts = (C.c_int64 * 2)()
-    ptrs = (C.c_void_p * max(1, len(rois)))(*[r.ctypes.data for r in rois])
+    ptrs = _host.pointers(rois)
     _lib.check(_lib.lib().fib_str_select(int(device), xyz.ctypes.data, npts.ctypes.data, npts.size, xyz.shape[0], shape[0], shape[1], shape[2],
                                          ptrs, len(rois), masks[0], masks[1], masks[2], masks[3], int(min_npts), int(max_npts),
                                          keep.ctypes.data, hits.ctypes.data, counts))
@@ -113,8 +96,11 @@ def str_connectome(tr: Tract, labels, ids=None, lengths: bool = True, device: in
     line end a node; counts[i, j] is the number of lines between nodes i and j, mean_length[i, j] their mean length in mm.  `ids`:
     the label values that are nodes, in node order (node k = ids[k - 1]); default: the sorted unique positive values of `labels`.
     Ends outside the volume or in a voxel whose label is no node go to row / column 0."""
-    shape = tuple(int(v) for v in tr.volsize)
-    lab = _volume(labels, shape, np.int32, "labels")
+    shape = _host.dims(tr.volsize)
+    lab = _host.volume(labels, shape, refuse="labels" + _SIZE)
+    if not np.issubdtype(lab.dtype, np.integer) and not np.array_equal(lab, np.rint(lab)):
+        raise ValueError("labels must hold integers")
+    lab = np.asfortranarray(lab, dtype=np.int32)
     if ids is None:
         ids = np.unique(lab[lab > 0])
     ids, remap = _remap(ids)

@@ -13,12 +13,11 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import Launch, float3, sync
 from .mri import MRI
-from .stream import _device_params
+from .stream import device_params
 from .tract import Tract
-from .xform import _row_major
 
 _HDR = struct.Struct("<6s3h3f3fh200sh200s16f444s4s4s6f2s6B3i")      # 1000 bytes, trk.jl:13-35
 assert _HDR.size == 1000
@@ -191,8 +190,8 @@ def stream_to_trk(outfile, field, shape, seeds, sublist, ref: MRI, stream=None, 
     on its way out (fibd_stream_pack_trk_xfm) and the header carries the output space (outsize, outres, outvox2ras)."""
     import time
     import torch
-    prm = _device_params(field, shape, seeds, sublist, "default", kw.get("len_min", 3), kw.get("len_max"), kw.get("ang_thresh", 45),
-                         kw.get("step_size", 0.5), kw.get("smooth_coeff", 0.2), kw.get("interp", "nearest"), integrator=kw.get("integrator", "euler"))
+    prm = device_params(field, shape, seeds, sublist, "default", kw.get("len_min", 3), kw.get("len_max"), kw.get("ang_thresh", 45),
+                        kw.get("step_size", 0.5), kw.get("smooth_coeff", 0.2), kw.get("interp", "nearest"), integrator=kw.get("integrator", "euler"))
     job = C.c_void_p()
     nl, npnt = C.c_int64(0), C.c_int64(0)
     lib = _lib.lib()
@@ -206,7 +205,7 @@ def stream_to_trk(outfile, field, shape, seeds, sublist, ref: MRI, stream=None, 
                 _lib.check(lib.fibd_stream_pack_trk(job, C.byref(vs), body.data_ptr(), L.sp))
             else:
                 vs = float3(xfm.outres)
-                _lib.check(lib.fibd_stream_pack_trk_xfm(job, _row_major(xfm), C.byref(vs), body.data_ptr(), L.sp))
+                _lib.check(lib.fibd_stream_pack_trk_xfm(job, _host.m16(xfm.vox2vox), C.byref(vs), body.data_ptr(), L.sp))
                 ref = SimpleNamespace(volsize=tuple(int(v) for v in xfm.outsize), volres=tuple(float(v) for v in xfm.outres),
                                       vox2ras=xfm.outvox2ras)
             sync(stream)                                    # the pack ran on `stream`: a copy only orders against the current one

@@ -4,17 +4,12 @@ definitions (pull-back through the output -> input matrix in float32, the inside
 "Volume resampling" section of include/fibers_hip.h.  All compute is in csrc/volxform.hip; there is no NumPy path here.
 
 Host tier: `MRI` in, `MRI` out, through fib_vol_xform.  Device tier: torch tensors in and out, through fibd_vol_xform on `stream`."""
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, tensor
 from .mri import MRI
-from .xform import Xform, _f32, _voxrot
-
-_WIDEN = {np.dtype(np.uint8): np.uint32, np.dtype(np.uint16): np.uint32, np.dtype(np.int8): np.int32, np.dtype(np.int16): np.int32}
-_WORDS = (np.dtype(np.float32), np.dtype(np.int32), np.dtype(np.uint32))
+from .xform import Xform, round32, voxrot_of
 
 
 def vol_xform_matrix(xfm: Xform) -> np.ndarray:
@@ -27,39 +22,7 @@ def vol_xform_matrix(xfm: Xform) -> np.ndarray:
         raise ValueError("vox2vox is singular: the volume cannot be pulled back through it") from None
     if not np.all(np.isfinite(inv)):
         raise ValueError("vox2vox is singular: the volume cannot be pulled back through it")
-    return _f32(inv)
-
-
-def _interp(interp):
-    if interp not in _lib.VOL_INTERP:
-        raise ValueError("interp must be 'nearest' or 'trilinear', not %r" % (interp,))
-    return _lib.VOL_INTERP[interp]
-
-
-def _row_major(m):
-    return (C.c_float * 16)(*[float(v) for v in np.ascontiguousarray(m, np.float32).reshape(-1)])
-
-
-def _bits(outside, dtype, narrow=None):
-    """`outside` cast to the volume's element type (`narrow` first, for a volume widened from it), as the int32 that carries its
-    32-bit pattern"""
-    with np.errstate(invalid="ignore", over="ignore"):
-        v = np.array([outside])
-        if narrow is not None:
-            v = v.astype(narrow)
-        return int(v.astype(dtype).view(np.int32)[0])
-
-
-def _words(mri, interp, who):
-    """mri.vol as the 32-bit words the sampler takes: float32 (either interpolation), int32 / uint32 as they are and 8- / 16-bit
-    integers widened, with "nearest"; anything else is a ValueError in the name of `who`"""
-    dt, nearest = mri.vol.dtype, _interp(interp) == _lib.VOL_INTERP["nearest"]
-    if dt in _WIDEN and nearest:
-        return np.asfortranarray(mri.vol.astype(_WIDEN[dt]))
-    if dt in _WORDS and (dt == np.float32 or nearest):
-        return np.asfortranarray(mri.vol)
-    raise ValueError("%s takes float32 volumes (either interpolation) or 8- / 16- / 32-bit integer volumes with 'nearest', not %s with %r"
-                     % (who, dt, interp))
+    return round32(inv)
 
 
 def xfm_header(inref: MRI, outref: MRI) -> Xform:
@@ -69,8 +32,8 @@ def xfm_header(inref: MRI, outref: MRI) -> Xform:
     A, B = np.asarray(inref.vox2ras, np.float32).astype(np.float64), np.asarray(outref.vox2ras, np.float32).astype(np.float64)
     x = Xform(insize=inref.volsize, outsize=outref.volsize, inres=inref.volres, outres=outref.volres,
               invox2ras=np.array(inref.vox2ras, np.float32), outvox2ras=np.array(outref.vox2ras, np.float32))
-    x.vox2vox = _f32(np.linalg.inv(B) @ A)
-    x.voxrot = _voxrot(x.vox2vox)
+    x.vox2vox = round32(np.linalg.inv(B) @ A)
+    x.voxrot = voxrot_of(x.vox2vox)
     return x
 
 
@@ -85,23 +48,14 @@ def mri_xform(xfm: Xform, mri: MRI, interp: str = "trilinear", outside=0, device
 
     `bval` / `bvec` are NOT carried over: reorienting gradients through the transform is out of scope, and copying them unrotated
     would be silently wrong.  mri.volsize must equal xfm.insize."""
-    code = _interp(interp)
+    _host.interp_code(interp)                               # (the first refusal, before the sizes are compared)
     if tuple(int(v) for v in xfm.insize) != tuple(mri.volsize):
         raise ValueError("the volume is %s but the transform's input space is %s" % (tuple(mri.volsize), tuple(int(v) for v in xfm.insize)))
-    dt = mri.vol.dtype
-    work = _words(mri, interp, "mri_xform")
+    code, work, bits, out = _host.resample_args(mri, interp, outside, xfm.outsize, "mri_xform")
     M = vol_xform_matrix(xfm)
-    nxi, nyi, nzi = (int(v) for v in mri.volsize)
-    nxo, nyo, nzo = (int(v) for v in xfm.outsize)
-    nf = mri.nframes
-    out = np.empty((nxo, nyo, nzo, nf), work.dtype, order="F")
-    _lib.check(_lib.lib().fib_vol_xform(int(device), _row_major(M), work.ctypes.data, nxi, nyi, nzi, nf, code,
-                                        _bits(outside, work.dtype, dt if dt in _WIDEN else None), out.ctypes.data, nxo, nyo, nzo))
-    if out.dtype != dt:
-        out = np.asfortranarray(out.astype(dt))
-    res = MRI(out, volres=tuple(float(v) for v in xfm.outres), vox2ras=np.array(xfm.outvox2ras, np.float32))
-    res.tr = mri.tr
-    return res
+    (nxi, nyi, nzi, nf), (nxo, nyo, nzo) = work.shape, out.shape[:3]
+    _lib.check(_lib.lib().fib_vol_xform(int(device), _host.m16(M), work.ctypes.data, nxi, nyi, nzi, nf, code, bits, out.ctypes.data, nxo, nyo, nzo))
+    return _host.resampled(out, mri, xfm.outres, xfm.outvox2ras)
 
 
 def vol_xform_device(out2in, vol, inshape, outshape, interp: str = "trilinear", outside=0, out=None, stream=None):
@@ -110,7 +64,7 @@ def vol_xform_device(out2in, vol, inshape, outshape, interp: str = "trilinear", 
     volume [nframes, nxo*nyo*nzo] (or [nvox]) in the input's type; `out` may be given (a view at any 4-byte boundary is fine; it
     must not overlap vol).  The call does not wait for the kernel."""
     import torch
-    code = _interp(interp)
+    code = _host.interp_code(interp)
     nxi, nyi, nzi = (int(v) for v in inshape)
     nxo, nyo, nzo = (int(v) for v in outshape)
     nvi, nvo = nxi * nyi * nzi, nxo * nyo * nzo
@@ -118,11 +72,11 @@ def vol_xform_device(out2in, vol, inshape, outshape, interp: str = "trilinear", 
     if vol.dtype != torch.float32 and code != _lib.VOL_INTERP["nearest"]:
         raise ArgError("'trilinear' takes float32 volumes, not %s" % vol.dtype)
     nf = vol.numel() // nvi
-    bits = _bits(outside, np.float32 if vol.dtype == torch.float32 else np.int32)
+    bits = _host.bits(outside, np.float32 if vol.dtype == torch.float32 else np.int32)
     with Launch(vol, stream) as L:
         if out is None:
             out = L.empty((nf, nvo) if vol.dim() > 1 else (nvo,), vol.dtype)
         else:
             tensor(out, vol.dtype, "out [nframes, nxo*nyo*nzo]", ref=vol, n=nf * nvo)
-        _lib.check(_lib.lib().fibd_vol_xform(_row_major(out2in), vol.data_ptr(), nxi, nyi, nzi, nf, code, bits, out.data_ptr(), nxo, nyo, nzo, L.sp))
+        _lib.check(_lib.lib().fibd_vol_xform(_host.m16(out2in), vol.data_ptr(), nxi, nyi, nzi, nf, code, bits, out.data_ptr(), nxo, nyo, nzo, L.sp))
     return out

@@ -10,13 +10,13 @@ from dataclasses import replace
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, tensor
+from ._host import dims as _dims, m16 as _m16
 from .mri import MRI
 from .nifti import load_nifti, mri_write
 from .tract import Tract
-from .volxform import _WIDEN, _bits, _interp, _row_major, _words
-from .xform import Xform, _f32
+from .xform import Xform, round32
 
 _ITK_VECTOR = 1007                                               # NIFTI_INTENT_VECTOR
 
@@ -126,7 +126,7 @@ def point_matrices(field_vox2ras, in_vox2ras, out_vox2ras, pre=None, post=None, 
     to_ras = _ras2ras(pre) @ _f64(in_vox2ras) @ _shift(-float(origin))
     to_field = _inv(_f64(field_vox2ras), "the field's vox2ras") @ to_ras
     from_ras = _shift(float(origin)) @ _inv(_f64(out_vox2ras), "the output's vox2ras") @ _ras2ras(post)
-    return _f32(to_ras), _f32(to_field), _f32(from_ras)
+    return round32(to_ras), round32(to_field), round32(from_ras)
 
 
 def volume_matrices(field_vox2ras, out_vox2ras, in_vox2ras, pre=None, post=None):
@@ -135,19 +135,15 @@ def volume_matrices(field_vox2ras, out_vox2ras, in_vox2ras, pre=None, post=None)
     to_ras = _ras2ras(pre) @ _f64(out_vox2ras)
     to_field = _inv(_f64(field_vox2ras), "the field's vox2ras") @ to_ras
     from_ras = _inv(_f64(in_vox2ras), "the volume's vox2ras") @ _ras2ras(post)
-    return _f32(to_ras), _f32(to_field), _f32(from_ras)
+    return round32(to_ras), round32(to_field), round32(from_ras)
 
 
 def invert_matrices(field_vox2ras, out_vox2ras):
     """(out_to_ras, ras_to_field) of warp_invert: the output grid's vox2ras and float32(inv(float64(field_vox2ras)))"""
-    return np.array(out_vox2ras, np.float32).reshape(4, 4), _f32(_inv(_f64(field_vox2ras), "the field's vox2ras"))
+    return np.array(out_vox2ras, np.float32).reshape(4, 4), round32(_inv(_f64(field_vox2ras), "the field's vox2ras"))
 
 
 # ---- host tier ----------------------------------------------------------------------------------------------------------------------
-def _dims(shape):
-    return tuple(int(v) for v in shape)
-
-
 def str_warp(warp: Warp, tr: Tract, outref: MRI = None, pre: Xform = None, post: Xform = None, origin=1, device: int = 0) -> Tract:
     """The lines of `tr` moved through the field.  A point travels tract volume -> (pre.ras2ras) -> field space A -> (phi) -> B ->
     (post.ras2ras) -> the output volume; `pre` and `post` are Xforms, each the identity when None.  The points are tr.xyz and
@@ -162,11 +158,11 @@ def str_warp(warp: Warp, tr: Tract, outref: MRI = None, pre: Xform = None, post:
     else:
         raise ValueError("str_warp needs the output geometry: outref (an MRI) or post (an Xform with outsize / outres / outvox2ras)")
     A, Q, B = point_matrices(warp.vox2ras, tr.vox2ras, v2r, pre, post, origin)
-    xyz = np.ascontiguousarray(np.asarray(tr.xyz, np.float32).reshape(-1, 3))
+    xyz, _ = _host.packed(tr)
     out = np.empty_like(xyz)
     nx, ny, nz = _dims(warp.volsize)
     disp = warp._planar()
-    _lib.check(_lib.lib().fib_warp_points(int(device), disp.ctypes.data, nx, ny, nz, _row_major(A), _row_major(Q), _row_major(B),
+    _lib.check(_lib.lib().fib_warp_points(int(device), disp.ctypes.data, nx, ny, nz, _m16(A), _m16(Q), _m16(B),
                                           xyz.ctypes.data, out.ctypes.data, xyz.shape[0]))
     return replace(tr, xyz=out, volsize=size, volres=res, vox2ras=v2r)
 
@@ -182,25 +178,15 @@ def mri_warp(warp: Warp, mri: MRI, outref: MRI = None, interp: str = "trilinear"
     one way and points the other way (warp_invert makes the field for the other half).
 
     Element types and the widening of narrow integers are mri_xform's.  `bval` / `bvec` are NOT carried over."""
-    code = _interp(interp)
-    dt = mri.vol.dtype
-    work = _words(mri, interp, "mri_warp")
     grid = warp.field if outref is None else outref
+    code, work, bits, out = _host.resample_args(mri, interp, outside, grid.volsize, "mri_warp")
     A, Q, B = volume_matrices(warp.vox2ras, grid.vox2ras, mri.vox2ras, pre, post)
     nx, ny, nz = _dims(warp.volsize)
-    nxi, nyi, nzi = _dims(mri.volsize)
-    nxo, nyo, nzo = _dims(grid.volsize)
-    nf = mri.nframes
-    out = np.empty((nxo, nyo, nzo, nf), work.dtype, order="F")
+    (nxi, nyi, nzi, nf), (nxo, nyo, nzo) = work.shape, out.shape[:3]
     disp = warp._planar()
-    _lib.check(_lib.lib().fib_warp_volume(int(device), disp.ctypes.data, nx, ny, nz, _row_major(A), _row_major(Q), _row_major(B), work.ctypes.data,
-                                          nxi, nyi, nzi, nf, code, _bits(outside, work.dtype, dt if dt in _WIDEN else None), out.ctypes.data,
-                                          nxo, nyo, nzo))
-    if out.dtype != dt:
-        out = np.asfortranarray(out.astype(dt))
-    res = MRI(out, volres=tuple(float(v) for v in grid.volres), vox2ras=np.array(grid.vox2ras, np.float32))
-    res.tr = mri.tr
-    return res
+    _lib.check(_lib.lib().fib_warp_volume(int(device), disp.ctypes.data, nx, ny, nz, _m16(A), _m16(Q), _m16(B), work.ctypes.data,
+                                          nxi, nyi, nzi, nf, code, bits, out.ctypes.data, nxo, nyo, nzo))
+    return _host.resampled(out, mri, grid.volres, grid.vox2ras)
 
 
 def warp_invert(warp: Warp, outref: MRI, niter: int = 20, device: int = 0):
@@ -215,7 +201,7 @@ def warp_invert(warp: Warp, outref: MRI, niter: int = 20, device: int = 0):
     inv = np.empty((nxo, nyo, nzo, 3), np.float32, order="F")
     err = np.empty((nxo, nyo, nzo, 1), np.float32, order="F")
     disp = warp._planar()
-    _lib.check(_lib.lib().fib_warp_invert(int(device), disp.ctypes.data, nx, ny, nz, _row_major(Y), _row_major(Q), int(niter), inv.ctypes.data,
+    _lib.check(_lib.lib().fib_warp_invert(int(device), disp.ctypes.data, nx, ny, nz, _m16(Y), _m16(Q), int(niter), inv.ctypes.data,
                                           err.ctypes.data, nxo, nyo, nzo))
     geo = dict(volres=tuple(float(v) for v in outref.volres), vox2ras=np.array(outref.vox2ras, np.float32))
     return Warp(MRI(inv, **geo)), MRI(err, **geo)
@@ -259,7 +245,7 @@ def warp_points_device(packed, shape, to_ras, to_field, from_ras, xyz, out=None,
         raise ArgError("xyz must be [N, 3] or a flat vector of 3N coordinates")
     with Launch(packed, stream) as L:
         out = L.empty(xyz.shape, torch.float32) if out is None else tensor(out, torch.float32, "out", ref=packed, n=xyz.numel())
-        _lib.check(_lib.lib().fibd_warp_points(packed.data_ptr(), nx, ny, nz, _row_major(to_ras), _row_major(to_field), _row_major(from_ras),
+        _lib.check(_lib.lib().fibd_warp_points(packed.data_ptr(), nx, ny, nz, _m16(to_ras), _m16(to_field), _m16(from_ras),
                                                xyz.data_ptr(), out.data_ptr(), xyz.numel() // 3, L.sp))
     return out
 
@@ -270,7 +256,7 @@ def warp_volume_device(packed, shape, to_ras, to_field, from_ras, vol, inshape, 
     back through the packed field onto a grid of `outshape` (volume_matrices) -> [nframes, nxo*nyo*nzo] (or [nvox]) in the input's
     type.  `out` may be given (any 4-byte boundary; it must not overlap vol).  Does not wait."""
     import torch
-    code = _interp(interp)
+    code = _host.interp_code(interp)
     nx, ny, nz = _packed(packed, shape)
     nxi, nyi, nzi = _dims(inshape)
     nxo, nyo, nzo = _dims(outshape)
@@ -279,13 +265,13 @@ def warp_volume_device(packed, shape, to_ras, to_field, from_ras, vol, inshape, 
     if vol.dtype != torch.float32 and code != _lib.VOL_INTERP["nearest"]:
         raise ArgError("'trilinear' takes float32 volumes, not %s" % vol.dtype)
     nf = vol.numel() // nvi
-    bits = _bits(outside, np.float32 if vol.dtype == torch.float32 else np.int32)
+    bits = _host.bits(outside, np.float32 if vol.dtype == torch.float32 else np.int32)
     with Launch(packed, stream) as L:
         if out is None:
             out = L.empty((nf, nvo) if vol.dim() > 1 else (nvo,), vol.dtype)
         else:
             tensor(out, vol.dtype, "out [nframes, nxo*nyo*nzo]", ref=packed, n=nf * nvo)
-        _lib.check(_lib.lib().fibd_warp_volume(packed.data_ptr(), nx, ny, nz, _row_major(to_ras), _row_major(to_field), _row_major(from_ras),
+        _lib.check(_lib.lib().fibd_warp_volume(packed.data_ptr(), nx, ny, nz, _m16(to_ras), _m16(to_field), _m16(from_ras),
                                                vol.data_ptr(), nxi, nyi, nzi, nf, code, bits, out.data_ptr(), nxo, nyo, nzo, L.sp))
     return out
 
@@ -307,6 +293,6 @@ def warp_invert_device(packed, shape, out_to_ras, ras_to_field, outshape, niter:
             err = None
         else:
             tensor(err, torch.float32, "err [nxo*nyo*nzo]", ref=packed, n=nvo)
-        _lib.check(_lib.lib().fibd_warp_invert(packed.data_ptr(), nx, ny, nz, _row_major(out_to_ras), _row_major(ras_to_field), int(niter),
+        _lib.check(_lib.lib().fibd_warp_invert(packed.data_ptr(), nx, ny, nz, _m16(out_to_ras), _m16(ras_to_field), int(niter),
                                                inv.data_ptr(), None if err is None else err.data_ptr(), nxo, nyo, nzo, L.sp))
     return inv, err

@@ -6,12 +6,11 @@ inverses, products, the SVD behind `voxrot` -- are computed in float64 from the 
 reference does them in Float32 through LAPACK/BLAS, whose operation order is not reproduced).  The per-point apply,
 the hot path, is HIP (csrc/xform.hip): a NumPy array goes through the host-buffer entry fib_xfm_apply, a CUDA tensor through
 fibd_xfm_apply on the caller's stream.  Only the integer-output form of `xfm_apply!` (round, ties to even) is evaluated here."""
-import ctypes as C
 from dataclasses import dataclass, field, replace
 
 import numpy as np
 
-from . import _lib
+from . import _host, _lib
 from ._dev import ArgError, Launch, tensor
 from .mri import MRI
 from .tract import Tract
@@ -44,14 +43,15 @@ class Xform:
         self.voxrot = np.asarray(self.voxrot, np.float32).reshape(3, 3)
 
 
-def _f32(a):
+def round32(a):
+    """a matrix computed in float64, rounded to float32 once (the rule of every matrix this package derives)"""
     return np.asarray(a, np.float64).astype(np.float32)
 
 
-def _voxrot(vox2vox):
-    """U * Vt of the SVD of vox2vox[1:3, 1:3] (util.jl:265-267)"""
+def voxrot_of(vox2vox):
+    """the rotational component of a vox2vox matrix: U * Vt of the SVD of vox2vox[1:3, 1:3] (util.jl:265-267)"""
     u, _, vt = np.linalg.svd(np.asarray(vox2vox, np.float64)[:3, :3])
-    return _f32(u @ vt)
+    return round32(u @ vt)
 
 
 # ---- xfm_read ---------------------------------------------------------------------------------------------------------------------
@@ -65,7 +65,7 @@ def _vox2ras(size, res, xras, yras, zras, cras):
     out = np.eye(4)
     out[:3, :3] = M
     out[:3, 3] = np.asarray(cras, np.float64) - (M @ np.asarray(size, np.float64)) / 2
-    return _f32(out)
+    return round32(out)
 
 
 def _read_lta(ltafile):
@@ -119,13 +119,13 @@ def _xfm_read_lta(ltafile):
     A, B, R = x.invox2ras.astype(np.float64), x.outvox2ras.astype(np.float64), regmat.astype(np.float64)
     if regtype == 0:                                                 # LINEAR_VOX_TO_VOX
         x.vox2vox = regmat.copy()
-        x.ras2ras = _f32(B @ R @ np.linalg.inv(A))
+        x.ras2ras = round32(B @ R @ np.linalg.inv(A))
     elif regtype == 1:                                               # LINEAR_RAS_TO_RAS
-        x.vox2vox = _f32(np.linalg.inv(B) @ R @ A)
+        x.vox2vox = round32(np.linalg.inv(B) @ R @ A)
         x.ras2ras = regmat.copy()
     else:
         raise ValueError("Invalid transform type %d in %s" % (regtype, ltafile))
-    x.voxrot = _voxrot(x.vox2vox)
+    x.voxrot = voxrot_of(x.vox2vox)
     return x
 
 
@@ -146,9 +146,9 @@ def _xfm_read_mat(matfile, inref: MRI, outref: MRI):
         raise ValueError("%s does not hold a 4 x 4 matrix" % matfile)
     x = Xform(insize=inref.volsize, outsize=outref.volsize, inres=inref.volres, outres=outref.volres,
               invox2ras=inref.vox2ras, outvox2ras=outref.vox2ras)
-    x.vox2vox = _f32(np.linalg.inv(_fsl_scale(outref)) @ mat @ _fsl_scale(inref))
-    x.ras2ras = _f32(x.outvox2ras.astype(np.float64) @ x.vox2vox.astype(np.float64) @ np.linalg.inv(x.invox2ras.astype(np.float64)))
-    x.voxrot = _voxrot(x.vox2vox)
+    x.vox2vox = round32(np.linalg.inv(_fsl_scale(outref)) @ mat @ _fsl_scale(inref))
+    x.ras2ras = round32(x.outvox2ras.astype(np.float64) @ x.vox2vox.astype(np.float64) @ np.linalg.inv(x.invox2ras.astype(np.float64)))
+    x.voxrot = voxrot_of(x.vox2vox)
     return x
 
 
@@ -157,7 +157,7 @@ def xfm_inv(xfm: Xform) -> Xform:
     """Base.inv(xfm) (util.jl:328-343)"""
     return Xform(insize=xfm.outsize.copy(), outsize=xfm.insize.copy(), inres=xfm.outres.copy(), outres=xfm.inres.copy(),
                  invox2ras=xfm.outvox2ras.copy(), outvox2ras=xfm.invox2ras.copy(),
-                 vox2vox=_f32(np.linalg.inv(xfm.vox2vox.astype(np.float64))), ras2ras=_f32(np.linalg.inv(xfm.ras2ras.astype(np.float64))),
+                 vox2vox=round32(np.linalg.inv(xfm.vox2vox.astype(np.float64))), ras2ras=round32(np.linalg.inv(xfm.ras2ras.astype(np.float64))),
                  voxrot=xfm.voxrot.T.copy())
 
 
@@ -171,8 +171,8 @@ def xfm_compose(xfm1: Xform, *xfms: Xform) -> Xform:
         v2v = v2v @ x.vox2vox.astype(np.float64)
         r2r = r2r @ x.ras2ras.astype(np.float64)
     out = Xform(insize=last.insize.copy(), outsize=xfm1.outsize.copy(), inres=last.inres.copy(), outres=xfm1.outres.copy(),
-                invox2ras=last.invox2ras.copy(), outvox2ras=xfm1.outvox2ras.copy(), vox2vox=_f32(v2v), ras2ras=_f32(r2r))
-    out.voxrot = _voxrot(out.vox2vox)
+                invox2ras=last.invox2ras.copy(), outvox2ras=xfm1.outvox2ras.copy(), vox2vox=round32(v2v), ras2ras=round32(r2r))
+    out.voxrot = voxrot_of(out.vox2vox)
     return out
 
 
@@ -186,11 +186,6 @@ def xfm_rotate(xfm: Xform, point):
 
 
 # ---- xfm_apply --------------------------------------------------------------------------------------------------------------------
-def _row_major(xfm: Xform):
-    """the vox2vox argument of the C ABI: row-major float32 [16]"""
-    return (C.c_float * 16)(*[float(v) for v in np.ascontiguousarray(xfm.vox2vox, np.float32).reshape(-1)])
-
-
 def _apply_int(m, p, out):
     """xfm_apply! into an Integer array (util.jl:423-425): the float32 loop, then round (ties to even); NaN or a value outside the
     integer type raises, as Julia's round(Int, x) does"""
@@ -235,7 +230,7 @@ def xfm_apply(xfm: Xform, points, out=None, device=0, stream=None):
         out = np.empty_like(p)
     elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.size == p.size):
         raise ValueError("out must be a contiguous float32 array of the input's size")
-    _lib.check(_lib.lib().fib_xfm_apply(int(device), _row_major(xfm), p.ctypes.data, out.ctypes.data, p.size // 3))
+    _lib.check(_lib.lib().fib_xfm_apply(int(device), _host.m16(xfm.vox2vox), p.ctypes.data, out.ctypes.data, p.size // 3))
     return out
 
 
@@ -245,7 +240,7 @@ def _apply_device(xfm, points, out, stream):
         raise ArgError("points must be [N, 3] or a flat vector of 3N coordinates")
     with Launch(points, stream) as L:
         out = L.empty(points.shape, torch.float32) if out is None else tensor(out, torch.float32, "out", ref=points, n=points.numel())
-        _lib.check(_lib.lib().fibd_xfm_apply(_row_major(xfm), points.data_ptr(), out.data_ptr(), points.numel() // 3, L.sp))
+        _lib.check(_lib.lib().fibd_xfm_apply(_host.m16(xfm.vox2vox), points.data_ptr(), out.data_ptr(), points.numel() // 3, L.sp))
     return out
 
 

@@ -152,7 +152,7 @@ def _job(fj, n=20, len_max=None, lcm=False):
     """a traced job on a small curved field (fibd_stream_trace / _trace_lcm), with the field, seeds and sublist it came from"""
     import torch
     from fibers_jl_amd import _lib
-    from fibers_jl_amd.stream import _params, default_workspace
+    from fibers_jl_amd.stream import default_workspace, params
     nz = 1 if lcm else n
     x, y, z = np.meshgrid(np.arange(n), np.arange(n), np.arange(nz), indexing="ij")
     c = (n - 1) / 2.0
@@ -164,7 +164,7 @@ def _job(fj, n=20, len_max=None, lcm=False):
     seeds = torch.nonzero(mout).flatten()
     sub = torch.tensor([[0.1, -0.2, 0.0 if lcm else 0.3], [0.3, 0.25, 0.0]], dtype=torch.float32, device="cuda")
     shape = (n, n, nz)
-    prm = _params(shape, 1, 3, len_max if len_max else max(shape), 60 if len_max else 45, 0.5, 0.2, ws=default_workspace(0))
+    prm = params(shape, 1, 3, len_max if len_max else max(shape), 60 if len_max else 45, 0.5, 0.2, ws=default_workspace(0))
     job, nl, npnt = C.c_void_p(), C.c_int64(0), C.c_int64(0)
     L = _lib.lib()
     sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -192,7 +192,7 @@ def _pack(fj, job, nl, npnt):
 
 def _pack_trk(fj, job, nl, npnt, xfm=None, vs=(1.0, 1.0, 1.0)):
     import torch
-    from fibers_jl_amd.xform import _row_major
+    from fibers_jl_amd._host import m16
     L = fj.lib()
     body = torch.full((nl + 3 * npnt,), -7.0, dtype=torch.float32, device="cuda")
     sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -200,7 +200,7 @@ def _pack_trk(fj, job, nl, npnt, xfm=None, vs=(1.0, 1.0, 1.0)):
     if xfm is None:
         rc = L.fibd_stream_pack_trk(job, C.byref(v), body.data_ptr(), sp)
     else:
-        rc = L.fibd_stream_pack_trk_xfm(job, _row_major(xfm), C.byref(v), body.data_ptr(), sp)
+        rc = L.fibd_stream_pack_trk_xfm(job, m16(xfm.vox2vox), C.byref(v), body.data_ptr(), sp)
     torch.cuda.synchronize()
     return rc, body.cpu().numpy().tobytes()
 

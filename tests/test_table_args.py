@@ -15,7 +15,7 @@ def _table(n=7):
 
 
 def test_table_args_gives_the_same_bytes_for_every_input_form():
-    from fibers_jl_amd.dti import _table_args
+    from fibers_jl_amd._host import table_args as _table_args
     bval, g = _table()
     g32 = g.astype(np.float32)
     forms = [(bval.tolist(), g.tolist()),

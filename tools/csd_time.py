@@ -19,7 +19,7 @@ import torch  # noqa: E402
 import fibers_jl_amd as fj  # noqa: E402
 from fibers_jl_amd import phantom  # noqa: E402
 from fibers_jl_amd.csd import csd_rec_device  # noqa: E402
-from fibers_jl_amd.dki import DKI_FIELDS, _nframes  # noqa: E402
+from fibers_jl_amd.dki import DKI_FIELDS, nframes  # noqa: E402
 
 RESPONSE = (1.7e-3, 0.3e-3, 1000.0)
 
@@ -78,7 +78,7 @@ def main():
         plan.close()
     if not a.no_dki:
         kplan = fj.DkiPlan(bval, bvec)
-        kout = {k: torch.empty((_nframes(k), nvox) if _nframes(k) > 1 else (nvox,), dtype=torch.float32, device=dev) for k in DKI_FIELDS}
+        kout = {k: torch.empty((nframes(k), nvox) if nframes(k) > 1 else (nvox,), dtype=torch.float32, device=dev) for k in DKI_FIELDS}
         for name, m in masks.items():
             inside = int(m.sum().item())
             med, lo, hi = timed(lambda: fj.dki_fit_device(kplan, dwi, m, out=kout, stream=stream), a.runs)

@@ -16,7 +16,7 @@ import torch  # noqa: E402
 
 import fibers_jl_amd as fj  # noqa: E402
 from fibers_jl_amd import phantom  # noqa: E402
-from fibers_jl_amd.dki import DKI_FIELDS, _nframes  # noqa: E402
+from fibers_jl_amd.dki import DKI_FIELDS, nframes  # noqa: E402
 from fibers_jl_amd.dti import DTI_FIELDS  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
@@ -53,7 +53,7 @@ def main():
     masks = {"mask A": torch.ones(nvox, dtype=torch.uint8, device=dev), "ball": phantom.ball_mask_torch(shape, dev)}
     stream = torch.cuda.current_stream()
     kplan, tplan = fj.DkiPlan(bval, bvec), fj.DtiPlan(bval, bvec)
-    kout = {k: torch.empty((_nframes(k), nvox) if _nframes(k) > 1 else (nvox,), dtype=torch.float32, device=dev) for k in DKI_FIELDS}
+    kout = {k: torch.empty((nframes(k), nvox) if nframes(k) > 1 else (nvox,), dtype=torch.float32, device=dev) for k in DKI_FIELDS}
     tout = {k: kout[k] for k in DTI_FIELDS}
     res = dict(shape=list(shape), nvol=nvol, ndir=kplan.ndir, runs=a.runs, lib=os.path.basename(fj.LIB_PATH), device=torch.cuda.get_device_name(0), cases={})
     for name, m in masks.items():

@@ -212,8 +212,8 @@ def leg_stream(shape=SHAPE, reps=3, dev=None):
     ov = np.ascontiguousarray(np.asfortranarray(phantom.fibre_field(nx, ny, nz).astype(np.float32)).reshape(nvox, 3, order="F").T)   # [3, nvox] planar
     mask = np.ascontiguousarray(phantom.ball_mask(nx, ny, nz).reshape(-1, order="F").astype(np.uint8))
     sub = np.array([[0.1, -0.2, 0.3]], np.float32)
-    smod = sys.modules[fj.stream_device_run.__module__]                    # (fj.stream is the function; its module holds _params)
-    prm = smod._params((nx, ny, nz), 1, 3, max(shape), 45, 0.5, 0.2, 0, 10, None)
+    smod = sys.modules[fj.stream_device_run.__module__]                    # (fj.stream is the function; its module holds params)
+    prm = smod.params((nx, ny, nz), 1, 3, max(shape), 45, 0.5, 0.2, 0, 10, None)
     pv = (C.c_void_p * 1)(ov.ctypes.data)
     res = {}
 

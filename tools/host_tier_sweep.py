@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import fibers_jl_amd as fj
 from fibers_jl_amd import phantom, _lib
-from fibers_jl_amd.dti import _check_tables, _mask_checked
+from fibers_jl_amd._host import check_tables, mask as mask_arg
 SHAPE = (140, 140, 140); dev = torch.device("cuda", 0)
 bval, bvec = phantom.scheme_gqi()
 d, _ = phantom.make_dwi_torch(SHAPE, bval, bvec, 2, dev, nfib=1)
@@ -16,7 +16,7 @@ if os.environ.get("MASK") == "ball":
     mk = np.asfortranarray(phantom.ball_mask_torch(SHAPE, dev).reshape(SHAPE[::-1]).permute(2, 1, 0).cpu().numpy().astype(np.uint8))
 dwi = fj.MRI(host, bval, bvec); mask = fj.MRI(mk)
 print("mask keeps %.1f %% of the volume" % (100.0 * mk.mean()))
-L = _lib.lib(); bv, bg = _check_tables(dwi); m, mdt = _mask_checked(mask, SHAPE)
+L = _lib.lib(); bv, bg = check_tables(dwi); m, mdt = mask_arg(mask, SHAPE)
 sph = fj.sphere_642
 v = np.asfortranarray(sph.vertices, np.float32); f = np.asfortranarray(sph.faces, np.int32)
 odf = np.ones(SHAPE + (sph.nvert,), np.float32, order="F")

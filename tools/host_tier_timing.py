@@ -32,10 +32,11 @@ for name, (bval, bvec), fn in (("dti_fit 140^3x64", phantom.scheme_dti(60, 4, 10
     # the C call alone, outputs allocated and touched beforehand (what the library itself costs)
     import ctypes as C
     from fibers_jl_amd import _lib
-    from fibers_jl_amd.dti import DTI_FIELDS, _check_tables, _mask_checked
+    from fibers_jl_amd._host import check_tables, mask as mask_arg
+    from fibers_jl_amd.dti import DTI_FIELDS
     L = _lib.lib()
-    bv, bg = _check_tables(dwi)
-    m, mdt = _mask_checked(mask, SHAPE)
+    bv, bg = check_tables(dwi)
+    m, mdt = mask_arg(mask, SHAPE)
     if "dti" in name:
         outs = {k: np.ones(SHAPE + ((3,) if "vec" in k else (1,)), np.float32, order="F") for k in DTI_FIELDS}
         o = _lib.DtiOut(*[outs[k].ctypes.data for k in DTI_FIELDS])

@@ -58,7 +58,7 @@ def main():
             small_n = torch.full((capl,), -7, dtype=torch.int32, device=dev)
             small_s = torch.zeros(capl, dtype=torch.int64, device=dev)
             small_x = torch.full((capp + 8, 3), -7.0, device=dev)
-            prm = smod._params(shape, nvec, len_min, 60, 45, 0.5, 0.3, 0, 10, smod.default_workspace(0))
+            prm = smod.params(shape, nvec, len_min, 60, 45, 0.5, 0.3, 0, 10, smod.default_workspace(0))
             nl, npnt = C.c_int64(0), C.c_int64(0)
             rc = _lib.lib().fibd_stream_run(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sub.data_ptr(), sub.shape[0],
                                             small_n.data_ptr(), small_s.data_ptr(), capl, small_x.data_ptr(), capp, C.byref(nl), C.byref(npnt), None)

@@ -92,9 +92,9 @@ def main():
     def density(mode):
         # (`out=` accumulates; the timed call is the plain form, zero-fill of the 11-MB map included, into a map that exists)
         from fibers_jl_amd import _lib
-        from fibers_jl_amd.dti import _stream_ptr
+        from fibers_jl_amd._dev import stream_ptr
         _lib.check(_lib.lib().fibd_str_density(xyz.data_ptr(), npts.data_ptr(), nl, npnt, 140, 140, 140, _lib.DENSITY_MODES[mode], dens.data_ptr(),
-                                               nout.data_ptr(), work.data_ptr(), work.numel() * 8, _stream_ptr(None)))
+                                               nout.data_ptr(), work.data_ptr(), work.numel() * 8, stream_ptr(None)))
     row("points", lambda: density("points"), 12, n_runs64)
     row("lines", lambda: density("lines"), 12, n_pairs)
     row("endpoints", lambda: density("endpoints"), 12, 2 * nl)

@@ -20,8 +20,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fibers_jl_amd as fj  # noqa: E402
 from fibers_jl_amd import _lib, phantom  # noqa: E402
-from fibers_jl_amd.stream import _params, default_workspace  # noqa: E402
-from fibers_jl_amd.xform import _row_major  # noqa: E402
+from fibers_jl_amd._host import m16  # noqa: E402
+from fibers_jl_amd.stream import default_workspace, params  # noqa: E402
 import xform_ref  # noqa: E402
 
 M = np.array([[0.98, -0.17, 0.05, 3.25], [0.16, 0.97, -0.11, -7.5], [-0.07, 0.12, 1.03, 12.125], [1e-4, -2e-4, 1.5e-4, 1.0]], np.float32)
@@ -60,7 +60,7 @@ def main():
     field, mout = fj.stream_field_device([o["eigvec1"]], fa=o["fa"], fa_thresh=0.1, mask=bm)
     seeds = torch.nonzero(mout).flatten()
     sub = torch.tensor([[0.1, -0.2, 0.3]], dtype=torch.float32, device=dev)
-    prm = _params(shape, 1, 3, None, 45, 0.5, 0.2, ws=default_workspace(0))
+    prm = params(shape, 1, 3, None, 45, 0.5, 0.2, ws=default_workspace(0))
     job, nl, npnt = C.c_void_p(), C.c_int64(0), C.c_int64(0)
     sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(L.fibd_stream_trace(C.byref(prm), field.data_ptr(), seeds.data_ptr(), seeds.numel(), sub.data_ptr(), 1, sp,
@@ -75,7 +75,7 @@ def main():
         # pack_trk vs pack_trk_xfm, interleaved
         body = torch.empty(nl + 3 * npnt, dtype=torch.float32, device=dev)
         vs = (C.c_float * 3)(1.0, 1.0, 1.0)
-        mx = _row_major(fj.Xform(vox2vox=M))
+        mx = m16(M)
         plain, xf = [], []
         for _ in range(args.reps):
             plain += events_ms(lambda: _lib.check(L.fibd_stream_pack_trk(job, C.byref(vs), body.data_ptr(), sp)), 1, 1)
