@@ -15,6 +15,9 @@ from .csd import CSD, CsdPlan, csd_design, csd_rec, csd_response, csd_write  # n
 # (the device tier of dwi_denoise is reached through the module: denoise.dwi_denoise_device)
 from . import denoise  # noqa: F401
 from .denoise import Denoised, dwi_denoise  # noqa: F401
+# (the device tier of the brain mask is reached through the module: mask.dwi_mask_device, mask.vol_median_device, mask.mask_components_device)
+from . import mask  # noqa: F401
+from .mask import BrainMask, dwi_mask, mask_components, vol_median  # noqa: F401
 from .gqi import (DSI, GQI, OdfPlan, dsi_rec, find_peaks, find_peaks_device, find_peaks_work, gqi_rec, odf_rec_device,  # noqa: F401
                   qa_normalize_device)
 from .rumba import RUMBASD, RumbaPlan, rumba_rec, rumba_rec_device  # noqa: F401

@@ -48,6 +48,18 @@ class CsdOut(C.Structure):
     _fields_ = [("sh", C.c_void_p), ("odf", C.c_void_p), ("niter", C.c_void_p), ("peak", C.c_void_p * 3), ("f", C.c_void_p * 3)]
 
 
+FIB_MASK_KEEP_LARGEST, FIB_MASK_FILL_HOLES = 1, 2
+
+
+class MaskParams(C.Structure):
+    _fields_ = [("radius", C.c_int), ("numpass", C.c_int), ("flags", C.c_int), ("dilate", C.c_int)]
+
+
+class MaskInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("kstar", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("threshold", C.c_double),
+                ("n_above", C.c_int64), ("n_components", C.c_int64), ("n_kept", C.c_int64), ("n_filled", C.c_int64), ("n_mask", C.c_int64)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("nvec", C.c_int32),
                 ("len_min", C.c_int32), ("len_max", C.c_int32),
@@ -114,6 +126,16 @@ _PROTOS = {
     "fibd_dwi_denoise_work_size": (i32, [i32, i32, i32, i32, i32, C.POINTER(C.c_uint64)]),
     "fibd_dwi_denoise": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     "fib_dwi_denoise": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "fib_dwi_mask_check": (i32, [i32, i32, i32, i32, vp, i32, C.POINTER(MaskParams)]),
+    "fibd_vol_median_work_size": (i32, [i32, i32, i32, i32, C.POINTER(C.c_uint64)]),
+    "fibd_vol_median": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, C.c_uint64, vp]),
+    "fibd_mask_components_work_size": (i32, [i32, i32, i32, C.POINTER(C.c_uint64)]),
+    "fibd_mask_components": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_dwi_mask_work_size": (i32, [i32, i32, i32, C.POINTER(C.c_uint64)]),
+    "fibd_dwi_mask": (i32, [vp, i64, i32, vp, i32, i32, i32, i32, C.POINTER(MaskParams), vp, vp, vp, vp, C.c_uint64, vp]),
+    "fib_dwi_mask": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, C.POINTER(MaskParams), vp, vp, C.POINTER(MaskInfo)]),
+    "fib_vol_median": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "fib_mask_components": (i32, [i32, vp, i32, i32, i32, i32, vp, vp, C.POINTER(MaskInfo)]),
     "fibd_dti_last_partial_count": (i32, [vp, vp, C.POINTER(i64)]),
     "fibd_odf_rec": (i32, [vp, vp, vp, i64, vp, vp, P3, P3, vp, i32, vp]),
     "fibd_qa_normalize": (i32, [P3, i64, f32, vp]),

@@ -780,6 +780,95 @@ extern "C" int fib_vol_xform(int device, const float out2in[16], const void *vol
                         });
 } FIB_API_CATCH
 
+// ---- the brain mask's host forms (volmask.hip).  What stays resident is allocated first, so that the chunk is sized by what is left.
+// dwi_mask: only the listed frames travel, a chunk at a time in the list's order, into the float64 sums of the workspace
+extern "C" int fib_dwi_mask(int device, const float *dwi, int nx, int ny, int nz, int nvol, const int32_t *frames, int nframes,
+                            const fib_mask_params *params, uint8_t *mask, float *b0, fib_mask_info *info) try {
+    FIB_CHECK(dwi && mask && info, FIB_ERR_INVALID, "NULL argument");
+    RC(fib_dwi_mask_check(nx, ny, nz, nvol, frames, nframes, params));
+    DevLease lease;
+    RC(lease.take(device, "dwi_mask runs on one device (FIB_DEVICE_ALL is not supported)"));
+    const size_t nvox = (size_t)nx * ny * nz;
+    size_t work_bytes = 0;
+    RC(fibd_dwi_mask_work_size(nx, ny, nz, &work_bytes));
+    fib::DevBuf<char> d_work;
+    fib::DevBuf<uint8_t> d_mask;
+    fib::DevBuf<float> d_b0, d_frames;
+    fib::DevBuf<fib_mask_info> d_info;
+    RC(d_work.alloc(work_bytes));
+    RC(d_mask.alloc(nvox));
+    if (b0) RC(d_b0.alloc(nvox));
+    RC(d_info.alloc(1));
+    int nfc = 0;
+    if (const char *e = fib::env("FIBERS_MASK_FRAMES")) nfc = std::min(atoi(e), nframes);
+    if (nfc <= 0) {
+        size_t fr = 0, tot = 0;
+        FIB_HIP(hipMemGetInfo(&fr, &tot));
+        nfc = fibh::frames_per_chunk(fr, nvox, 0, nframes);
+        FIB_CHECK(nfc >= 1, FIB_ERR_NOMEM, "dwi_mask: one frame does not fit in device memory beside the workspace");
+    }
+    RC(d_frames.alloc(nvox * nfc));
+    for (int f0 = 0; f0 < nframes; f0 += nfc) {
+        const int nf = std::min(nfc, nframes - f0);
+        for (int j = 0; j < nf; j++) RC(h2d(d_frames.p + nvox * j, dwi + nvox * frames[f0 + j], sizeof(float) * nvox));
+        RC(fib::vm_mean_add(d_work.p, d_frames.p, (int64_t)nvox, nf, f0 == 0, nullptr));
+        FIB_HIP(hipStreamSynchronize(nullptr));             // (the chunk's buffer is written again next round)
+    }
+    RC(fib::vm_mask_finish(d_work.p, nframes, nx, ny, nz, params, d_mask.p, b0 ? d_b0.p : nullptr, d_info.p, nullptr));
+    RC(d2h(mask, d_mask.p, nvox));
+    if (b0) RC(d2h(b0, d_b0.p, sizeof(float) * nvox));
+    RC(d2h(info, d_info.p, sizeof(fib_mask_info)));
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_vol_median(int device, const float *in, int nx, int ny, int nz, int nframes, int radius, int numpass, float *out) try {
+    FIB_CHECK(in && out, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nframes > 0, FIB_ERR_INVALID, "nframes must be positive");
+    size_t work_bytes = 0;
+    RC(fibd_vol_median_work_size(nx, ny, nz, numpass, &work_bytes));
+    FIB_CHECK(radius >= 1 && radius <= 3, FIB_ERR_INVALID, "the median's radius must be 1, 2 or 3, not %d", radius);
+    const size_t nvox = (size_t)nx * ny * nz;
+    const uintptr_t ai = reinterpret_cast<uintptr_t>(in), ao = reinterpret_cast<uintptr_t>(out);
+    FIB_CHECK(ai + 4 * nvox * nframes <= ao || ao + 4 * nvox * nframes <= ai, FIB_ERR_INVALID, "in and out must not overlap");
+    DevLease lease;
+    RC(lease.take(device, "vol_median runs on one device (FIB_DEVICE_ALL is not supported)"));
+    fib::DevBuf<char> d_work;
+    RC(d_work.alloc(work_bytes));
+    return frame_chunks(in, nvox, out, nvox, nframes, "FIBERS_MEDIAN_FRAMES", "vol_median: one input and one output frame do not fit in device memory",
+                        [&](const uint32_t *d_in, uint32_t *d_out, int nf) {
+                            for (int f = 0; f < nf; f++)
+                                RC(fibd_vol_median(reinterpret_cast<const float *>(d_in) + nvox * f, nx, ny, nz, radius, numpass,
+                                                   reinterpret_cast<float *>(d_out) + nvox * f, d_work.p, work_bytes, nullptr));
+                            return (int)FIB_OK;
+                        });
+} FIB_API_CATCH
+
+extern "C" int fib_mask_components(int device, const uint8_t *mask, int nx, int ny, int nz, int flags, int32_t *labels, uint8_t *out_mask,
+                                   fib_mask_info *info) try {
+    FIB_CHECK(mask && info, FIB_ERR_INVALID, "NULL argument");
+    size_t work_bytes = 0;
+    RC(fibd_mask_components_work_size(nx, ny, nz, &work_bytes));
+    FIB_CHECK((flags & ~(FIB_MASK_KEEP_LARGEST | FIB_MASK_FILL_HOLES)) == 0, FIB_ERR_INVALID, "mask_components: unknown flags 0x%x", flags);
+    DevLease lease;
+    RC(lease.take(device, "mask_components runs on one device (FIB_DEVICE_ALL is not supported)"));
+    const size_t nvox = (size_t)nx * ny * nz;
+    fib::DevBuf<char> d_work;
+    fib::DevBuf<uint8_t> d_mask, d_out;
+    fib::DevBuf<int32_t> d_labels;
+    fib::DevBuf<fib_mask_info> d_info;
+    RC(d_work.alloc(work_bytes));
+    RC(fib::upload(d_mask, mask, nvox));
+    if (out_mask) RC(d_out.alloc(nvox));
+    if (labels) RC(d_labels.alloc(nvox));
+    RC(d_info.alloc(1));
+    RC(fibd_mask_components(d_mask.p, nx, ny, nz, flags, labels ? d_labels.p : nullptr, out_mask ? d_out.p : nullptr, d_info.p, d_work.p,
+                            work_bytes, nullptr));
+    if (out_mask) RC(d2h(out_mask, d_out.p, nvox));
+    if (labels) RC(d2h(labels, d_labels.p, sizeof(int32_t) * nvox));
+    RC(d2h(info, d_info.p, sizeof(fib_mask_info)));
+    return FIB_OK;
+} FIB_API_CATCH
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // non-linear warps: host forms.  One device; the planar field is uploaded and packed once and stays resident for the call, the points
 // or the frames travel in chunks.  Copies block on the NULL stream, so a read-back comes behind its kernel.  The buffers are local.

@@ -115,7 +115,7 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // Environment variables.  The product library reads these names, none of which selects a kernel variant: FIBERS_ODF_FORMAT (what
 // FIB_ODF_FORMAT_DEFAULT means: fp16x2 | bf16x3 | f32 -- the format itself is a plan-creation parameter; its former spellings
 // FIBERS_ODF_GEMM=f32 / FIBERS_ODF_EXACT=1 are still honoured) and the host tier's pipeline shape (FIBERS_HOST_CHUNK, FIBERS_HOST_PACK,
-// FIBERS_COPY_THREADS, FIBERS_HOST_NT) and fib_st_recon's and fib_dwi_denoise's slab thickness (FIBERS_ST_RECON_SLAB, FIBERS_DENOISE_SLAB) and fib_vol_xform's frames per chunk (FIBERS_VOL_XFORM_FRAMES) and the chunks of fib_warp_points / fib_warp_volume (FIBERS_WARP_POINTS, FIBERS_WARP_FRAMES), through env() below.  The A/B partners of the shipped kernels
+// FIBERS_COPY_THREADS, FIBERS_HOST_NT) and fib_st_recon's and fib_dwi_denoise's slab thickness (FIBERS_ST_RECON_SLAB, FIBERS_DENOISE_SLAB) and the frames per chunk of fib_vol_xform, fib_dwi_mask and fib_vol_median (FIBERS_VOL_XFORM_FRAMES, FIBERS_MASK_FRAMES, FIBERS_MEDIAN_FRAMES) and the chunks of fib_warp_points / fib_warp_volume (FIBERS_WARP_POINTS, FIBERS_WARP_FRAMES), through env() below.  The A/B partners of the shipped kernels
 // and the knobs of the measurement tools (schedule variants, the split of an XCD's workgroups, the list unit, the phase stamps) exist
 // in the DIAGNOSTIC build only (`make stamp`: -DFIB_CLOCK_STAMP -DFIB_AB_VARIANTS -> libfibers_hip_stamp.so, which tools/ load
 // through FIBERS_HIP_LIB): ab_env() is a constant nullptr in the product.
@@ -193,5 +193,12 @@ size_t prob_work_bytes(int64_t nlines);                  // the work area of a r
 int prob_count(const ProbRun &run, void *work, size_t work_bytes, hipStream_t stream, int64_t *nlines, int64_t *npoints);
 // pass 2: the kept lines replayed into npts / seed_index / xyz (which hold at least the totals prob_count returned); asynchronous
 int prob_emit(const ProbRun &run, void *work, int32_t *npts, int64_t *seed_index, float *xyz, hipStream_t stream);
+
+// The mean of dwi_mask as fib_dwi_mask takes it (volmask.hip): nf frames [nf][nvox] on the device added, in their order, to the float64
+// sums that lie in a workspace of fibd_dwi_mask_work_size bytes (first: the sums start from zero); then the sums divided by `count`
+// and everything fibd_dwi_mask does after its mean.  b0 may be NULL; info is device memory.
+int vm_mean_add(void *work, const float *frames, int64_t nvox, int nf, bool first, hipStream_t stream);
+int vm_mask_finish(void *work, int count, int nx, int ny, int nz, const fib_mask_params *params, uint8_t *mask, float *b0, fib_mask_info *info,
+                   hipStream_t stream);
 
 }  // namespace fib

@@ -290,6 +290,65 @@ int fibd_dwi_denoise_work_size(int nx, int ny, int nz, int nvol, int patch, size
 int fibd_dwi_denoise(const float *dwi, int nx, int ny, int nz, int zin0, int nzin, int z0, int z1, int nvol, int patch, int estimator,
                      const uint8_t *mask, float *out, float *sigma, float *rank, void *work, size_t work_bytes, void *stream);
 
+/* ---- Brain mask: median-Otsu, the volume median and the components of a mask (not in the reference; this section is the definition,
+ *      DESIGN.md §5 points here, tests/mask_ref.py restates it in NumPy and the kernels are held to that bit for bit) ----
+ * Linear voxel index i = x + nx (y + ny z).
+ * Order of float32 values: by the ordered-uint key of the bit pattern b: key = ~b when the sign bit is set, else b | 0x80000000.  So
+ *   -0 < +0, NaNs sort to the two ends by their sign bit, and every comparison below, being one of keys, has a result for any pattern.
+ * Mean b0: frames is a list of frame indices (they may repeat).  b0[i] = the float64 sequential sum of the float32 samples in the
+ *   list's order, divided by the count in float64, rounded to float32 once.  The sum starts from +0, so a mean of -0 samples is +0.
+ * Median, radius r in {1, 2, 3}: the window of (x, y, z) is the (2r+1)^3 cube with every coordinate clamped into the volume (edge
+ *   replication; any dimension >= 1); the result is the element of rank floor(n / 2) (0-based) of the n = (2r+1)^3 keys.  numpass >= 0
+ *   passes, each on the output of the one before.
+ * Histogram of the filtered volume: lo, hi = its smallest and largest finite value (by key; non-finite = exponent all ones).  No finite
+ *   value, or hi == lo (as floats): the mask is all zero and info.status = 1 -- a result, not an error.  A finite v falls in bin
+ *   min(255, (int64) floor(((double) v - lo) / ((double) hi - lo) * 256.0)); non-finite voxels enter no bin and are outside the mask.
+ * Otsu on the 256 int64 counts h: for k = 0 .. 254, c0 = sum_{j<=k} h_j, s0 = sum_{j<=k} j h_j, c1 and s1 the rest; candidates with
+ *   c0 == 0 or c1 == 0 are skipped; d = s0 c1 - s1 c0 (int64, exact for nvox <= 2^27; more voxels: FIB_ERR_UNSUPPORTED);
+ *   crit = ((double) d * (double) d) / ((double) c0 * (double) c1); k* = the first maximum of crit.  A voxel is above threshold iff its
+ *   bin > k*.  info.threshold = lo + (k* + 1) (hi - lo) / 256 in float64 is for reporting; the mask never compares against it.
+ * Components: 6-connectivity over the voxels above threshold.  A component's label is 1 + the smallest linear index in it.
+ *   FIB_MASK_KEEP_LARGEST keeps the component of most voxels, ties to the smaller label.
+ * Holes: FIB_MASK_FILL_HOLES adds every 6-connected component of the complement that has no voxel on a face of the volume.
+ * Dilation: dilate >= 0 passes of the 6-neighbourhood, last.
+ * info: status (0; 1 = no threshold exists, see above; -1 = an iteration cap of the labelling was reached, which a correct run never
+ *   does), kstar (-1 with status 1), lo, hi (0 without a finite value), threshold (0 with status 1), n_above (voxels above threshold),
+ *   n_components (of those), n_kept (after the selection), n_filled (added by the holes), n_mask (the result's voxels). */
+#define FIB_MASK_KEEP_LARGEST 1
+#define FIB_MASK_FILL_HOLES 2
+typedef struct {
+    int radius, numpass;      /* the median */
+    int flags;                /* FIB_MASK_KEEP_LARGEST | FIB_MASK_FILL_HOLES */
+    int dilate;
+} fib_mask_params;
+typedef struct {
+    int32_t status, kstar;
+    float lo, hi;
+    double threshold;
+    int64_t n_above, n_components, n_kept, n_filled, n_mask;
+} fib_mask_info;
+/* Host only (no device needed): the refusals of dwi_mask -- radius outside 1..3, negative numpass or dilate, unknown flags, an empty
+ * frame list or an index outside [0, nvol): FIB_ERR_INVALID; more than 2^27 voxels: FIB_ERR_UNSUPPORTED. */
+int fib_dwi_mask_check(int nx, int ny, int nz, int nvol, const int32_t *frames, int nframes, const fib_mask_params *params);
+/* The median of a device volume: in, out float32 [nx * ny * nz], distinct buffers; numpass = 0 copies.  work: 8-byte aligned,
+ * fibd_vol_median_work_size bytes (one volume when numpass >= 2). */
+int fibd_vol_median_work_size(int nx, int ny, int nz, int numpass, size_t *bytes);
+int fibd_vol_median(const float *in, int nx, int ny, int nz, int radius, int numpass, float *out, void *work, size_t work_bytes, void *stream);
+/* Components of a device mask (uint8, nonzero = inside), then the selection and the holes as `flags` say.  out_mask (or NULL): the
+ * result as 0 / 1; labels (or NULL): int32, the labels of the result's components (0 outside).  info: 64 bytes of DEVICE memory
+ * (status, n_above = the input's voxels, n_components, n_kept, n_filled, n_mask; the rest 0), complete when the stream has run.
+ * At most 2^27 voxels. */
+int fibd_mask_components_work_size(int nx, int ny, int nz, size_t *bytes);
+int fibd_mask_components(const uint8_t *mask, int nx, int ny, int nz, int flags, int32_t *labels, uint8_t *out_mask, fib_mask_info *info,
+                         void *work, size_t work_bytes, void *stream);
+/* dwi_mask on a planar device series: frame f begins at dwi + f * frame_stride (frame_stride >= nx * ny * nz); frames is a HOST list of
+ * nframes indices into the nvol frames.  mask uint8 [nvox], b0 float32 [nvox] or NULL, info in DEVICE memory; nothing returns to the
+ * host between the steps.  Up to 64 frames are summed and finalised in one launch, longer lists frame by frame into a float64 buffer
+ * of the workspace: the same sums. */
+int fibd_dwi_mask_work_size(int nx, int ny, int nz, size_t *bytes);
+int fibd_dwi_mask(const float *dwi, int64_t frame_stride, int nvol, const int32_t *frames, int nframes, int nx, int ny, int nz,
+                  const fib_mask_params *params, uint8_t *mask, float *b0, fib_mask_info *info, void *work, size_t work_bytes, void *stream);
+
 /* gqi_rec / dsi_rec volume loop + find_peaks! + peak/qa extraction (gqi.jl:132-162,
  * dsi.jl:197-261).  odf [nvox*nvert] planar; pdf [nvox*nvol] (DSI plans only, else NULL);
  * peak[k] [nvox*3] planar, qa[k] [nvox].  `flags` is a bit set:
@@ -908,6 +967,17 @@ int fib_st_recon(int device, const float *vol, int nx, int ny, int nz, float sig
  * results do not depend on the slab thickness.  FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED. */
 int fib_dwi_denoise(int device, const float *dwi, int nx, int ny, int nz, int nvol, const uint8_t *mask, int patch, int estimator,
                     float *out, float *sigma, float *rank);
+/* host-buffer forms of the brain mask section.  fib_dwi_mask: dwi float32 [nx,ny,nz,nvol] (column-major), mask uint8 [nx,ny,nz], b0
+ * float32 [nx,ny,nz] or NULL, info in host memory.  Only the listed frames are uploaded, in chunks of what fits in half the free device
+ * memory (FIBERS_MASK_FRAMES forces the frames per chunk), and summed into a float64 buffer on the device: a series larger than the
+ * device goes through, and the result does not depend on the chunk.  fib_vol_median: in, out float32 [nx,ny,nz,nframes], every frame
+ * on its own, chunked likewise (FIBERS_MEDIAN_FRAMES).  fib_mask_components: mask uint8 (nonzero = inside); labels int32 or NULL,
+ * out_mask uint8 or NULL.  FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED. */
+int fib_dwi_mask(int device, const float *dwi, int nx, int ny, int nz, int nvol, const int32_t *frames, int nframes,
+                 const fib_mask_params *params, uint8_t *mask, float *b0, fib_mask_info *info);
+int fib_vol_median(int device, const float *in, int nx, int ny, int nz, int nframes, int radius, int numpass, float *out);
+int fib_mask_components(int device, const uint8_t *mask, int nx, int ny, int nz, int flags, int32_t *labels, uint8_t *out_mask,
+                        fib_mask_info *info);
 /* xfm_apply(xfm, point) (util.jl:385-420) on npoints float32 points [npoints][3] (x, y, z of a point adjacent, as the 3N vector the
  * reference takes).  vox2vox is ROW-major: vox2vox[4 * i + j] = xfm.vox2vox[i + 1, j + 1] (Julia passes permutedims(vox2vox)).
  * Per point, in float32 with every multiply and add rounded on its own, in the reference's order: w = 0 + m41 x + m42 y + m43 z + m44,

@@ -294,6 +294,70 @@ function dwi_denoise(dwi::MRI, mask::MRI; patch::Integer=5, estimator::Symbol=:e
   return Denoised(D, S, R)
 end
 
+# layout: fib_mask_params sizeof 16: radius@0 numpass@4 flags@8 dilate@12
+struct FibMaskParams
+  radius::Cint; numpass::Cint; flags::Cint; dilate::Cint
+end
+# layout: fib_mask_info sizeof 64: status@0 kstar@4 lo@8 hi@12 threshold@16 n_above@24 n_components@32 n_kept@40 n_filled@48 n_mask@56
+mutable struct FibMaskInfo
+  status::Int32; kstar::Int32; lo::Float32; hi::Float32; threshold::Float64
+  n_above::Int64; n_components::Int64; n_kept::Int64; n_filled::Int64; n_mask::Int64
+  FibMaskInfo() = new(0, 0, 0f0, 0f0, 0.0, 0, 0, 0, 0, 0)
+end
+mask_flags(keep_largest::Bool, fill_holes::Bool) = Cint((keep_largest ? 1 : 0) | (fill_holes ? 2 : 0))
+
+"Container for outputs of dwi_mask: the mask (UInt8), the mean of the chosen frames and the info record"
+struct BrainMask
+  mask::MRI; b0::MRI; info::FibMaskInfo
+end
+
+"dwi_mask(dwi; frames, radius, numpass, keep_largest, fill_holes, dilate) — median-Otsu brain mask (not in the reference;
+ include/fibers_hip.h).  frames are 1-based; the default is the frames of the smallest b-value (dti.jl:117), frame 1 without a b-table."
+function dwi_mask(dwi::MRI; frames::Union{Nothing,Vector{<:Integer}}=nothing, radius::Integer=2, numpass::Integer=4,
+                  keep_largest::Bool=true, fill_holes::Bool=true, dilate::Integer=0, device::Integer=0)
+  nx, ny, nz, nvol = size(dwi.vol)
+  fr = frames !== nothing ? Int32.(frames .- 1) : isempty(dwi.bval) ? Int32[0] : Int32.(findall(dwi.bval .== minimum(dwi.bval)) .- 1)
+  p = FibMaskParams(radius, numpass, mask_flags(keep_largest, fill_holes), dilate)
+  vol = dwi.vol::Array{Float32,4}
+  M = MRI(dwi, 1, UInt8); B = MRI(dwi, 1, Float32)
+  info = FibMaskInfo()
+  GC.@preserve vol fr M B fib_check(ccall((:fib_dwi_mask, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Cint, Ptr{Int32}, Cint, Ref{FibMaskParams}, Ptr{UInt8}, Ptr{Float32}, Ref{FibMaskInfo}),
+      device, vol, nx, ny, nz, nvol, fr, length(fr), p, pointer(M.vol), pointer(B.vol), info))
+  return BrainMask(M, B, info)
+end
+
+"vol_median(mri; radius, numpass) — the 3-D median of every frame, window (2 radius + 1)^3 with edge replication"
+function vol_median(mri::MRI; radius::Integer=1, numpass::Integer=1, device::Integer=0)
+  nx, ny, nz, nf = size(mri.vol)
+  vol = mri.vol::Array{Float32,4}
+  out = Array{Float32,4}(undef, nx, ny, nz, nf)
+  GC.@preserve vol out fib_check(ccall((:fib_vol_median, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float32}),
+      device, vol, nx, ny, nz, nf, radius, numpass, out))
+  D = deepcopy(mri)
+  D.vol = out
+  return D
+end
+
+"mask_components(mask; keep_largest, fill_holes, compact) — Int32 labels of the 6-connected components of mask .!= 0 (after the selection
+ and the holes); a label is 1 + the smallest 0-based linear index of its component, compact=true renumbers them 1..n in that order"
+function mask_components(mask::MRI; keep_largest::Bool=false, fill_holes::Bool=false, compact::Bool=true, device::Integer=0)
+  nx, ny, nz = size(mask.vol)[1:3]
+  m = UInt8.(view(mask.vol, :, :, :, 1) .!= 0)
+  L = MRI(mask, 1, Int32)
+  info = FibMaskInfo()
+  GC.@preserve m L fib_check(ccall((:fib_mask_components, libfibers), Cint,
+      (Cint, Ptr{UInt8}, Cint, Cint, Cint, Cint, Ptr{Int32}, Ptr{UInt8}, Ref{FibMaskInfo}),
+      device, m, nx, ny, nz, mask_flags(keep_largest, fill_holes), pointer(L.vol), C_NULL, info))
+  if compact
+    u = sort(unique(filter(!=(0), L.vol)))
+    rank = Dict(v => Int32(i) for (i, v) in enumerate(u))
+    L.vol = map(v -> v == 0 ? Int32(0) : rank[v], L.vol)
+  end
+  return L
+end
+
 "rumba_rec(dwi, mask, odf_dirs, niter, ...) — replaces rusd.jl:419-636"
 function rumba_rec(dwi::MRI, mask::MRI, odf_dirs::ODF=sphere_724, niter::Integer=600, λ_para::Float32=Float32(1.7e-3),
                    λ_perp::Float32=Float32(0.2e-3), λ_csf::Float32=Float32(3.0e-3), λ_gm::Float32=Float32(0.8e-4),
