@@ -18,6 +18,9 @@ from .denoise import Denoised, dwi_denoise  # noqa: F401
 # (the device tier of the brain mask is reached through the module: mask.dwi_mask_device, mask.vol_median_device, mask.mask_components_device)
 from . import mask  # noqa: F401
 from .mask import BrainMask, dwi_mask, mask_components, vol_median  # noqa: F401
+# (the device tier of the Gibbs-ringing removal is reached through the module: degibbs.dwi_degibbs_device)
+from . import degibbs  # noqa: F401
+from .degibbs import Degibbsed, dwi_degibbs, dwi_degibbs_check, dwi_degibbs_work_size  # noqa: F401
 from .gqi import (DSI, GQI, OdfPlan, dsi_rec, find_peaks, find_peaks_device, find_peaks_work, gqi_rec, odf_rec_device,  # noqa: F401
                   qa_normalize_device)
 from .rumba import RUMBASD, RumbaPlan, rumba_rec, rumba_rec_device  # noqa: F401

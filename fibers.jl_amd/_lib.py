@@ -60,6 +60,10 @@ class MaskInfo(C.Structure):
                 ("n_above", C.c_int64), ("n_components", C.c_int64), ("n_kept", C.c_int64), ("n_filled", C.c_int64), ("n_mask", C.c_int64)]
 
 
+class DegibbsParams(C.Structure):
+    _fields_ = [("slice_axis", C.c_int), ("nshifts", C.c_int), ("minW", C.c_int), ("maxW", C.c_int)]
+
+
 class StreamParams(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("nvec", C.c_int32),
                 ("len_min", C.c_int32), ("len_max", C.c_int32),
@@ -136,6 +140,11 @@ _PROTOS = {
     "fib_dwi_mask": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, C.POINTER(MaskParams), vp, vp, C.POINTER(MaskInfo)]),
     "fib_vol_median": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "fib_mask_components": (i32, [i32, vp, i32, i32, i32, i32, vp, vp, C.POINTER(MaskInfo)]),
+    "fib_dwi_degibbs_check": (i32, [i32, i32, i32, i32, C.POINTER(DegibbsParams)]),
+    "fib_degibbs_table": (i32, [i32, i32, vp]),
+    "fibd_dwi_degibbs_work_size": (i32, [i32, i32, i32, i32, C.POINTER(DegibbsParams), C.POINTER(C.c_uint64)]),
+    "fibd_dwi_degibbs": (i32, [vp, i32, i32, i32, i32, C.POINTER(DegibbsParams), vp, vp, vp, vp, C.c_uint64, vp]),
+    "fib_dwi_degibbs": (i32, [i32, vp, i32, i32, i32, i32, C.POINTER(DegibbsParams), vp, vp, vp]),
     "fibd_dti_last_partial_count": (i32, [vp, vp, C.POINTER(i64)]),
     "fibd_odf_rec": (i32, [vp, vp, vp, i64, vp, vp, P3, P3, vp, i32, vp]),
     "fibd_qa_normalize": (i32, [P3, i64, f32, vp]),

@@ -869,8 +869,82 @@ extern "C" int fib_mask_components(int device, const uint8_t *mask, int nx, int 
     return FIB_OK;
 } FIB_API_CATCH
 
+// ---- Gibbs-ringing removal (degibbs.hip).  Slices are independent: a chunk is whole frames, or slices [a0, a1) of one frame, and the
+// device entry takes it as a volume of its own whose slice axis is that short.  A slab of slices is a run of `height` pieces of `width`
+// elements, `pitch` apart in the host volume and back to back on the device (slice axis 2: one piece).
+namespace {
+struct SliceSlab { size_t off, width, height, pitch; };
+SliceSlab slice_slab(int axis, int nx, int ny, int nz, int a0, int a1) {
+    const size_t s = (size_t)(a1 - a0), plane = (size_t)nx * ny;
+    if (axis == 2) return SliceSlab{plane * a0, plane * s, 1, plane * s};
+    if (axis == 1) return SliceSlab{(size_t)nx * a0, (size_t)nx * s, (size_t)nz, plane};
+    return SliceSlab{(size_t)a0, s, (size_t)ny * nz, (size_t)nx};
+}
+int slab_copy(void *dev, void *host, const SliceSlab &b, size_t es, bool to_device) {
+    char *h = static_cast<char *>(host) + b.off * es;
+    if (b.height == 1) return to_device ? h2d(dev, h, b.width * es) : d2h(h, dev, b.width * es);
+    if (to_device) FIB_HIP(hipMemcpy2D(dev, b.width * es, h, b.pitch * es, b.width * es, b.height, hipMemcpyHostToDevice));
+    else FIB_HIP(hipMemcpy2D(h, b.pitch * es, dev, b.width * es, b.width * es, b.height, hipMemcpyDeviceToHost));
+    return FIB_OK;
+}
+}  // namespace
+
+extern "C" int fib_dwi_degibbs(int device, const float *dwi, int nx, int ny, int nz, int nvol, const fib_degibbs_params *params, float *out,
+                               int8_t *shift_u, int8_t *shift_v) try {
+    FIB_CHECK(dwi && out, FIB_ERR_INVALID, "NULL argument");
+    RC(fib_dwi_degibbs_check(nx, ny, nz, nvol, params));
+    const fib_degibbs_params dflt = FIB_DEGIBBS_PARAMS_DEFAULT, prm = params ? *params : dflt;
+    const size_t nvox = (size_t)nx * ny * nz;
+    const uintptr_t ai = reinterpret_cast<uintptr_t>(dwi), ao = reinterpret_cast<uintptr_t>(out);
+    FIB_CHECK(ai + 4 * nvox * nvol <= ao || ao + 4 * nvox * nvol <= ai, FIB_ERR_INVALID, "dwi_degibbs: dwi and out must not overlap (there is no in-place form)");
+    DevLease lease;
+    RC(lease.take(device, "dwi_degibbs runs on one device (FIB_DEVICE_ALL is not supported)"));
+    const int axis = prm.slice_axis, dims[3] = {nx, ny, nz}, ns = dims[axis];
+    const size_t slice = nvox / ns;                        // voxels of a slice
+    int64_t per = 0;                                       // slices per chunk
+    if (const char *e = fib::env("FIBERS_DEGIBBS_SLICES")) per = atoll(e);
+    if (per <= 0) {
+        size_t fr = 0, tot = 0, wb = 0;
+        FIB_HIP(hipMemGetInfo(&fr, &tot));
+        RC(fibd_dwi_degibbs_work_size(nx, ny, nz, nvol, &prm, &wb));        // (the whole series': no chunk needs more)
+        // a slice costs its float32 input and output and two int8 planes; the workspace comes off first, twice, as the plan is for half
+        per = (int64_t)((fr > 2 * wb ? fr - 2 * wb : 0) / 2 / (10 * slice));
+        FIB_CHECK(per >= 1, FIB_ERR_NOMEM, "dwi_degibbs: one slice does not fit in device memory beside the workspace");
+    }
+    const int nfc = per >= ns ? (int)std::min<int64_t>(per / ns, nvol) : 1, nsc = per >= ns ? ns : (int)per;      // frames and slices of a chunk
+    int cd[3] = {nx, ny, nz};
+    cd[axis] = nsc;
+    size_t work_bytes = 0;
+    RC(fibd_dwi_degibbs_work_size(cd[0], cd[1], cd[2], nfc, &prm, &work_bytes));
+    const size_t cvox = slice * nsc;
+    fib::DevBuf<float> d_in, d_out;
+    fib::DevBuf<int8_t> d_su, d_sv;
+    fib::DevBuf<char> d_work;
+    RC(d_in.alloc(cvox * nfc));
+    RC(d_out.alloc(cvox * nfc));
+    if (shift_u) RC(d_su.alloc(cvox * nfc));
+    if (shift_v) RC(d_sv.alloc(cvox * nfc));
+    RC(d_work.alloc(work_bytes));
+    for (int f0 = 0; f0 < nvol; f0 += nfc)
+        for (int a0 = 0; a0 < ns; a0 += nsc) {
+            const int nf = std::min(nfc, nvol - f0), a1 = std::min(ns, a0 + nsc);
+            const SliceSlab b = slice_slab(axis, nx, ny, nz, a0, a1);
+            const size_t n = slice * (a1 - a0);
+            cd[axis] = a1 - a0;
+            for (int f = 0; f < nf; f++) RC(slab_copy(d_in.p + n * f, const_cast<float *>(dwi) + nvox * (f0 + f), b, 4, true));
+            RC(fibd_dwi_degibbs(d_in.p, cd[0], cd[1], cd[2], nf, &prm, d_out.p, shift_u ? d_su.p : nullptr, shift_v ? d_sv.p : nullptr, d_work.p,
+                                work_bytes, nullptr));
+            for (int f = 0; f < nf; f++) {                 // (blocking copies on the NULL stream: behind the kernels)
+                RC(slab_copy(d_out.p + n * f, out + nvox * (f0 + f), b, 4, false));
+                if (shift_u) RC(slab_copy(d_su.p + n * f, shift_u + nvox * (f0 + f), b, 1, false));
+                if (shift_v) RC(slab_copy(d_sv.p + n * f, shift_v + nvox * (f0 + f), b, 1, false));
+            }
+        }
+    return FIB_OK;
+} FIB_API_CATCH
+
 // ------------------------------------------------------------------------------------------------------------------------------
-// non-linear warps: host forms.  One device; the planar field is uploaded and packed once and stays resident for the call, the points
+// non-linear warps: host forms. One device; the planar field is uploaded and packed once and stays resident for the call, the points
 // or the frames travel in chunks.  Copies block on the NULL stream, so a read-back comes behind its kernel.  The buffers are local.
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {

@@ -115,7 +115,7 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // Environment variables.  The product library reads these names, none of which selects a kernel variant: FIBERS_ODF_FORMAT (what
 // FIB_ODF_FORMAT_DEFAULT means: fp16x2 | bf16x3 | f32 -- the format itself is a plan-creation parameter; its former spellings
 // FIBERS_ODF_GEMM=f32 / FIBERS_ODF_EXACT=1 are still honoured) and the host tier's pipeline shape (FIBERS_HOST_CHUNK, FIBERS_HOST_PACK,
-// FIBERS_COPY_THREADS, FIBERS_HOST_NT) and fib_st_recon's and fib_dwi_denoise's slab thickness (FIBERS_ST_RECON_SLAB, FIBERS_DENOISE_SLAB) and the frames per chunk of fib_vol_xform, fib_dwi_mask and fib_vol_median (FIBERS_VOL_XFORM_FRAMES, FIBERS_MASK_FRAMES, FIBERS_MEDIAN_FRAMES) and the chunks of fib_warp_points / fib_warp_volume (FIBERS_WARP_POINTS, FIBERS_WARP_FRAMES), through env() below.  The A/B partners of the shipped kernels
+// FIBERS_COPY_THREADS, FIBERS_HOST_NT) and fib_st_recon's and fib_dwi_denoise's slab thickness (FIBERS_ST_RECON_SLAB, FIBERS_DENOISE_SLAB) and the frames per chunk of fib_vol_xform, fib_dwi_mask and fib_vol_median (FIBERS_VOL_XFORM_FRAMES, FIBERS_MASK_FRAMES, FIBERS_MEDIAN_FRAMES) and the chunks of fib_warp_points / fib_warp_volume (FIBERS_WARP_POINTS, FIBERS_WARP_FRAMES) and the slices per chunk of fib_dwi_degibbs (FIBERS_DEGIBBS_SLICES), through env() below.  The A/B partners of the shipped kernels
 // and the knobs of the measurement tools (schedule variants, the split of an XCD's workgroups, the list unit, the phase stamps) exist
 // in the DIAGNOSTIC build only (`make stamp`: -DFIB_CLOCK_STAMP -DFIB_AB_VARIANTS -> libfibers_hip_stamp.so, which tools/ load
 // through FIBERS_HIP_LIB): ab_env() is a constant nullptr in the product.
@@ -200,5 +200,10 @@ int prob_emit(const ProbRun &run, void *work, int32_t *npts, int64_t *seed_index
 int vm_mean_add(void *work, const float *frames, int64_t nvox, int nf, bool first, hipStream_t stream);
 int vm_mask_finish(void *work, int count, int nx, int ny, int nz, const fib_mask_params *params, uint8_t *mask, float *b0, fib_mask_info *info,
                    hipStream_t stream);
+
+// Gibbs-ringing removal (include/fibers_hip.h; setup.cpp): the circulant table of a row length n, D[(j - 1) * n + t] = D(t + s_j) for the
+// 2K shifted candidates j = 1 .. 2K; the (cos, sin) pairs of 2 pi k / n and the weights c[p] = 1 + cos(2 pi p / n) (0 where 2 p == n)
+void host_degibbs_table(int n, int K, double *D);
+void host_degibbs_twiddles(int n, double *cs, double *c);
 
 }  // namespace fib

@@ -453,3 +453,44 @@ extern "C" int fib_dki_design(const float *bval, const float *bvec, int nvol, fl
               "(the design has rank %d of 22 on %d frames)", r, nvol);
     return FIB_OK;
 } FIB_API_CATCH
+
+// ---- Gibbs-ringing removal (include/fibers_hip.h): the tables of a row length n ---------------------------------------------------
+namespace fib {
+// D[(j - 1) * n + t] = D(t + s_j), j = 1 .. 2K, t = 0 .. n - 1, with D(t) = (1 + 2 sum_{k=1..h} cos(2 pi k t / n)) / n, h = (n - 1) / 2,
+// s_j = j / (2K + 1) for j <= K and -(j - K) / (2K + 1) after.  The argument k (t J + i) mod (n J) is reduced in integers, so every
+// cosine is taken of an angle in [0, 2 pi); the sum runs in long double and is rounded to float64 once.
+void host_degibbs_table(int n, int K, double *D) {
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    const int64_t J = 2 * (int64_t)K + 1, period = (int64_t)n * J;
+    const int h = (n - 1) / 2;
+    std::vector<long double> c((size_t)period);                    // cos(2 pi a / (n J)): every angle the sums meet
+    for (int64_t a = 0; a < period; a++) c[(size_t)a] = cosl(two_pi * (long double)a / (long double)period);
+    for (int j = 1; j <= 2 * K; j++) {
+        const int64_t i = j <= K ? j : -(int64_t)(j - K);          // the shift in units of 1 / J
+        for (int t = 0; t < n; t++) {
+            const int64_t a = (((int64_t)t * J + i) % period + period) % period;
+            long double s = 0.0L;
+            for (int k = h; k >= 1; k--) s += c[(size_t)((a * k) % period)];
+            D[(size_t)(j - 1) * n + t] = (double)((1.0L + 2.0L * s) / (long double)n);
+        }
+    }
+}
+// cos and sin of 2 pi k / n, k = 0 .. n - 1, as (cos, sin) pairs, and the weights c[p] = 1 + cos(2 pi p / n), exactly 0 where 2 p == n
+void host_degibbs_twiddles(int n, double *cs, double *c) {
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    for (int k = 0; k < n; k++) {
+        const long double a = two_pi * (long double)k / (long double)n;
+        cs[2 * k] = (double)cosl(a);
+        cs[2 * k + 1] = (double)sinl(a);
+        c[k] = 2 * k == n ? 0.0 : 1.0 + cs[2 * k];
+    }
+}
+}  // namespace fib
+
+extern "C" int fib_degibbs_table(int n, int nshifts, double *table) try {
+    FIB_CHECK(table, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(n >= 1 && n <= FIB_DEGIBBS_MAX_SIZE, FIB_ERR_INVALID, "degibbs_table: the row length must lie in 1 .. %d, not %d", FIB_DEGIBBS_MAX_SIZE, n);
+    FIB_CHECK(nshifts >= 1 && nshifts <= 32, FIB_ERR_INVALID, "dwi_degibbs: nshifts must lie in 1 .. 32, not %d", nshifts);
+    fib::host_degibbs_table(n, nshifts, table);
+    return FIB_OK;
+} FIB_API_CATCH

@@ -349,6 +349,48 @@ int fibd_dwi_mask_work_size(int nx, int ny, int nz, size_t *bytes);
 int fibd_dwi_mask(const float *dwi, int64_t frame_stride, int nvol, const int32_t *frames, int nframes, int nx, int ny, int nz,
                   const fib_mask_params *params, uint8_t *mask, float *b0, fib_mask_info *info, void *work, size_t work_bytes, void *stream);
 
+/* ---- Gibbs-ringing removal: local subvoxel shifts (not in the reference; after Kellner et al. 2016, the method of MRtrix's mrdegibbs
+ *      and dipy's gibbs_removal; this section is the definition, DESIGN.md §5 points here and tests/degibbs_ref.py restates it in
+ *      float64 by two routes.  Conformity to either tool bit for bit is not claimed) ----
+ * dwi: float32 [N][nvox], planar, x fastest.  slice_axis in {0, 1, 2} names the axis across the slices; the two other axes, in
+ *   ascending order, are the in-plane axes u and v of sizes nu and nv.  nshifts K, 1 <= K <= 32; windows 1 <= minW <= maxW <= 6.
+ *   Each in-plane size must be >= 2 maxW + 3 (FIB_ERR_INVALID) and <= FIB_DEGIBBS_MAX_SIZE (FIB_ERR_UNSUPPORTED, the limit in the
+ *   message).  There is no mask: the method works on whole slices, and slices and frames are independent of each other.
+ * Everything below is float64 on the float32 samples; the result is rounded to float32 once.  No fused contraction is prescribed.
+ * Per slice a[u][v]:
+ *   1. A = DFT2(a), A[p][q] = sum a[u][v] e^{-2 pi i (p u / nu + q v / nv)}.
+ *   2. cu[p] = 1 + cos(2 pi p / nu), and exactly 0 when 2 p == nu; cv[q] likewise.
+ *   3. Gu = cv / (cu + cv), Gv = cu / (cu + cv); both are 0 in the bin where 2 p == nu and 2 q == nv (decided by the integer test).
+ *   4. au = Re IDFT2(A Gu), av = Re IDFT2(A Gv): au still rings along u only, av along v only.
+ *   5. result = unring(au along u) + unring(av along v).
+ * unring of one row r[0 .. n-1], indices circular.  Candidates, J = 2 K + 1: s_0 = 0, s_j = j / J for j = 1 .. K, s_{K+j} = -j / J for
+ *   j = 1 .. K.  r_0 = r; for j >= 1, r_j[l] = sum_m r[m] D(l - m + s_j) with D(t) = (1 / n) (1 + 2 sum_{k=1..h} cos(2 pi k t / n)),
+ *   h = floor((n - 1) / 2): the band-limited row sampled at l + s_j, the Nyquist term of an even n dropped.
+ *   d_j[l] = |r_j[l+1] - r_j[l]|; L_j[l] = sum_{w=minW..maxW} d_j[l-w-1]; R_j[l] = sum_{w=minW..maxW} d_j[l+w], both sequential in
+ *   ascending w; t_j[l] = min(L_j[l], R_j[l]); j*(l) = the first j, in the order above, that attains min_j t_j[l].
+ *   Output, s = s_{j*}: s > 0: r_{j*}[l] (1 - s) + r_{j*}[l-1] s; otherwise r_{j*}[l] (1 + s) - r_{j*}[l+1] s.  j* = 0 returns r[l].
+ * Consequences: an all-zero slice returns exact zeros (every candidate ties at 0 and j* = 0).  A slice that holds a non-finite sample
+ *   has an unspecified result; the call still returns FIB_OK and every other slice is unaffected.
+ * shift_u, shift_v (int8 [N][nvox], or NULL): j* of the search along u and along v, the diagnostic that lets the choice be checked. */
+#define FIB_DEGIBBS_MAX_SIZE 256
+typedef struct {
+    int slice_axis;           /* 0, 1 or 2: the axis across the slices */
+    int nshifts;              /* K */
+    int minW, maxW;
+} fib_degibbs_params;
+#define FIB_DEGIBBS_PARAMS_DEFAULT { 2, 20, 1, 3 }
+/* Host only (no device needed): the refusals above, non-positive dimensions and nvol < 1 (FIB_ERR_INVALID).  params NULL: the default. */
+int fib_dwi_degibbs_check(int nx, int ny, int nz, int nvol, const fib_degibbs_params *params);
+/* Host only: the circulant table of a row length n (1 .. FIB_DEGIBBS_MAX_SIZE), float64 [2 nshifts][n]: table[(j - 1) n + t] =
+ * D(t + s_j), t = 0 .. n - 1, summed in extended precision and rounded once.  The kernels read this table. */
+int fib_degibbs_table(int n, int nshifts, double *table);
+/* The device entry: dwi, out float32 [nvol][nvox] on the device, distinct buffers (out == dwi, or any overlap: FIB_ERR_INVALID);
+ * shift_u, shift_v int8 [nvol][nvox] or NULL.  work: 8-byte aligned, fibd_dwi_degibbs_work_size bytes (the tables and the float64
+ * planes of a batch of slices; the batch does not change the result).  Asynchronous on `stream`. */
+int fibd_dwi_degibbs_work_size(int nx, int ny, int nz, int nvol, const fib_degibbs_params *params, size_t *bytes);
+int fibd_dwi_degibbs(const float *dwi, int nx, int ny, int nz, int nvol, const fib_degibbs_params *params, float *out, int8_t *shift_u,
+                     int8_t *shift_v, void *work, size_t work_bytes, void *stream);
+
 /* gqi_rec / dsi_rec volume loop + find_peaks! + peak/qa extraction (gqi.jl:132-162,
  * dsi.jl:197-261).  odf [nvox*nvert] planar; pdf [nvox*nvol] (DSI plans only, else NULL);
  * peak[k] [nvox*3] planar, qa[k] [nvox].  `flags` is a bit set:
@@ -978,6 +1020,12 @@ int fib_dwi_mask(int device, const float *dwi, int nx, int ny, int nz, int nvol,
 int fib_vol_median(int device, const float *in, int nx, int ny, int nz, int nframes, int radius, int numpass, float *out);
 int fib_mask_components(int device, const uint8_t *mask, int nx, int ny, int nz, int flags, int32_t *labels, uint8_t *out_mask,
                         fib_mask_info *info);
+/* host-buffer form of the Gibbs-ringing removal: dwi, out float32 [nx,ny,nz,nvol] (column-major; overlapping buffers: FIB_ERR_INVALID),
+ * shift_u, shift_v int8 of that shape or NULL.  Slices are independent, so the series travels in chunks of whole slices: whole frames
+ * where more than one fits in half the free device memory, else slabs of slices of one frame (FIBERS_DEGIBBS_SLICES forces the slices
+ * per chunk); the result does not depend on the chunk.  FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED. */
+int fib_dwi_degibbs(int device, const float *dwi, int nx, int ny, int nz, int nvol, const fib_degibbs_params *params, float *out,
+                    int8_t *shift_u, int8_t *shift_v);
 /* xfm_apply(xfm, point) (util.jl:385-420) on npoints float32 points [npoints][3] (x, y, z of a point adjacent, as the 3N vector the
  * reference takes).  vox2vox is ROW-major: vox2vox[4 * i + j] = xfm.vox2vox[i + 1, j + 1] (Julia passes permutedims(vox2vox)).
  * Per point, in float32 with every multiply and add rounded on its own, in the reference's order: w = 0 + m41 x + m42 y + m43 z + m44,

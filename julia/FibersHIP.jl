@@ -340,6 +340,35 @@ function vol_median(mri::MRI; radius::Integer=1, numpass::Integer=1, device::Int
   return D
 end
 
+# layout: fib_degibbs_params sizeof 16: slice_axis@0 nshifts@4 minW@8 maxW@12
+struct FibDegibbsParams
+  slice_axis::Cint; nshifts::Cint; minW::Cint; maxW::Cint
+end
+
+"Container for outputs of dwi_degibbs: the unrung series and, with shifts=true, the chosen candidates along the two in-plane axes"
+struct Degibbsed
+  dwi::MRI; shift_u::Union{Nothing,Array{Int8,4}}; shift_v::Union{Nothing,Array{Int8,4}}
+end
+
+"dwi_degibbs(dwi; slice_axis, nshifts, min_w, max_w, shifts) — Gibbs-ringing removal by local subvoxel shifts (not in the reference;
+ include/fibers_hip.h).  slice_axis is 1-based (3: slices across z); 1 <= nshifts <= 32, 1 <= min_w <= max_w <= 6."
+function dwi_degibbs(dwi::MRI; slice_axis::Integer=3, nshifts::Integer=20, min_w::Integer=1, max_w::Integer=3, shifts::Bool=false,
+                     device::Integer=0)
+  nx, ny, nz, nvol = size(dwi.vol)
+  p = FibDegibbsParams(slice_axis - 1, nshifts, min_w, max_w)
+  fib_check(ccall((:fib_dwi_degibbs_check, libfibers), Cint, (Cint, Cint, Cint, Cint, Ref{FibDegibbsParams}), nx, ny, nz, nvol, p))
+  vol = dwi.vol::Array{Float32,4}
+  out = Array{Float32,4}(undef, nx, ny, nz, nvol)
+  su = shifts ? Array{Int8,4}(undef, nx, ny, nz, nvol) : nothing
+  sv = shifts ? Array{Int8,4}(undef, nx, ny, nz, nvol) : nothing
+  GC.@preserve vol out su sv fib_check(ccall((:fib_dwi_degibbs, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Cint, Ref{FibDegibbsParams}, Ptr{Float32}, Ptr{Int8}, Ptr{Int8}),
+      device, vol, nx, ny, nz, nvol, p, out, shifts ? pointer(su) : C_NULL, shifts ? pointer(sv) : C_NULL))
+  D = deepcopy(dwi)
+  D.vol = out
+  return Degibbsed(D, su, sv)
+end
+
 "mask_components(mask; keep_largest, fill_holes, compact) — Int32 labels of the 6-connected components of mask .!= 0 (after the selection
  and the holes); a label is 1 + the smallest 0-based linear index of its component, compact=true renumbers them 1..n in that order"
 function mask_components(mask::MRI; keep_largest::Bool=false, fill_holes::Bool=false, compact::Bool=true, device::Integer=0)
