@@ -40,6 +40,10 @@ from .tractsel import (Connectome, str_connectome, str_connectome_device, str_ga
 from .bundle import (Bundles, str_assign_device, str_bundles, str_centroids, str_centroids_device, str_profile, str_resample,  # noqa: F401
                      str_resample_device)
 from .volxform import mri_xform, vol_xform_device, vol_xform_matrix, xfm_header  # noqa: F401
+# (the device tier of the registration is reached through the module: register.reg_hist_device, register.vol_halve_device,
+# register.vol_range_device, register.mri_register_device)
+from . import register  # noqa: F401
+from .register import Moco, Registration, dwi_moco, mri_register  # noqa: F401
 # (the device tier of prob_stream is reached through the module: probtrack.prob_table_device, probtrack.prob_stream_device)
 from . import probtrack  # noqa: F401
 from .probtrack import ProbPlan, prob_row_pitch, prob_stream, prob_work_size  # noqa: F401

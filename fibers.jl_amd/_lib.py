@@ -172,6 +172,21 @@ _PROTOS = {
     "fib_warp_points": (i32, [i32, vp, i32, i32, i32, M16, M16, M16, vp, vp, i64]),
     "fib_warp_volume": (i32, [i32, vp, i32, i32, i32, M16, M16, M16, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32]),
     "fib_warp_invert": (i32, [i32, vp, i32, i32, i32, M16, M16, i32, vp, vp, i32, i32, i32]),
+    "fibd_vol_halve": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "fibd_vol_range": (i32, [vp, i64, i32, i32, vp, vp]),
+    "fibd_reg_hist_work_size": (i32, [i32, C.POINTER(C.c_uint64)]),
+    "fibd_reg_hist": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, C.c_uint64, vp]),
+    "fib_reg_levels": (i32, [vp, vp, C.POINTER(i32)]),
+    "fib_reg_matrix": (i32, [vp, i32, M16, vp, M16, i32, vp, vp]),
+    "fib_reg_nmi": (i32, [vp, i32, i64, C.c_double, C.POINTER(C.c_double)]),
+    "fib_reg_search_create": (i32, [i32, vp, vp, M16, vp, M16, i32, i32, i32, C.c_double, vp, C.POINTER(vp)]),
+    "fib_reg_search_destroy": (None, [vp]),
+    "fib_reg_search_jobs": (i32, [vp, C.POINTER(i32), C.POINTER(i32), vp]),
+    "fib_reg_search_feed": (i32, [vp, vp, i32, i64]),
+    "fib_reg_search_result": (i32, [vp, vp, C.POINTER(C.c_double), C.POINTER(i32), vp, i32]),
+    "fibd_reg_run_work_size": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_uint64)]),
+    "fibd_reg_run": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, C.c_uint64, vp]),
+    "fib_mri_register": (i32, [i32, vp, vp, M16, i32, vp, vp, vp, M16, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, i32, vp]),
     "fibd_str_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
     "fibd_str_density": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, C.c_uint64, vp]),
     "fibd_str_sample": (i32, [vp, i64, vp, i32, i32, i32, i32, f32, vp, vp]),

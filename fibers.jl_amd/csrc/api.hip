@@ -1022,6 +1022,57 @@ extern "C" int fib_warp_invert(int device, const float *disp, int nx, int ny, in
 } FIB_API_CATCH
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// registration: the host form.  One device; both volumes, the pyramids and (for dwi_moco) the resampled series stay on the device, the
+// searches are the host state machines of setup.cpp and fibd_reg_run moves histograms between the two.
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_mri_register(int device, const float *moving, const int32_t moving_size[3], const float moving_vox2ras[16], int nframes,
+                                const float *fixed, const int32_t fixed_size[3], const float fixed_res[3], const float fixed_vox2ras[16], int dof,
+                                int nbins, int levels, int halvings, int maxit, double min_overlap, double *theta, double *cost, int *niter,
+                                double *trace, int trace_rows, float *resampled) try {
+    FIB_CHECK(moving && moving_size && moving_vox2ras && fixed && fixed_size && fixed_res && fixed_vox2ras && theta, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nframes > 0, FIB_ERR_INVALID, "nframes must be positive");
+    FIB_CHECK(trace_rows >= 0 && (trace || trace_rows == 0), FIB_ERR_INVALID, "trace_rows rows need a trace buffer");
+    struct Searches {                                       // (the refusals of fib_reg_search_create come before the device is touched)
+        std::vector<fib_reg_search *> h;
+        ~Searches() { for (auto *s : h) fib_reg_search_destroy(s); }
+    } searches;
+    for (int f = 0; f < nframes; f++) {
+        fib_reg_search *s = nullptr;
+        RC(fib_reg_search_create(dof, fixed_size, fixed_res, fixed_vox2ras, moving_size, moving_vox2ras, levels, halvings, maxit, min_overlap, nullptr, &s));
+        searches.h.push_back(s);
+    }
+    if (levels == 0) RC(fib_reg_levels(fixed_size, moving_size, &levels));
+    size_t work_bytes = 0;
+    RC(fibd_reg_run_work_size(fixed_size, moving_size, nframes, nframes, levels, nbins, &work_bytes));
+    DevLease lease;
+    RC(lease.take(device, "mri_register runs on one device (FIB_DEVICE_ALL is not supported)"));
+    const size_t nvf = (size_t)fixed_size[0] * fixed_size[1] * fixed_size[2], nvm = (size_t)moving_size[0] * moving_size[1] * moving_size[2];
+    fib::DevBuf<float> d_fixed, d_moving, d_out;
+    fib::DevBuf<char> d_work;
+    RC(fib::upload(d_fixed, fixed, nvf));
+    RC(fib::upload(d_moving, moving, nvm * nframes));
+    RC(d_work.alloc(work_bytes));
+    std::vector<int32_t> frames((size_t)nframes);
+    for (int f = 0; f < nframes; f++) frames[f] = f;
+    RC(fibd_reg_run(searches.h.data(), frames.data(), nframes, d_fixed.p, fixed_size, d_moving.p, moving_size, nframes, levels, nbins, d_work.p,
+                    work_bytes, nullptr));
+    for (int f = 0; f < nframes; f++)
+        RC(fib_reg_search_result(searches.h[f], theta + 12 * (size_t)f, cost ? cost + f : nullptr, niter ? niter + f : nullptr,
+                                 trace ? trace + (size_t)FIB_REG_TRACE_ROW * trace_rows * f : nullptr, trace_rows));
+    if (!resampled) return FIB_OK;
+    // every frame through its own final level-0 matrix onto the fixed grid: trilinear, 0 outside
+    RC(d_out.alloc(nvf * nframes));
+    for (int f = 0; f < nframes; f++) {
+        float M[16];
+        RC(fib_reg_matrix(theta + 12 * (size_t)f, 12, fixed_vox2ras, fixed_size, moving_vox2ras, 0, M, nullptr));
+        RC(fibd_vol_xform(M, d_moving.p + nvm * f, moving_size[0], moving_size[1], moving_size[2], 1, FIB_VOL_TRILINEAR, 0, d_out.p + nvf * f,
+                          fixed_size[0], fixed_size[1], fixed_size[2], nullptr));
+    }
+    RC(d2h(resampled, d_out.p, sizeof(float) * nvf * nframes));
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // tract maps: host forms.  One device; the points travel in chunks cut at line boundaries, the volume stays on the device.
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {

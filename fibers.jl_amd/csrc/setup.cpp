@@ -2,6 +2,7 @@
 //   DTIwork/ADCwork  dti.jl:39-84,101-155   -> host_dti_design + host_pinv
 //   GQIwork          gqi.jl:32-82           -> host_gqi_matrix + host_neighbours
 //   DSIwork          dsi.jl:41-143          -> host_dsi_matrix (+ the linear per-voxel chain dsi.jl:204-242)
+//   Registration (not in the reference; include/fibers_hip.h): fib_reg_matrix, fib_reg_nmi and the pattern search fib_reg_search_*
 // Nothing here runs per voxel; tables are built in float64 where the reference uses LAPACK/FFTW
 // float32 routines and rounded once to float32.
 #include <algorithm>
@@ -492,5 +493,281 @@ extern "C" int fib_degibbs_table(int n, int nshifts, double *table) try {
     FIB_CHECK(n >= 1 && n <= FIB_DEGIBBS_MAX_SIZE, FIB_ERR_INVALID, "degibbs_table: the row length must lie in 1 .. %d, not %d", FIB_DEGIBBS_MAX_SIZE, n);
     FIB_CHECK(nshifts >= 1 && nshifts <= 32, FIB_ERR_INVALID, "dwi_degibbs: nshifts must lie in 1 .. 32, not %d", nshifts);
     fib::host_degibbs_table(n, nshifts, table);
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ---- Registration (include/fibers_hip.h): the matrices, the cost and the pattern search, in float64 on the host ---------------------
+namespace {
+
+using M4 = double[16];
+
+void m4_mul(const double *a, const double *b, double *c) {
+    double r[16];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double s = 0;
+            for (int k = 0; k < 4; k++) s += a[4 * i + k] * b[4 * k + j];
+            r[4 * i + j] = s;
+        }
+    memcpy(c, r, sizeof r);
+}
+
+bool m4_inv(const double *a, double *out) {                    // Gauss-Jordan with partial pivoting
+    double w[4][8];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) { w[i][j] = a[4 * i + j]; w[i][4 + j] = i == j; }
+    for (int c = 0; c < 4; c++) {
+        int p = c;
+        for (int r = c + 1; r < 4; r++) if (std::fabs(w[r][c]) > std::fabs(w[p][c])) p = r;
+        if (!(std::fabs(w[p][c]) > 0) || !std::isfinite(w[p][c])) return false;
+        if (p != c) for (int j = 0; j < 8; j++) std::swap(w[p][j], w[c][j]);
+        const double d = w[c][c];
+        for (int j = 0; j < 8; j++) w[c][j] /= d;
+        for (int r = 0; r < 4; r++) {
+            if (r == c) continue;
+            const double f = w[r][c];
+            if (f != 0) for (int j = 0; j < 8; j++) w[r][j] -= f * w[c][j];
+        }
+    }
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) out[4 * i + j] = w[i][4 + j];
+    return true;
+}
+
+void m3_mul(const double a[9], const double b[9], double c[9]) {
+    double r[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) r[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+    memcpy(c, r, sizeof r);
+}
+
+// G(theta) = C A C^-1 with A = [Rz Ry Rx Sh S | t] and c = V_fix (n - 1) / 2: fixed RAS -> moving RAS
+void reg_G(const double *theta, int dof, const float *Vf, const int32_t *size, double *G) {
+    double th[12] = {0};
+    for (int i = 0; i < dof; i++) th[i] = theta[i];
+    const double d2r = M_PI / 180.0, rx = th[3] * d2r, ry = th[4] * d2r, rz = th[5] * d2r;
+    const double Rx[9] = {1, 0, 0, 0, std::cos(rx), -std::sin(rx), 0, std::sin(rx), std::cos(rx)};
+    const double Ry[9] = {std::cos(ry), 0, std::sin(ry), 0, 1, 0, -std::sin(ry), 0, std::cos(ry)};
+    const double Rz[9] = {std::cos(rz), -std::sin(rz), 0, std::sin(rz), std::cos(rz), 0, 0, 0, 1};
+    const double Sh[9] = {1, th[9], th[10], 0, 1, th[11], 0, 0, 1};
+    const double S[9] = {std::exp(th[6]), 0, 0, 0, std::exp(th[7]), 0, 0, 0, std::exp(th[8])};
+    double L[9];
+    m3_mul(Rz, Ry, L); m3_mul(L, Rx, L); m3_mul(L, Sh, L); m3_mul(L, S, L);
+    double c[3];
+    for (int i = 0; i < 3; i++) {
+        c[i] = (double)Vf[4 * i + 3];
+        for (int j = 0; j < 3; j++) c[i] += (double)Vf[4 * i + j] * (((double)size[j] - 1.0) / 2.0);
+    }
+    for (int i = 0; i < 16; i++) G[i] = (i % 5 == 0);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) G[4 * i + j] = L[3 * i + j];
+        G[4 * i + 3] = c[i] + th[i] - (L[3 * i] * c[0] + L[3 * i + 1] * c[1] + L[3 * i + 2] * c[2]);
+    }
+}
+
+// out2in of a level: float32(inv(V_mov D_l) G (V_fix D_l)); D_l = [2^l I | (2^l - 1) / 2]
+bool reg_out2in(const double *G, const float *Vf, const float *Vm, int level, float *out) {
+    double D[16], A[16], B[16], Ai[16], vf[16], vm[16];
+    for (int i = 0; i < 16; i++) { D[i] = 0; vf[i] = Vf[i]; vm[i] = Vm[i]; }
+    const double s = std::ldexp(1.0, level);
+    D[0] = D[5] = D[10] = s; D[15] = 1;
+    D[3] = D[7] = D[11] = (s - 1.0) / 2.0;
+    m4_mul(vm, D, A);
+    m4_mul(vf, D, B);
+    if (!m4_inv(A, Ai)) return false;
+    m4_mul(Ai, G, A);
+    m4_mul(A, B, A);
+    for (int i = 0; i < 16; i++) out[i] = (float)A[i];
+    return true;
+}
+
+double reg_entropy(const uint64_t *c, int n, double N) {      // ln N - (sum c ln c) / N over the non-zero cells, in their order
+    double s = 0;
+    for (int i = 0; i < n; i++) if (c[i]) s += (double)c[i] * std::log((double)c[i]);
+    return std::log(N) - s / N;
+}
+
+double reg_nmi(const uint32_t *h, int nb, int64_t nfinite, double min_overlap) {
+    const double ninf = -HUGE_VAL;
+    std::vector<uint64_t> rows((size_t)nb, 0), cols((size_t)nb, 0), cells((size_t)nb * nb);
+    uint64_t N = 0;
+    for (int a = 0; a < nb; a++)
+        for (int b = 0; b < nb; b++) { const uint64_t c = h[(size_t)a * nb + b]; cells[(size_t)a * nb + b] = c; rows[a] += c; cols[b] += c; N += c; }
+    if (N == 0 || (double)N < min_overlap * (double)nfinite) return ninf;
+    const double hj = reg_entropy(cells.data(), nb * nb, (double)N);
+    if (hj == 0) return ninf;
+    return (reg_entropy(rows.data(), nb, (double)N) + reg_entropy(cols.data(), nb, (double)N)) / hj;
+}
+
+int reg_levels(const int32_t *a, const int32_t *b) {
+    int n = 1, sa[3] = {a[0], a[1], a[2]}, sb[3] = {b[0], b[1], b[2]};
+    for (int l = 1; l <= 3; l++) {
+        int lo = 1 << 30;
+        for (int c = 0; c < 3; c++) { sa[c] = (sa[c] + 1) / 2; sb[c] = (sb[c] + 1) / 2; lo = std::min({lo, sa[c], sb[c]}); }
+        if (lo >= 8) n = l + 1;
+    }
+    return n;
+}
+
+}  // namespace
+
+// The pattern search as a state machine: fib_reg_search_jobs hands out the matrices to evaluate, fib_reg_search_feed takes their
+// histograms and decides.  A stage is (level, parameters searched); a stage starts with one job, the cost of the current theta there.
+struct fib_reg_search {
+    int dof, halvings, maxit;
+    double min_overlap;
+    int32_t fsize[3];
+    float fres[3], Vf[16], Vm[16];
+    double theta[12], step[12], cur, cand[24][12];
+    int nstages, stage, stage_level[5], stage_nd[5], phase, fails, it;
+    bool done;
+    std::vector<double> trace;
+
+    int level() const { return stage_level[stage]; }
+    int nd() const { return stage_nd[stage]; }
+    void start_stage() {
+        phase = 0; fails = it = 0;
+        const int l = level();
+        const double h = std::ldexp(1.0, l) * (double)std::min({fres[0], fres[1], fres[2]});
+        double s = 0;
+        for (int c = 0; c < 3; c++) { const double e = (double)fsize[c] * (double)fres[c]; s = s + e * e; }
+        const double R = 0.5 * std::sqrt(s) / std::sqrt(3.0);
+        for (int i = 0; i < 12; i++) step[i] = i < 3 ? h : i < 6 ? (h / R) * (180.0 / M_PI) : h / R;
+    }
+    void end_iteration() {
+        if (fails < halvings + 1 && it < maxit) return;
+        if (++stage >= nstages) { done = true; stage = nstages - 1; return; }
+        start_stage();
+    }
+};
+
+extern "C" int fib_reg_levels(const int32_t fixed_size[3], const int32_t moving_size[3], int *levels) try {
+    FIB_CHECK(fixed_size && moving_size && levels, FIB_ERR_INVALID, "NULL argument");
+    for (int c = 0; c < 3; c++) FIB_CHECK(fixed_size[c] > 0 && moving_size[c] > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
+    *levels = reg_levels(fixed_size, moving_size);
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_reg_matrix(const double *theta, int dof, const float fixed_vox2ras[16], const int32_t fixed_size[3], const float moving_vox2ras[16],
+                              int level, float out2in[16], double *G) try {
+    FIB_CHECK(theta && fixed_vox2ras && fixed_size && moving_vox2ras && (out2in || G), FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(dof == 6 || dof == 12, FIB_ERR_INVALID, "dof must be 6 or 12, not %d", dof);
+    FIB_CHECK(level >= 0 && level <= 3, FIB_ERR_INVALID, "level %d outside 0..3", level);
+    double g[16];
+    reg_G(theta, dof, fixed_vox2ras, fixed_size, g);
+    if (G) memcpy(G, g, sizeof g);
+    if (out2in) FIB_CHECK(reg_out2in(g, fixed_vox2ras, moving_vox2ras, level, out2in), FIB_ERR_INVALID, "the moving volume's vox2ras is singular");
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_reg_nmi(const uint32_t *hist, int nbins, int64_t nfinite_fixed, double min_overlap, double *cost) try {
+    FIB_CHECK(hist && cost, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nbins >= FIB_REG_MIN_BINS && nbins <= FIB_REG_MAX_BINS, FIB_ERR_INVALID, "nbins %d outside %d..%d", nbins, FIB_REG_MIN_BINS, FIB_REG_MAX_BINS);
+    FIB_CHECK(nfinite_fixed >= 0 && min_overlap >= 0, FIB_ERR_INVALID, "nfinite_fixed and min_overlap must not be negative");
+    *cost = reg_nmi(hist, nbins, nfinite_fixed, min_overlap);
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_reg_search_create(int dof, const int32_t fixed_size[3], const float fixed_res[3], const float fixed_vox2ras[16],
+                                     const int32_t moving_size[3], const float moving_vox2ras[16], int levels, int halvings, int maxit,
+                                     double min_overlap, const double *theta0, fib_reg_search **out) try {
+    FIB_CHECK(fixed_size && fixed_res && fixed_vox2ras && moving_size && moving_vox2ras && out, FIB_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    FIB_CHECK(dof == 6 || dof == 12, FIB_ERR_INVALID, "dof must be 6 or 12, not %d", dof);
+    for (int c = 0; c < 3; c++)
+        FIB_CHECK(fixed_size[c] > 0 && moving_size[c] > 0 && fixed_res[c] > 0 && std::isfinite(fixed_res[c]), FIB_ERR_INVALID, "sizes and voxel sizes must be positive");
+    FIB_CHECK(levels >= 0 && levels <= 4, FIB_ERR_INVALID, "levels must lie in 1 .. 4 (0: the default), not %d", levels);
+    FIB_CHECK(halvings >= 0 && maxit >= 0 && min_overlap >= 0, FIB_ERR_INVALID, "halvings, maxit and min_overlap must not be negative");
+    float probe[16];
+    double g[16];
+    const double zero[12] = {0};
+    reg_G(zero, 6, fixed_vox2ras, fixed_size, g);
+    FIB_CHECK(reg_out2in(g, fixed_vox2ras, moving_vox2ras, 0, probe), FIB_ERR_INVALID, "the moving volume's vox2ras is singular");
+    std::unique_ptr<fib_reg_search> s(new fib_reg_search());
+    s->dof = dof; s->halvings = halvings; s->maxit = maxit; s->min_overlap = min_overlap;
+    for (int c = 0; c < 3; c++) { s->fsize[c] = fixed_size[c]; s->fres[c] = fixed_res[c]; }
+    memcpy(s->Vf, fixed_vox2ras, sizeof s->Vf);
+    memcpy(s->Vm, moving_vox2ras, sizeof s->Vm);
+    for (int i = 0; i < 12; i++) s->theta[i] = theta0 && i < dof ? theta0[i] : 0.0;
+    const int nl = levels ? levels : reg_levels(fixed_size, moving_size);
+    s->nstages = 0;
+    for (int l = nl - 1; l >= 0; l--) { s->stage_level[s->nstages] = l; s->stage_nd[s->nstages++] = 6; }
+    if (dof == 12) { s->stage_level[s->nstages] = 0; s->stage_nd[s->nstages++] = 12; }
+    s->stage = 0; s->done = false; s->cur = -HUGE_VAL;
+    s->start_stage();
+    *out = s.release();
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" void fib_reg_search_destroy(fib_reg_search *s) try { delete s; } FIB_API_CATCH_VOID
+
+extern "C" int fib_reg_search_jobs(fib_reg_search *s, int *level, int *njobs, float *out2in) try {
+    FIB_CHECK(s && level && njobs && out2in, FIB_ERR_INVALID, "NULL argument");
+    *level = s->level();
+    *njobs = 0;
+    if (s->done) return FIB_OK;
+    double g[16];
+    if (s->phase == 0) {
+        reg_G(s->theta, 12, s->Vf, s->fsize, g);
+        reg_out2in(g, s->Vf, s->Vm, s->level(), out2in);
+        *njobs = 1;
+        return FIB_OK;
+    }
+    const int nd = s->nd();
+    for (int i = 0; i < nd; i++)
+        for (int sg = 0; sg < 2; sg++) {
+            double *c = s->cand[2 * i + sg];
+            memcpy(c, s->theta, sizeof s->theta);
+            c[i] = c[i] + (sg ? -1.0 : 1.0) * s->step[i];
+            reg_G(c, 12, s->Vf, s->fsize, g);
+            reg_out2in(g, s->Vf, s->Vm, s->level(), out2in + 16 * (2 * i + sg));
+        }
+    *njobs = 2 * nd;
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_reg_search_feed(fib_reg_search *s, const uint32_t *hist, int nbins, int64_t nfinite_fixed) try {
+    FIB_CHECK(s && hist, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(!s->done, FIB_ERR_INVALID, "the search has finished: it handed out no jobs");
+    FIB_CHECK(nbins >= FIB_REG_MIN_BINS && nbins <= FIB_REG_MAX_BINS, FIB_ERR_INVALID, "nbins %d outside %d..%d", nbins, FIB_REG_MIN_BINS, FIB_REG_MAX_BINS);
+    const size_t nb2 = (size_t)nbins * nbins;
+    if (s->phase == 0) {
+        s->cur = reg_nmi(hist, nbins, nfinite_fixed, s->min_overlap);
+        s->phase = 1;
+        s->end_iteration();                                     // (maxit == 0: the stage is over)
+        return FIB_OK;
+    }
+    const int nd = s->nd();
+    double row[FIB_REG_TRACE_ROW];
+    for (int i = 0; i < FIB_REG_TRACE_ROW; i++) row[i] = std::nan("");
+    int best = 0;
+    for (int j = 0; j < 2 * nd; j++) {
+        row[5 + j] = reg_nmi(hist + nb2 * j, nbins, nfinite_fixed, s->min_overlap);
+        if (row[5 + j] > row[5 + best]) best = j;               // the first maximum
+    }
+    row[0] = s->level(); row[1] = nd; row[2] = best; row[4] = s->cur;
+    if (row[5 + best] > s->cur) {
+        memcpy(s->theta, s->cand[best], sizeof s->theta);
+        s->cur = row[5 + best];
+        row[3] = 1;
+    } else {
+        for (int i = 0; i < 12; i++) s->step[i] = s->step[i] / 2.0;
+        s->fails++;
+        row[3] = 0;
+    }
+    s->trace.insert(s->trace.end(), row, row + FIB_REG_TRACE_ROW);
+    s->it++;
+    s->end_iteration();
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_reg_search_result(const fib_reg_search *s, double *theta, double *cost, int *niter, double *trace, int trace_rows) try {
+    FIB_CHECK(s, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(trace_rows >= 0 && (trace || trace_rows == 0), FIB_ERR_INVALID, "trace_rows rows need a trace buffer");
+    const int n = (int)(s->trace.size() / FIB_REG_TRACE_ROW);
+    if (theta) memcpy(theta, s->theta, sizeof s->theta);
+    if (cost) *cost = s->cur;
+    if (niter) *niter = n;
+    if (trace) memcpy(trace, s->trace.data(), sizeof(double) * FIB_REG_TRACE_ROW * (size_t)std::min(n, trace_rows));
     return FIB_OK;
 } FIB_API_CATCH

@@ -7,6 +7,42 @@
 
 __device__ __forceinline__ int vx_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
+// The INSIDE rule on the rounded coordinates (the float values of rint(p_c)): NaN fails every comparison, -0.0 passes, and nothing is
+// converted to an integer before.  vx_inside is the rule alone, for a caller that skips outside samples (register.hip).
+__device__ __forceinline__ bool vx_inside_rounded(float rx, float ry, float rz, int nxi, int nyi, int nzi) {
+    return rx >= 0.f && rx <= (float)(nxi - 1) && ry >= 0.f && ry <= (float)(nyi - 1) && rz >= 0.f && rz <= (float)(nzi - 1);
+}
+__device__ __forceinline__ bool vx_inside(const float3 p, int nxi, int nyi, int nzi) {
+    return vx_inside_rounded(rintf(p.x), rintf(p.y), rintf(p.z), nxi, nyi, nzi);
+}
+
+// FIB_VOL_TRILINEAR in its two steps, the one definition of its operation order.  vx_cell: the 8 offsets and the 3 weight pairs of an
+// inside p (floor in [-1, n - 1] there, both neighbours clamped into the volume), the same for every frame.  vx_cell_value: one frame's
+// value, x pairs, then y, then z.
+struct VxCell {
+    int64_t o000, o100, o010, o110, o001, o101, o011, o111;
+    float fx, fy, fz, gx, gy, gz;
+};
+__device__ __forceinline__ VxCell vx_cell(const float3 p, int nxi, int nyi, int nzi) {
+    VxCell c;
+    const float flx = floorf(p.x), fly = floorf(p.y), flz = floorf(p.z);
+    c.fx = p.x - flx; c.fy = p.y - fly; c.fz = p.z - flz;
+    c.gx = 1.f - c.fx; c.gy = 1.f - c.fy; c.gz = 1.f - c.fz;
+    const int x0 = vx_clamp((int)flx, nxi), x1 = vx_clamp((int)flx + 1, nxi);
+    const int64_t y0 = (int64_t)nxi * vx_clamp((int)fly, nyi), y1 = (int64_t)nxi * vx_clamp((int)fly + 1, nyi);
+    const int64_t z0 = (int64_t)nxi * nyi * vx_clamp((int)flz, nzi), z1 = (int64_t)nxi * nyi * vx_clamp((int)flz + 1, nzi);
+    c.o000 = x0 + y0 + z0; c.o100 = x1 + y0 + z0; c.o010 = x0 + y1 + z0; c.o110 = x1 + y1 + z0;
+    c.o001 = x0 + y0 + z1; c.o101 = x1 + y0 + z1; c.o011 = x0 + y1 + z1; c.o111 = x1 + y1 + z1;
+    return c;
+}
+__device__ __forceinline__ float vx_cell_value(const VxCell &c, const float *__restrict__ v) {
+    const float c00 = c.gx * v[c.o000] + c.fx * v[c.o100], c10 = c.gx * v[c.o010] + c.fx * v[c.o110];
+    const float c01 = c.gx * v[c.o001] + c.fx * v[c.o101], c11 = c.gx * v[c.o011] + c.fx * v[c.o111];
+    const float c0 = c.gy * c00 + c.fy * c10;
+    const float c1 = c.gy * c01 + c.fy * c11;
+    return c.gz * c0 + c.fz * c1;
+}
+
 // UNROLL frames of the loop go together: 4 for a series (the loads of four frames are in flight at once), 1 for a volume of fewer than
 // 4 frames; profiles/vol_xform/README.md has both measured
 template <int UNROLL>
@@ -14,9 +50,7 @@ __device__ __forceinline__ void vx_sample(const float3 p, const uint32_t *__rest
                                           uint32_t fill, uint32_t *__restrict__ dst, int64_t nvo) {
     const int64_t nvi = (int64_t)nxi * nyi * nzi;
     const float rx = rintf(p.x), ry = rintf(p.y), rz = rintf(p.z);
-    // tested on the float values: NaN fails every comparison, -0.0 passes, and nothing is converted to an integer before
-    const bool inside = rx >= 0.f && rx <= (float)(nxi - 1) && ry >= 0.f && ry <= (float)(nyi - 1) && rz >= 0.f && rz <= (float)(nzi - 1);
-    if (!inside) {
+    if (!vx_inside_rounded(rx, ry, rz, nxi, nyi, nzi)) {
         for (int f = 0; f < nframes; f++) dst[(int64_t)f * nvo] = fill;
         return;
     }
@@ -26,23 +60,9 @@ __device__ __forceinline__ void vx_sample(const float3 p, const uint32_t *__rest
         for (int f = 0; f < nframes; f++) dst[(int64_t)f * nvo] = src[(int64_t)f * nvi];
         return;
     }
-    // trilinear: floor in [-1, n - 1] here (rint(p) is inside), both neighbours clamped into the volume
-    const float flx = floorf(p.x), fly = floorf(p.y), flz = floorf(p.z);
-    const float fx = p.x - flx, fy = p.y - fly, fz = p.z - flz;
-    const float gx = 1.f - fx, gy = 1.f - fy, gz = 1.f - fz;
-    const int x0 = vx_clamp((int)flx, nxi), x1 = vx_clamp((int)flx + 1, nxi);
-    const int64_t y0 = (int64_t)nxi * vx_clamp((int)fly, nyi), y1 = (int64_t)nxi * vx_clamp((int)fly + 1, nyi);
-    const int64_t z0 = (int64_t)nxi * nyi * vx_clamp((int)flz, nzi), z1 = (int64_t)nxi * nyi * vx_clamp((int)flz + 1, nzi);
-    const int64_t o000 = x0 + y0 + z0, o100 = x1 + y0 + z0, o010 = x0 + y1 + z0, o110 = x1 + y1 + z0;
-    const int64_t o001 = x0 + y0 + z1, o101 = x1 + y0 + z1, o011 = x0 + y1 + z1, o111 = x1 + y1 + z1;
+    const VxCell c = vx_cell(p, nxi, nyi, nzi);
     const float *__restrict__ v = reinterpret_cast<const float *>(vol);
     float *__restrict__ d = reinterpret_cast<float *>(dst);
 #pragma unroll UNROLL                                          // (vol and out do not overlap: the loads of UNROLL frames go out together)
-    for (int f = 0; f < nframes; f++, v += nvi) {
-        const float c00 = gx * v[o000] + fx * v[o100], c10 = gx * v[o010] + fx * v[o110];
-        const float c01 = gx * v[o001] + fx * v[o101], c11 = gx * v[o011] + fx * v[o111];
-        const float c0 = gy * c00 + fy * c10;
-        const float c1 = gy * c01 + fy * c11;
-        d[(int64_t)f * nvo] = gz * c0 + fz * c1;
-    }
+    for (int f = 0; f < nframes; f++, v += nvi) d[(int64_t)f * nvo] = vx_cell_value(c, v);
 }

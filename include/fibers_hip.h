@@ -945,6 +945,110 @@ int fibd_warp_invert(const void *packed, int nx, int ny, int nz, const float out
                      float *inv, float *err, int nxo, int nyo, int nzo, void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Registration: rigid / affine alignment by normalised mutual information               */
+/* (NOT in the reference)                                                                 */
+/* ------------------------------------------------------------------------------------ */
+/* The conventions of "Volume resampling": planar volumes with x fastest, 0-based voxel indices, float32 with every multiply and add
+ * rounded on its own, matrices derived in float64 from float32 fields and rounded to float32 once.  These definitions are this
+ * project's own; they are the contract, tests/register_ref.py restates them in NumPy, and everything up to the histogram is held to
+ * that bit for bit (a joint histogram is an integer count).
+ *
+ * PYRAMID (fibd_vol_halve).  The output size is ceil(n_c / 2) per axis.  Output voxel (i, j, k) is the float32 sum of the EXISTING
+ * input voxels (2i + dx, 2j + dy, 2k + dz), dx, dy, dz in {0, 1}, started from +0 and added with dz outermost and dx innermost,
+ * divided by their count as a float32 (a block cut by an odd size has fewer than 8).  Level-l voxel x sits at level-0 voxel
+ * 2^l x + (2^l - 1) / 2: the matrix D_l.
+ *
+ * RANGE (fibd_vol_range), per frame, 16 bytes { float lo, hi, scale; uint32_t nfinite }: lo and hi are the smallest and largest FINITE
+ * value by the ordered-uint key of "Brain mask" (so -0 < +0 and the result does not depend on the order of the reduction),
+ * scale = float32(nbins) / (hi - lo), one float32 division, nfinite the number of finite values.  Without a finite value lo = hi = 0 and
+ * scale = NaN; hi == lo gives scale = +Inf.  The device form writes that and returns; the drivers refuse it ("constant volume",
+ * FIB_ERR_INVALID).
+ *
+ * BIN.  t = (v - lo) * scale, two float32 roundings.  A NaN t (a NaN v, or Inf * 0) has no bin; otherwise
+ * bin(v) = clamp(floor(t), 0, nbins - 1), clamped as a float before the conversion (so v = hi, and +-Inf, land in an end bin).
+ *
+ * JOINT HISTOGRAMS (fibd_reg_hist).  One fixed volume, the frames of a moving series and njobs jobs; job j is (moving frame
+ * job_frame[j], out2in matrix job_out2in + 16 j: FIXED voxel -> MOVING voxel, row-major float[16]).  For every fixed voxel (i, j, k)
+ * whose value a is finite: p = xfm_point(M_j, i, j, k) with fib_xfm_apply's arithmetic; the INSIDE rule of "Volume resampling" on p
+ * against the moving size -- outside samples are SKIPPED, not filled; v = the FIB_VOL_TRILINEAR value of the frame at p, in that
+ * section's operation order; a sample without a bin on either side is skipped; else hist[j][bin_fixed(a)][bin_moving(v)] += 1, with the
+ * fixed volume's range and the range of frame job_frame[j].  hist is uint32 [njobs][nbins][nbins], zeroed by the call; every sum is an
+ * integer sum, so the result does not depend on the launch shape.  nbins in FIB_REG_MIN_BINS .. FIB_REG_MAX_BINS.  job_frame and
+ * job_out2in are HOST arrays (copied to the head of `work` on the stream before the launch: they may be reused on return); the ranges
+ * are DEVICE memory as fibd_vol_range leaves them.  The kernel is asynchronous on `stream` and nothing is allocated; the copy of the job
+ * table (80 bytes a job) comes from pageable host memory, which the runtime stages before the call returns and for which it may wait for
+ * earlier work of `stream`: no other wait is inside.  `work` is
+ * 8-byte aligned, fibd_reg_hist_work_size bytes.  The launch's third dimension is the job: one launch carries the 2 dof candidates of
+ * every live frame of a series.  FIB_ERR_INVALID: NULL pointers, non-positive sizes, nbins or njobs out of range, a frame index outside
+ * [0, nframes), a short workspace, misaligned pointers, ANY overlap of hist or work with a volume, a range or each other; a dimension
+ * above 2^24 is FIB_ERR_UNSUPPORTED.
+ *
+ * MATRICES (fib_reg_matrix; host, float64).  theta: dof 6 = (tx, ty, tz mm; rx, ry, rz degrees); dof 12 adds (ln sx, ln sy, ln sz;
+ * hxy, hxz, hyz).  A = [Rz Ry Rx Sh S | t] with the right-handed rotations about x, y, z, Sh unit upper-triangular with the three
+ * shears and S = diag(exp(.)); G(theta) = C A C^-1 with C the translation to c = fixed.vox2ras (n - 1) / 2; G maps FIXED RAS -> MOVING
+ * RAS.  out2in_l = float32(inv(V_mov D_l) G (V_fix D_l)).  G (or NULL) receives G itself, row-major double[16]; out2in may be NULL.
+ *
+ * COST (fib_reg_nmi; host, float64).  N = sum hist; cost = -Inf when N == 0 or N < min_overlap * nfinite_fixed (the finite fixed voxels
+ * of that level); H(c) = ln N - (sum c ln c) / N over the non-zero cells in row-major order; cost = (H(rows) + H(cols)) / H(joint), -Inf
+ * when H(joint) == 0.
+ *
+ * PATTERN SEARCH (fib_reg_search_*; host, float64, HIP-free: the caller evaluates the histograms).  Levels run from the coarsest,
+ * levels - 1, to 0; levels = 0 means fib_reg_levels: 1 + the largest l <= 3 at which both volumes keep every dimension >= 8.  Steps at
+ * level l: h = 2^l min(fixed.volres), R = 0.5 sqrt(sum (n_c res_c)^2) / sqrt(3); h mm, degrees(h / R) and h / R for translations,
+ * rotations and scale / shear.  A stage (a level, the first 6 or all 12 parameters) starts with ONE job, the cost of the current theta
+ * at that level; then every iteration hands out the 2 n candidates theta +- step_i e_i (index 2 i: +, 2 i + 1: -), takes the first
+ * maximum of their costs, moves there iff it is strictly greater than the current cost, else halves all steps.  A stage ends after
+ * halvings + 1 failures or maxit iterations.  dof 12 runs the 6-parameter stages over all levels, then one 12-parameter stage at level 0
+ * from that result.  fib_reg_search_jobs: the level and the matrices to evaluate (njobs <= 24; 0 when the search has finished);
+ * fib_reg_search_feed: their histograms [njobs][nbins][nbins] with that level's nfinite.  fib_reg_search_result: theta (12 values, zero
+ * beyond dof), the cost of theta at level 0, the number of iterations and min(niter, trace_rows) rows of FIB_REG_TRACE_ROW doubles:
+ * level, parameters searched, chosen index, 1 = moved / 0 = halved, the cost before, the candidates' costs (NaN beyond 2 n).
+ *
+ * RUN (fibd_reg_run).  nsearch searches (all created for the same volumes and `levels`), search s against moving frame frames[s], run
+ * to their end on device-resident volumes: the pyramids and the ranges of all levels are made in `work` (16-byte aligned,
+ * fibd_reg_run_work_size bytes) and the ranges read back once -- a volume without two distinct finite values at any level is
+ * FIB_ERR_INVALID ("constant volume"); then, every round, the searches that wait at the coarsest pending level put their jobs into ONE
+ * fibd_reg_hist launch, the histograms come back once and every search decides.  Finished searches leave the job list.  Searches are
+ * independent: a search's result does not depend on what shares its launches.  The call waits on `stream` once per round; the results
+ * are read from the handles.
+ *
+ * HOST FORM (fib_mri_register).  Every frame of `moving` [nframes][nvox_m] registered to `fixed`, each from theta = 0, on one device
+ * (FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED): theta [nframes][12], cost [nframes], niter [nframes] (each may be NULL but theta), trace
+ * [nframes][trace_rows][FIB_REG_TRACE_ROW] or NULL.  levels = 0: fib_reg_levels.  resampled (or NULL): [nframes][nvox_f], frame f pulled
+ * through its own final level-0 out2in with fibd_vol_xform, FIB_VOL_TRILINEAR, 0 outside -- the series of dwi_moco. */
+#define FIB_REG_MIN_BINS 8
+#define FIB_REG_MAX_BINS 64
+#define FIB_REG_MAX_JOBS 65535
+#define FIB_REG_TRACE_ROW 29
+typedef struct fib_reg_search fib_reg_search;
+int fibd_vol_halve(const float *in, int nx, int ny, int nz, int nframes, float *out, void *stream);
+int fibd_vol_range(const float *vol, int64_t nvox, int nframes, int nbins, void *range, void *stream);
+int fibd_reg_hist_work_size(int njobs, size_t *bytes);
+int fibd_reg_hist(const float *fixed, int nxf, int nyf, int nzf, const void *fixed_range, const float *moving, int nxm, int nym, int nzm,
+                  int nframes, const void *moving_range, const int32_t *job_frame, const float *job_out2in, int njobs, int nbins,
+                  uint32_t *hist, void *work, size_t work_bytes, void *stream);
+int fib_reg_levels(const int32_t fixed_size[3], const int32_t moving_size[3], int *levels);
+int fib_reg_matrix(const double *theta, int dof, const float fixed_vox2ras[16], const int32_t fixed_size[3], const float moving_vox2ras[16],
+                   int level, float out2in[16], double *G);
+int fib_reg_nmi(const uint32_t *hist, int nbins, int64_t nfinite_fixed, double min_overlap, double *cost);
+int fib_reg_search_create(int dof, const int32_t fixed_size[3], const float fixed_res[3], const float fixed_vox2ras[16],
+                          const int32_t moving_size[3], const float moving_vox2ras[16], int levels, int halvings, int maxit,
+                          double min_overlap, const double *theta0, fib_reg_search **out);
+void fib_reg_search_destroy(fib_reg_search *search);
+int fib_reg_search_jobs(fib_reg_search *search, int *level, int *njobs, float *out2in);
+int fib_reg_search_feed(fib_reg_search *search, const uint32_t *hist, int nbins, int64_t nfinite_fixed);
+int fib_reg_search_result(const fib_reg_search *search, double *theta, double *cost, int *niter, double *trace, int trace_rows);
+int fibd_reg_run_work_size(const int32_t fixed_size[3], const int32_t moving_size[3], int nframes, int nsearch, int levels, int nbins,
+                           size_t *bytes);
+int fibd_reg_run(fib_reg_search *const *searches, const int32_t *frames, int nsearch, const float *fixed, const int32_t fixed_size[3],
+                 const float *moving, const int32_t moving_size[3], int nframes, int levels, int nbins, void *work, size_t work_bytes,
+                 void *stream);
+int fib_mri_register(int device, const float *moving, const int32_t moving_size[3], const float moving_vox2ras[16], int nframes,
+                     const float *fixed, const int32_t fixed_size[3], const float fixed_res[3], const float fixed_vox2ras[16], int dof,
+                     int nbins, int levels, int halvings, int maxit, double min_overlap, double *theta, double *cost, int *niter,
+                     double *trace, int trace_rows, float *resampled);
+
+/* ------------------------------------------------------------------------------------ */
 /* Host-buffer drop-in entry points (what the Julia wrapper ccalls)                       */
 /* ------------------------------------------------------------------------------------ */
 

@@ -575,6 +575,80 @@ function vol_xform(xfm::Xform{Float32}, vol::Array{Int32,4}; interp::Symbol=:nea
   return vol_xform_call(xfm, vol, interp, Int32(outside), device)
 end
 
+# ---- registration (NOT in the reference; the definitions are the "Registration" section of include/fibers_hip.h) ------------------
+const FIB_REG_TRACE_ROW = 29
+rowmajor(m) = Matrix{Float32}(permutedims(Float32.(m)))        # a 4 x 4 matrix as the row-major float[16] of the C ABI
+# an MRI's Float32 voxels as [nx, ny, nz, nframes]: MRI(ref, 1, T) and a one-frame file hold a 3-D array (mri.jl:251-252); same memory
+vol4(v::Array{Float32}) = reshape(v, size(v, 1), size(v, 2), size(v, 3), size(v, 4))
+# the rotational part of a vox2vox, U * Vt of its SVD (util.jl:265-267), kept in Float64
+rot64(v2v) = (F = svd(Float64.(v2v[1:3, 1:3])); F.U * F.Vt)
+
+"G(theta), fixed RAS -> moving RAS, Float64 4 x 4 (fib_reg_matrix)"
+function reg_G(theta::Vector{Float64}, fixed::MRI, moving::MRI)
+  G = Matrix{Float64}(undef, 4, 4)
+  fv = rowmajor(fixed.vox2ras0); mv = rowmajor(moving.vox2ras0); fs = Int32.(collect(fixed.volsize[1:3]))
+  GC.@preserve theta fv mv fs G fib_check(ccall((:fib_reg_matrix, libfibers), Cint,
+      (Ptr{Float64}, Cint, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Cint, Ptr{Float32}, Ptr{Float64}),
+      theta, length(theta), fv, fs, mv, 0, C_NULL, G))
+  return permutedims(G)
+end
+
+"the Xform of a registration result, in = moving, out = fixed: ras2ras = Float32(inv(G)), vox2vox = Float32(inv(V_fix) inv(G) V_mov)"
+function reg_xform(theta::Vector{Float64}, moving::MRI, fixed::MRI)
+  Gi = inv(reg_G(theta, fixed, moving))
+  v2v = Float32.(inv(Float64.(fixed.vox2ras0)) * Gi * Float64.(moving.vox2ras0))
+  return Xform{Float32}(collect(moving.volsize[1:3]), collect(fixed.volsize[1:3]), Float32.(moving.volres), Float32.(fixed.volres),
+                        Float32.(moving.vox2ras0), Float32.(fixed.vox2ras0), v2v, Float32.(Gi), Float32.(rot64(v2v)))
+end
+
+"every frame of `vol` registered to frame 1 of `fixed` (fib_mri_register): (theta [12, N], cost [N], niter [N], trace [29, rows, N], resampled)"
+function reg_call(vol::Array{Float32,4}, moving::MRI, fixed::MRI, dof::Integer, nbins::Integer, levels::Integer, resample::Bool, device::Integer)
+  nf = size(vol, 4); rows = 400
+  fvol = vol4(fixed.vol)
+  ms = Int32.(collect(size(vol)[1:3])); fs = Int32.(collect(size(fvol)[1:3])); fres = Float32.(collect(fixed.volres))
+  mv = rowmajor(moving.vox2ras0); fv = rowmajor(fixed.vox2ras0)
+  theta = zeros(Float64, 12, nf); cost = zeros(Float64, nf); niter = zeros(Int32, nf); trace = Array{Float64,3}(undef, FIB_REG_TRACE_ROW, rows, nf)
+  out = resample ? Array{Float32,4}(undef, fs[1], fs[2], fs[3], nf) : Array{Float32,4}(undef, 0, 0, 0, 0)
+  GC.@preserve vol fvol ms fs fres mv fv theta cost niter trace out fib_check(ccall((:fib_mri_register, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Cint, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Cint, Cint, Cint, Cint, Cint, Cdouble,
+       Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Cint, Ptr{Float32}),
+      device, vol, ms, mv, nf, fvol, fs, fres, fv, dof, nbins, levels, 4, 80, 0.5,
+      theta, cost, niter, trace, rows, resample ? pointer(out) : Ptr{Float32}(C_NULL)))
+  return theta, cost, niter, trace, out
+end
+
+"mri_register(moving, fixed; dof, nbins, levels, frame) — rigid (dof 6) or affine (dof 12) registration by normalised mutual information;
+returns (xfm, theta, cost, trace): mri_xform / vol_xform through `xfm` puts the moving volume on the fixed grid.  levels = 0: the default."
+function mri_register(moving::MRI, fixed::MRI; dof::Integer=6, nbins::Integer=32, levels::Integer=0, frame::Integer=1, device::Integer=0)
+  vol = vol4(moving.vol)[:, :, :, frame:frame]
+  theta, cost, niter, trace, _ = reg_call(vol, moving, fixed, dof, nbins, levels, false, device)
+  th = theta[1:dof, 1]
+  return (xfm = reg_xform(th, moving, fixed), theta = th, cost = cost[1], trace = trace[:, 1:niter[1], 1])
+end
+
+"dwi_moco(dwi; target, nbins, levels) — every frame registered (dof 6) to `target` (default: the Float64 mean of the frames of the
+smallest b-value) and resampled onto its grid, trilinear, 0 outside; bvec rows rotated by the rotational part of their frame's transform
+(U * Vt of the SVD of vox2vox in Float64, applied in Float64, rounded once: what fibers_jl_amd.register.rotate_bvec does).
+Returns (dwi, theta, xfm, cost)."
+function dwi_moco(dwi::MRI; target::Union{MRI,Nothing}=nothing, nbins::Integer=32, levels::Integer=0, device::Integer=0)
+  vol = vol4(dwi.vol)
+  if target === nothing
+    fr = isempty(dwi.bval) ? [1] : findall(dwi.bval .== minimum(dwi.bval))
+    acc = zeros(Float64, size(vol)[1:3])
+    for f in fr; acc .+= Float64.(view(vol, :, :, :, f)); end
+    target = MRI(dwi, 1, Float32)
+    target.vol = Float32.(acc ./ length(fr))                        # (3-D, as MRI(dwi, 1, Float32) holds it)
+  end
+  theta, cost, _, _, out = reg_call(vol, dwi, target, 6, nbins, levels, true, device)
+  nf = size(vol, 4)
+  xfms = [reg_xform(theta[1:6, f], dwi, target) for f in 1:nf]
+  moved = MRI(target, nf, Float32)
+  moved.vol = nf == 1 ? out[:, :, :, 1] : out                     # (MRI(target, 1, Float32) holds a 3-D array)
+  moved.bval = copy(dwi.bval)
+  moved.bvec = isempty(dwi.bvec) ? copy(dwi.bvec) : Float32.(reduce(vcat, [(rot64(xfms[f].vox2vox) * Float64.(dwi.bvec[f, :]))' for f in 1:nf]))
+  return (dwi = moved, theta = theta[1:6, :], xfm = xfms, cost = cost)
+end
+
 # ---- non-linear warps (NOT in the reference; the definitions are the "Non-linear warps" section of include/fibers_hip.h) -----------
 # A field is a Float32 array [nx, ny, nz, 3] (the displacement in mm, RAS) with the vox2ras of its grid.  Matrices are made in Float64
 # from the Float32 fields, rounded once, and go to the C ABI row-major.
