@@ -50,3 +50,7 @@ from .probtrack import ProbPlan, prob_row_pitch, prob_stream, prob_work_size  # 
 # (the device tier of the warps likewise: warp.warp_pack_device, warp.warp_points_device, warp.warp_volume_device, warp.warp_invert_device)
 from . import warp  # noqa: F401
 from .warp import Warp, mri_warp, str_warp, warp_invert, warp_read, warp_write  # noqa: F401
+# (the device tier of the non-linear registration likewise: nlreg.nlreg_step_device, nlreg.warp_smooth_device, nlreg.warp_upsample_device,
+# nlreg.warp_unpack_device, nlreg.warp_jacobian_device, nlreg.mri_nlreg_device)
+from . import nlreg  # noqa: F401
+from .nlreg import NonlinearRegistration, mri_nlreg, warp_jacobian  # noqa: F401

@@ -187,6 +187,17 @@ _PROTOS = {
     "fibd_reg_run_work_size": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_uint64)]),
     "fibd_reg_run": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, C.c_uint64, vp]),
     "fib_mri_register": (i32, [i32, vp, vp, M16, i32, vp, vp, vp, M16, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, i32, vp]),
+    "fib_nlreg_level": (i32, [M16, M16, vp, i32, f32, vp, vp, vp, C.POINTER(f32)]),
+    "fibd_nlreg_step_work_size": (i32, [i32, i32, i32, C.POINTER(C.c_uint64)]),
+    "fibd_nlreg_step": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, vp, M16, M16, vp, f32, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_warp_smooth": (i32, [vp, i32, i32, i32, f32, vp, vp, C.c_uint64, vp]),
+    "fibd_warp_upsample": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, vp]),
+    "fibd_warp_unpack": (i32, [vp, i32, i32, i32, vp, vp]),
+    "fibd_warp_jacobian": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "fibd_nlreg_work_size": (i32, [vp, vp, i32, vp, C.POINTER(C.c_uint64)]),
+    "fibd_nlreg_run": (i32, [vp, vp, M16, vp, vp, M16, vp, i32, vp, f32, f32, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fib_mri_nlreg": (i32, [i32, vp, vp, M16, vp, vp, M16, vp, i32, vp, f32, f32, vp, vp, vp, vp, vp]),
+    "fib_warp_jacobian": (i32, [i32, vp, i32, i32, i32, vp, vp]),
     "fibd_str_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
     "fibd_str_density": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, C.c_uint64, vp]),
     "fibd_str_sample": (i32, [vp, i64, vp, i32, i32, i32, i32, f32, vp, vp]),

@@ -1073,6 +1073,55 @@ extern "C" int fib_mri_register(int device, const float *moving, const int32_t m
 } FIB_API_CATCH
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// non-linear registration: the host forms.  One device; both volumes, the workspace of fibd_nlreg_run and the field stay on the device
+// for the call, the planar field and the warped volume come back at its end.
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_mri_nlreg(int device, const float *moving, const int32_t moving_size[3], const float moving_vox2ras[16], const float *fixed,
+                             const int32_t fixed_size[3], const float fixed_vox2ras[16], const float *post, int levels, const int32_t *niter,
+                             float sigma, float step, float *disp, double *cost, int64_t *count, const float *warp_mats, float *warped) try {
+    FIB_CHECK(moving && moving_size && moving_vox2ras && fixed && fixed_size && fixed_vox2ras && niter && disp, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(!warped || warp_mats, FIB_ERR_INVALID, "the warped volume needs its three matrices");
+    size_t work_bytes = 0;
+    RC(fibd_nlreg_work_size(fixed_size, moving_size, levels, niter, &work_bytes));     // (sizes, levels and niter are refused here)
+    FIB_CHECK(sigma >= 0.f && sigma <= 4.f, FIB_ERR_INVALID, "sigma %g outside [0, 4]", (double)sigma);
+    float m[16 + 16 + 9 + 1];
+    for (int l = 0; l < levels; l++) RC(fib_nlreg_level(fixed_vox2ras, moving_vox2ras, post, l, step, m, m + 16, m + 32, m + 41));
+    DevLease lease;
+    RC(lease.take(device, "mri_nlreg runs on one device (FIB_DEVICE_ALL is not supported)"));
+    const size_t nvf = (size_t)fixed_size[0] * fixed_size[1] * fixed_size[2], nvm = (size_t)moving_size[0] * moving_size[1] * moving_size[2];
+    fib::DevBuf<float> d_fixed, d_moving, d_field, d_out;
+    fib::DevBuf<char> d_work;
+    RC(fib::upload(d_fixed, fixed, nvf));
+    RC(fib::upload(d_moving, moving, nvm));
+    RC(d_field.alloc(4 * nvf));
+    RC(d_out.alloc(3 * nvf));
+    RC(d_work.alloc(work_bytes));
+    RC(fibd_nlreg_run(d_fixed.p, fixed_size, fixed_vox2ras, d_moving.p, moving_size, moving_vox2ras, post, levels, niter, sigma, step, d_field.p, cost,
+                      count, d_work.p, work_bytes, nullptr));
+    RC(fibd_warp_unpack(d_field.p, fixed_size[0], fixed_size[1], fixed_size[2], d_out.p, nullptr));
+    RC(d2h(disp, d_out.p, sizeof(float) * 3 * nvf));
+    if (!warped) return FIB_OK;
+    RC(fibd_warp_volume(d_field.p, fixed_size[0], fixed_size[1], fixed_size[2], warp_mats, warp_mats + 16, warp_mats + 32, d_moving.p, moving_size[0],
+                        moving_size[1], moving_size[2], 1, FIB_VOL_TRILINEAR, 0, d_out.p, fixed_size[0], fixed_size[1], fixed_size[2], nullptr));
+    RC(d2h(warped, d_out.p, sizeof(float) * nvf));
+    return FIB_OK;
+} FIB_API_CATCH
+
+extern "C" int fib_warp_jacobian(int device, const float *disp, int nx, int ny, int nz, const float linv[9], float *out) try {
+    FIB_CHECK(disp && linv && out, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "the field's dimensions must be positive");
+    DevLease lease;
+    RC(lease.take(device, "warp_jacobian runs on one device (FIB_DEVICE_ALL is not supported)"));
+    const size_t nvox = (size_t)nx * ny * nz;
+    fib::DevBuf<float> d_field, d_out;
+    RC(warp_field_upload(disp, nx, ny, nz, d_field));
+    RC(d_out.alloc(nvox));
+    RC(fibd_warp_jacobian(d_field.p, nx, ny, nz, linv, d_out.p, nullptr));
+    RC(d2h(out, d_out.p, sizeof(float) * nvox));
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // tract maps: host forms.  One device; the points travel in chunks cut at line boundaries, the volume stays on the device.
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {

@@ -206,4 +206,8 @@ int vm_mask_finish(void *work, int count, int nx, int ny, int nz, const fib_mask
 void host_degibbs_table(int n, int K, double *D);
 void host_degibbs_twiddles(int n, double *cs, double *c);
 
+// Non-linear registration (include/fibers_hip.h; setup.cpp): the taps of the regularisation, radius r = ceil(3 sigma) <= max_radius and
+// w[t + r] = float32(exp(-t^2 / (2 sigma^2)) / sum) for t = -r .. r, made in float64; sigma == 0 gives r = 0 and the one tap 1
+int host_gauss_taps(float sigma, int max_radius, int *radius, float *w);
+
 }  // namespace fib

@@ -771,3 +771,47 @@ extern "C" int fib_reg_search_result(const fib_reg_search *s, double *theta, dou
     if (trace) memcpy(trace, s->trace.data(), sizeof(double) * FIB_REG_TRACE_ROW * (size_t)std::min(n, trace_rows));
     return FIB_OK;
 } FIB_API_CATCH
+
+// ---- Non-linear registration (include/fibers_hip.h): the matrices of a level and the Gaussian taps, in float64 on the host ----------
+extern "C" int fib_nlreg_level(const float fixed_vox2ras[16], const float moving_vox2ras[16], const float *post, int level, float step,
+                               float to_ras[16], float from_ras[16], float T[9], float *kappa) try {
+    FIB_CHECK(fixed_vox2ras && moving_vox2ras && to_ras && from_ras && T && kappa, FIB_ERR_INVALID, "NULL argument");
+    FIB_CHECK(level >= 0 && level <= 3, FIB_ERR_INVALID, "level %d outside 0..3", level);
+    FIB_CHECK(step > 0.f && std::isfinite(step), FIB_ERR_INVALID, "step must be positive and finite, not %g", (double)step);
+    double D[16], A[16], B[16], Ai[16], Bi[16], vf[16], vm[16], P[16];
+    for (int i = 0; i < 16; i++) { D[i] = 0; vf[i] = fixed_vox2ras[i]; vm[i] = moving_vox2ras[i]; P[i] = post ? (double)post[i] : (double)(i % 5 == 0); }
+    const double s = std::ldexp(1.0, level);
+    D[0] = D[5] = D[10] = s; D[15] = 1;
+    D[3] = D[7] = D[11] = (s - 1.0) / 2.0;
+    m4_mul(vf, D, B);                                           // V_fix D_l
+    m4_mul(vm, D, A);                                           // V_mov D_l
+    FIB_CHECK(m4_inv(A, Ai), FIB_ERR_INVALID, "the moving volume's vox2ras is singular");
+    double L[16];                                               // the linear part of V_fix D_l, alone
+    for (int i = 0; i < 16; i++) L[i] = (i % 4 < 3 && i / 4 < 3) ? B[i] : (double)(i % 5 == 0);
+    FIB_CHECK(m4_inv(L, Bi), FIB_ERR_INVALID, "the fixed volume's vox2ras is singular");
+    m4_mul(Ai, P, A);                                           // inv(V_mov D_l) post
+    for (int i = 0; i < 16; i++) { to_ras[i] = (float)B[i]; from_ras[i] = (float)A[i]; }
+    for (int c = 0; c < 3; c++)
+        for (int k = 0; k < 3; k++) T[3 * c + k] = (float)Bi[4 * k + c];                // inv(L) transposed
+    const double ell = s * (double)step;
+    *kappa = (float)(1.0 / (ell * ell));
+    for (int i = 0; i < 16; i++) FIB_CHECK(std::isfinite(to_ras[i]) && std::isfinite(from_ras[i]), FIB_ERR_INVALID, "a matrix of level %d is not finite", level);
+    return FIB_OK;
+} FIB_API_CATCH
+
+namespace fib {
+
+int host_gauss_taps(float sigma, int max_radius, int *radius, float *w) {
+    FIB_CHECK(sigma >= 0.f && sigma <= 4.f, FIB_ERR_INVALID, "sigma %g outside [0, 4]", (double)sigma);
+    const double sg = (double)sigma;
+    const int r = (int)std::ceil(3.0 * sg);
+    FIB_CHECK(r <= max_radius, FIB_ERR_INVALID, "sigma %g needs a radius of %d, above %d", sg, r, max_radius);
+    *radius = r;
+    if (r == 0) { w[0] = 1.f; return FIB_OK; }
+    double e[64], sum = 0;
+    for (int t = -r; t <= r; t++) { e[t + r] = std::exp(-((double)t * (double)t) / (2.0 * sg * sg)); sum += e[t + r]; }
+    for (int t = 0; t <= 2 * r; t++) w[t] = (float)(e[t] / sum);
+    return FIB_OK;
+}
+
+}  // namespace fib

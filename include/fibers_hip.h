@@ -1049,6 +1049,96 @@ int fib_mri_register(int device, const float *moving, const int32_t moving_size[
                      double *trace, int trace_rows, float *resampled);
 
 /* ------------------------------------------------------------------------------------ */
+/* Non-linear registration: a displacement field estimated by demons, its Jacobian map   */
+/* (NOT in the reference)                                                                 */
+/* ------------------------------------------------------------------------------------ */
+/* The estimator of the field that "Non-linear warps" applies: single-contrast, multi-resolution, additive demons (Thirion 1998; the
+ * forces come from the FIXED image's gradient) with a fixed number of iterations per level, so nothing in it depends on the data.  The
+ * conventions are those of "Non-linear warps": float32, every multiply, add and divide rounded on its own, no fused multiply-add, planar
+ * volumes [nframes][nz][ny][nx], 0-based voxels, the packed float4 field on the device.  These definitions are this project's own; they
+ * are the contract, and tests/nlreg_ref.py restates them in NumPy.
+ *
+ * GEOMETRY.  The field lives on the FIXED volume's grid (space A) and phi(x) = x + d(x) takes fixed RAS to moving RAS (space B), so that
+ * fib_warp_volume of the moving volume onto the fixed grid pulls it into place (the ANTs convention).  `post` is the initial affine,
+ * fixed RAS -> moving RAS, row-major float[16] (NULL: the identity).  Level l of a pyramid of `levels` levels (1 .. 4) holds the volumes
+ * halved l times by fibd_vol_halve; the level-l field sits on the level-l fixed grid, whose vox2ras is V_fix D_l (D_l of "Registration").
+ * fib_nlreg_level makes what a level needs, in float64 from the float32 inputs and rounded once:
+ *   to_ras = float32(V_fix D_l),  from_ras = float32(inv(V_mov D_l) post),  T = float32(inv(L)^T) with L the 3 x 3 linear part of
+ *   V_fix D_l (row-major float[9]),  kappa = float32(1 / ell^2) with ell = 2^l step, `step` in mm (the bindings default it to the
+ *   smallest fixed voxel size).
+ *
+ * ONE ITERATION at level l, for every fixed level-l voxel (i, j, k):
+ *   1. NORMALISED VALUES.  n(v) = (v - lo) * s, two roundings, with lo, hi the level volume's finite range by fibd_vol_range's rule and
+ *      s = float32(1) / (hi - lo), one float32 subtraction and one division.  norm[4] = { lo_fixed, s_fixed, lo_moving, s_moving }.  A
+ *      level volume without two distinct finite values is refused by the drivers ("constant volume", FIB_ERR_INVALID).
+ *   2. MOVING SAMPLE.  m = the value fibd_warp_volume gives at this voxel with FIB_VOL_TRILINEAR, the current level field, to_field the
+ *      identity (q = (i, j, k); S(q) is still the 8-neighbour sample with f = 0, not special-cased), to_ras and from_ras as above.  A
+ *      sample that the INSIDE rule puts outside the moving level volume is ABSENT, not filled.  Then m <- n_moving(m).
+ *   3. FIXED GRADIENT.  f = n_fixed(F) at the voxel.  THE DIFFERENCE RULE along a voxel axis of size n at index i:
+ *      (f[i + 1] - f[i - 1]) * 0.5 for 0 < i < n - 1, f[1] - f[0] at i = 0, f[n - 1] - f[n - 2] at i = n - 1, and 0 when n == 1.
+ *      g_c = (T[c][0] v_0 + T[c][1] v_1) + T[c][2] v_2 with v the three voxel-axis differences: the gradient in 1 / mm, RAS.
+ *   4. FORCE.  diff = f - m;  den = ((g_0 g_0 + g_1 g_1) + g_2 g_2) + (diff diff) kappa.  u = 0 if m is absent, if any of f, m, g_c is not
+ *      finite, or if den is zero or not finite; otherwise q = diff / den and u_c = q g_c.  d'_c = d_c + u_c with d the field's value AT
+ *      the voxel; the fourth word of the packed field is written as 0.  |u| <= ell / 2: an iteration moves a sample by at most half a
+ *      level voxel.
+ *   5. COST.  count = the number of voxels whose u was computed (exact); ssd = the float64 sum of the float32 squares diff diff over
+ *      them (the order of the sum is the kernel's: workgroup partials, then one workgroup over the partials; a run repeats its bits);
+ *      cost = ssd / count, NaN when count == 0.
+ *   6. REGULARISATION.  d' is smoothed by a separable Gaussian of sigma level voxels (0: none; at most 4): radius r = ceil(3 sigma),
+ *      taps w_t = float32(exp(-t^2 / (2 sigma^2)) / sum over t = -r .. r, added in that order) made in float64 on the host; per
+ *      component and pass acc = +0, then acc = acc + w_t v[clamp(i + t, 0, n - 1)] for t = -r .. r in that order (the edge value
+ *      continues beyond the grid, as in SAMPLE); the x pass over the whole field, then y, then z, each rounded to float32 before the next.
+ *
+ * BETWEEN LEVELS (fibd_warp_upsample).  The coarsest level starts from zero.  The level-l field becomes the start of level l - 1: fine
+ * voxel y takes S(q) of the coarse field at q_c = 0.5 y_c - 0.25 (exact in float32; S is SAMPLE with its clamp).  Displacements are mm
+ * and are not scaled.  niter[r] is the count of row r, the rows running from the COARSEST level (r = 0) to level 0; there is no other
+ * stopping rule.
+ *
+ * JACOBIAN MAP (fibd_warp_jacobian).  Per field voxel, D[c][k] = the difference rule of step 3 on component c of the field along voxel
+ * axis k; G[c][r] = (D[c][0] Linv[0][r] + D[c][1] Linv[1][r]) + D[c][2] Linv[2][r] with linv = float32(inv(L)), L the linear part of
+ * the field's vox2ras (row-major float[9]); J = G with 1 + G[c][c] on the diagonal;
+ *   m0 = J11 J22 - J12 J21,  m1 = J10 J22 - J12 J20,  m2 = J10 J21 - J11 J20,  det = (J00 m0 - J01 m1) + J02 m2,
+ * every product and difference rounded on its own.  A value <= 0 marks a fold: the estimate-side companion of fibd_warp_invert's err.
+ *
+ * DEVICE ENTRIES.  Asynchronous on `stream`, nothing is allocated, 64-bit offsets, one thread per field voxel, and no kernel waits for
+ * another workgroup.  fibd_nlreg_step: steps 1-5; reads `packed`, writes `out` (another packed field) and *cost = { double ssd;
+ * uint64_t count } in DEVICE memory (8-byte aligned); `work` (8-byte aligned, fibd_nlreg_step_work_size bytes) takes the workgroups'
+ * partials.  fibd_warp_smooth: step 6 from `packed` into `out` through `work` (a third packed field: 16 nvox bytes, 16-byte aligned);
+ * sigma == 0 copies.  fibd_warp_unpack: packed -> planar, the inverse of fibd_warp_pack.  FIB_ERR_INVALID: NULL pointers, non-positive
+ * sizes, a packed field that is not 16-byte aligned (volumes, disp and out of the Jacobian: 4 bytes), a short workspace, sigma outside
+ * [0, 4], niter < 0, levels outside 1 .. 4, a step that is not positive and finite, a singular vox2ras, ANY overlap between an output
+ * or the workspace and anything else the call touches; a dimension above 2^24 is FIB_ERR_UNSUPPORTED.
+ *
+ * RUN (fibd_nlreg_run).  The whole pyramid on device-resident volumes: the pyramids, the ranges (read back once: a constant level volume
+ * is FIB_ERR_INVALID), three packed fields of the level-0 size, the partials and a level's costs live in `work` (16-byte aligned,
+ * fibd_nlreg_work_size bytes).  `field` receives the packed level-0 field.  cost and count (HOST arrays, or NULL) are
+ * [levels][max(1, max niter)], row r for niter[r]; entries no iteration fills are NaN and 0.  The call waits on `stream` once for the
+ * ranges and once per level for that level's costs (not at all for a level when both are NULL).
+ *
+ * HOST FORMS.  fib_mri_nlreg: one volume `moving` against `fixed` on one device (FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED), on that device's
+ * lease; disp receives the planar field [3][nvox_f].  warped (or NULL) receives fibd_warp_volume of `moving` through the final field
+ * onto the fixed grid, FIB_VOL_TRILINEAR, 0 outside, with the three matrices warp_mats = { to_ras, to_field, from_ras } (48 floats:
+ * what the caller would hand fib_warp_volume, so the two agree bit for bit).  fib_warp_jacobian: the planar field in, the map out. */
+int fib_nlreg_level(const float fixed_vox2ras[16], const float moving_vox2ras[16], const float *post, int level, float step,
+                    float to_ras[16], float from_ras[16], float T[9], float *kappa);
+int fibd_nlreg_step_work_size(int nx, int ny, int nz, size_t *bytes);
+int fibd_nlreg_step(const float *fixed, int nxf, int nyf, int nzf, const float *moving, int nxm, int nym, int nzm, const float norm[4],
+                    const float to_ras[16], const float from_ras[16], const float T[9], float kappa, const void *packed, void *out,
+                    void *cost, void *work, size_t work_bytes, void *stream);
+int fibd_warp_smooth(const void *packed, int nx, int ny, int nz, float sigma, void *out, void *work, size_t work_bytes, void *stream);
+int fibd_warp_upsample(const void *coarse, int cx, int cy, int cz, void *out, int nx, int ny, int nz, void *stream);
+int fibd_warp_unpack(const void *packed, int nx, int ny, int nz, float *disp, void *stream);
+int fibd_warp_jacobian(const void *packed, int nx, int ny, int nz, const float linv[9], float *out, void *stream);
+int fibd_nlreg_work_size(const int32_t fixed_size[3], const int32_t moving_size[3], int levels, const int32_t *niter, size_t *bytes);
+int fibd_nlreg_run(const float *fixed, const int32_t fixed_size[3], const float fixed_vox2ras[16], const float *moving,
+                   const int32_t moving_size[3], const float moving_vox2ras[16], const float *post, int levels, const int32_t *niter,
+                   float sigma, float step, void *field, double *cost, int64_t *count, void *work, size_t work_bytes, void *stream);
+int fib_mri_nlreg(int device, const float *moving, const int32_t moving_size[3], const float moving_vox2ras[16], const float *fixed,
+                  const int32_t fixed_size[3], const float fixed_vox2ras[16], const float *post, int levels, const int32_t *niter,
+                  float sigma, float step, float *disp, double *cost, int64_t *count, const float *warp_mats, float *warped);
+int fib_warp_jacobian(int device, const float *disp, int nx, int ny, int nz, const float linv[9], float *out);
+
+/* ------------------------------------------------------------------------------------ */
 /* Host-buffer drop-in entry points (what the Julia wrapper ccalls)                       */
 /* ------------------------------------------------------------------------------------ */
 

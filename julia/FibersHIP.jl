@@ -717,6 +717,53 @@ function warp_invert(field::Array{Float32,4}, field_vox2ras::Matrix{Float32}, ou
   return invf, err
 end
 
+# ---- non-linear registration (NOT in the reference; "Non-linear registration" in include/fibers_hip.h) -----------------------------
+"mri_nlreg(moving, fixed; init, levels, niter, sigma, step, frame) — the displacement field (additive demons, a fixed number of
+iterations per level) that takes `moving` onto `fixed`.  `init`: the Xform of mri_register(moving, fixed) (in = moving, out = fixed);
+levels = 0: mri_register's default; niter: one count, or one per level from the coarsest; sigma in level voxels; step in mm (default: the
+smallest fixed voxel size).  Returns (field [nx, ny, nz, 3] on the fixed grid, post_ras2ras (fixed RAS -> moving RAS, what mri_warp and
+str_warp take with the field), warped [nx, ny, nz], cost [maxit, levels], count): warped equals mri_warp(field, fixed.vox2ras0, moving
+frame, moving.vox2ras0, size(fixed), fixed.vox2ras0; post_ras2ras) bit for bit."
+function mri_nlreg(moving::MRI, fixed::MRI; init::Union{Xform{Float32},Nothing}=nothing, levels::Integer=0, niter=30, sigma::Real=1.0,
+                   step::Real=minimum(Float32.(fixed.volres)), frame::Integer=1, device::Integer=0)
+  mvol = vol4(moving.vol)[:, :, :, frame:frame]; fvol = vol4(fixed.vol)[:, :, :, 1:1]
+  ms = Int32.(collect(size(mvol)[1:3])); fs = Int32.(collect(size(fvol)[1:3]))
+  mv = rowmajor(moving.vox2ras0); fv = rowmajor(fixed.vox2ras0)
+  if levels == 0
+    nl = Ref{Cint}(0)
+    GC.@preserve fs ms fib_check(ccall((:fib_reg_levels, libfibers), Cint, (Ptr{Int32}, Ptr{Int32}, Ref{Cint}), fs, ms, nl))
+    levels = Int(nl[])
+  end
+  n = niter isa Integer ? fill(Int32(niter), levels) : Int32.(collect(niter))
+  length(n) == levels || error("niter holds $(length(n)) counts for a pyramid of $levels levels (one per level, coarsest first)")
+  post64 = init === nothing ? Matrix{Float64}(I, 4, 4) : Float64.(Float32.(inv(Float64.(init.ras2ras))))
+  post = rowmajor(post64)
+  to_ras = Float64.(fixed.vox2ras0)
+  mats = hcat(vec(permutedims(Float32.(to_ras))), vec(permutedims(Float32.(inv(Float64.(fixed.vox2ras0)) * to_ras))),
+              vec(permutedims(Float32.(inv(Float64.(moving.vox2ras0)) * post64))))      # to_ras, to_field, from_ras of mri_warp, row-major
+  width = max(1, Int(maximum(n)))
+  field = Array{Float32,4}(undef, fs[1], fs[2], fs[3], 3); warped = Array{Float32,3}(undef, fs[1], fs[2], fs[3])
+  cost = Matrix{Float64}(undef, width, levels); count = Matrix{Int64}(undef, width, levels)
+  GC.@preserve mvol fvol ms fs mv fv post n field cost count mats warped fib_check(ccall((:fib_mri_nlreg, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Int32}, Cfloat, Cfloat,
+       Ptr{Float32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float32}, Ptr{Float32}),
+      device, mvol, ms, mv, fvol, fs, fv, init === nothing ? Ptr{Float32}(C_NULL) : pointer(post), levels, n, Float32(sigma), Float32(step),
+      field, cost, count, mats, warped))
+  return (field = field, post_ras2ras = Float32.(post64), warped = warped, cost = cost, count = count)
+end
+
+"warp_jacobian(field, field_vox2ras) — det(I + dd/dx) [nx, ny, nz] of a displacement field: a value <= 0 marks a fold"
+function warp_jacobian(field::Array{Float32,4}, field_vox2ras::Matrix{Float32}; device::Integer=0)
+  size(field, 4) == 3 || error("a displacement field has 3 frames")
+  linv = Matrix{Float32}(permutedims(Float32.(inv(Float64.(field_vox2ras[1:3, 1:3])))))     # row-major float[9]
+  nx, ny, nz = size(field)[1:3]
+  out = Array{Float32,3}(undef, nx, ny, nz)
+  GC.@preserve field linv out fib_check(ccall((:fib_warp_jacobian, libfibers), Cint,
+      (Cint, Ptr{Float32}, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}),
+      device, field, nx, ny, nz, linv, out))
+  return out
+end
+
 # ---- tract maps (NOT in the reference; the definitions are the "Tract maps" section of include/fibers_hip.h) ----------------------
 const FIB_DENSITY_MODES = Dict(:points => 0, :lines => 1, :endpoints => 2)
 const FIB_DENSITY_ACCUMULATE = 0x100
