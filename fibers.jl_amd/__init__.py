@@ -39,6 +39,10 @@ from .tractsel import (Connectome, str_connectome, str_connectome_device, str_ga
                        str_select_device, str_select_work_size, str_take)
 from .bundle import (Bundles, str_assign_device, str_bundles, str_centroids, str_centroids_device, str_profile, str_resample,  # noqa: F401
                      str_resample_device)
+# (the device tier of the tractogram weights is reached through the module: fixel.fixel_assign_device, fixel.fixel_td_device,
+# fixel.str_weights_device, fixel.str_weights_work_size)
+from . import fixel  # noqa: F401
+from .fixel import FixelOverflow, TractWeights, connectome_weighted, str_weights  # noqa: F401
 from .volxform import mri_xform, vol_xform_device, vol_xform_matrix, xfm_header  # noqa: F401
 # (the device tier of the registration is reached through the module: register.reg_hist_device, register.vol_halve_device,
 # register.vol_range_device, register.mri_register_device)

@@ -222,6 +222,19 @@ _PROTOS = {
     "fib_str_resample": (i32, [i32, vp, vp, i64, i64, C.POINTER(C.c_float * 3), i32, vp, vp]),
     "fib_str_assign": (i32, [i32, vp, i64, i32, vp, i32, C.POINTER(C.c_float * 3), f32, vp, vp, vp, vp]),
     "fib_str_centroids": (i32, [i32, vp, i64, i32, vp, vp, i32, i32, vp, vp]),
+    "fibd_fixel_quantise": (i32, [i32, i64, vp, vp, vp, f32, vp, vp, vp]),
+    "fibd_fixel_assign": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, f32, f32, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_fixel_td": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, C.c_uint64, vp]),
+    "fibd_fixel_mu": (i32, [vp, i64, vp, vp]),
+    "fibd_fixel_update": (i32, [vp, vp, i64, i64, vp, vp, i64, i32, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_fixel_cost": (i32, [vp, vp, i64, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_fixel_output": (i32, [vp, i64, vp, i64, vp, vp, vp, vp]),
+    "fibd_fixel_fit_work_size": (i32, [i64, C.POINTER(C.c_uint64)]),
+    "fibd_fixel_fit": (i32, [vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fibd_str_weights_work_size": (i32, [i64, i64, i32, i64, C.POINTER(C.c_uint64)]),
+    "fibd_str_weights": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
+    "fib_str_weights": (i32, [i32, vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, C.POINTER(C.c_double), vp,
+                              C.POINTER(i64)]),
     "fibd_stream_trace_lcm": (i32, [C.POINTER(StreamParams), vp, vp, f32, i32, i32, C.c_uint64, vp, i64, vp, i32, vp,
                                     C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]),
     "fibd_stream_pack_flags": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -310,7 +323,7 @@ def shutdown():
 
 def trim():
     """fib_trim: the host tier's buffers kept between calls (pinned ring, its device mirror, fib_stream's device buffers, the tracer's
-    workspace, the device buffers of the tract maps, the selection, the connectome and the bundle tools) go back to the driver; plans stay"""
+    workspace, the device buffers of the tract maps, the selection, the connectome, the bundle tools and the tractogram weights) go back to the driver; plans stay"""
     check(lib().fib_trim())
 
 

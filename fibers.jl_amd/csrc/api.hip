@@ -16,6 +16,7 @@
 // Every other host form but fib_xfm_apply runs on one device with blocking copies, under a DevLease (the worker, its lock, the device).
 // The tractogram forms (fib_str_*) take a TmLease, which adds the worker's buffer set; the five that take lines of any length walk them with
 // tm_walk_lines, in the chunks that fibh::next_line_chunk cuts (host_tier.h), and keep a body per chunk.
+// fib_str_weights cuts the same chunks with a size of its own (FIBERS_FIXEL_POINTS) and keeps the fixel ids of every chunk resident.
 // The volume, warp, structure-tensor, RUMBA and peak-finder forms keep nothing between calls: their buffers are local.  The two frame
 // resamplers share frame_checks / frame_chunks, the peak finders find_peaks_host; the sizes taken from the free memory are host_tier.h's.
 // The tracking forms (fib_stream, fib_stream_lcm, fib_prob_stream) return through one owner, fibh::TractArrays, and one download path,
@@ -168,6 +169,14 @@ struct DevState {
         fib::DevBuf<uint8_t> flip;
         fib::DevBuf<double> sums;
         fib::DevBuf<uint32_t> bcnt;
+        // fib_str_weights: the peak field, every line's count, and what stays resident for the iterations: ids, Aq, TDq, N_s, q
+        fib::DevBuf<float> fx_vec, fx_f, fx_w, fx_td;
+        fib::DevBuf<uint8_t> fx_mask;
+        fib::DevBuf<int32_t> fx_npts, fx_ids;
+        fib::DevBuf<uint64_t> fx_aq, fx_tdq, fx_nline;
+        fib::DevBuf<uint32_t> fx_q;
+        fib::DevBuf<double> fx_cost;
+        fib::DevBuf<int64_t> fx_state;
     };
     // each set is created by its first user (stream_worker, TmLease) and released as a whole by trim()
     std::unique_ptr<StreamBufs> sb;
@@ -1340,6 +1349,76 @@ extern "C" int fib_str_connectome(int device, const float *xyz, const int32_t *n
     RC(d2h(cmat, b.cmat.p, sizeof(uint32_t) * cells));
     if (wmat) RC(d2h(wmat, b.wmat.p, sizeof(double) * cells));
     *n_lines = total;
+    return FIB_OK;
+} FIB_API_CATCH
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// tractogram weights: host form.  One device; the points go up once, in chunks cut at line boundaries, only to make the fixel ids; the
+// ids, q, TDq and the field stay resident for the iterations.  FIBERS_FIXEL_POINTS=<n> overrides the points per chunk.
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_str_weights(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
+                               int32_t nvec, const float *const *ovec, const float *const *f, const uint8_t *mask, float f_thresh, float cos2,
+                               int niter, const uint32_t *q0, uint32_t *q, float *weights, float *td, double *mu, double *cost, int64_t *counts) try {
+    FIB_CHECK(nx > 0 && ny > 0 && nz > 0, FIB_ERR_INVALID, "volume dimensions must be positive");
+    FIB_CHECK(nvec >= 1 && nvec <= 3, FIB_ERR_INVALID, "nvec must be 1, 2 or 3, not %d", nvec);
+    FIB_CHECK(niter >= 0, FIB_ERR_INVALID, "niter must not be negative");
+    FIB_CHECK(f_thresh >= 0.0f, FIB_ERR_INVALID, "f_thresh must not be negative (amplitudes are positive)");
+    FIB_CHECK(ovec && f && td && mu && cost && counts && (nlines <= 0 || (q && weights)), FIB_ERR_INVALID, "NULL argument");
+    for (int k = 0; k < nvec; k++) FIB_CHECK(ovec[k] && f[k], FIB_ERR_INVALID, "peak %d is NULL", k);
+    RC(tm_host_check(npts, nlines, npoints));
+    FIB_CHECK(npoints == 0 || xyz, FIB_ERR_INVALID, "NULL xyz");
+    const size_t nvox = (size_t)nx * ny * nz, nfix = nvox * nvec;
+    FIB_CHECK(nfix < ((size_t)1 << 31) && npoints < ((int64_t)1 << 31), FIB_ERR_UNSUPPORTED, "the weights take fewer than 2^31 fixels and points");
+    int64_t chunk = TM_CHUNK_POINTS;
+    if (const char *e = fib::env("FIBERS_FIXEL_POINTS")) { const long long v = atoll(e); if (v > 0) chunk = v; }
+    TmLease lease;
+    RC(lease.take(device));
+    auto &b = *lease.b;
+    RC(b.fx_vec.ensure(3 * nfix)); RC(b.fx_f.ensure(nfix)); RC(b.fx_aq.ensure(nfix)); RC(b.fx_tdq.ensure(nfix)); RC(b.fx_td.ensure(nfix));
+    RC(b.fx_npts.ensure((size_t)nlines)); RC(b.fx_nline.ensure((size_t)nlines)); RC(b.fx_q.ensure((size_t)nlines)); RC(b.fx_w.ensure((size_t)nlines));
+    RC(b.fx_ids.ensure((size_t)npoints)); RC(b.fx_cost.ensure((size_t)niter + 1)); RC(b.fx_state.ensure(FIB_FIXEL_STATE_SLOTS));
+    const float *d_ovec[3] = {nullptr, nullptr, nullptr}, *d_f[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < nvec; k++) {
+        d_ovec[k] = b.fx_vec.p + 3 * nvox * k; d_f[k] = b.fx_f.p + nvox * k;
+        RC(h2d(b.fx_vec.p + 3 * nvox * k, ovec[k], sizeof(float) * 3 * nvox));
+        RC(h2d(b.fx_f.p + nvox * k, f[k], sizeof(float) * nvox));
+    }
+    if (mask) { RC(b.fx_mask.ensure(nvox)); RC(h2d(b.fx_mask.p, mask, nvox)); }
+    const uint8_t *d_mask = mask ? b.fx_mask.p : nullptr;
+    RC(fibd_fixel_quantise(nvec, (int64_t)nvox, d_ovec, d_f, d_mask, f_thresh, b.fx_aq.p, b.fx_state.p, nullptr));
+    int64_t total[2] = {0, 0}, p0 = 0;
+    for (int64_t l0 = 0; l0 < nlines;) {
+        const fibh::LineChunk c = fibh::next_line_chunk(npts, nlines, l0, chunk, fibh::LINES_UNBOUNDED);
+        const int64_t nl = c.l1 - l0, np = c.np;
+        size_t wb = 0;
+        RC(fibd_str_work_size(nl, &wb));
+        RC(b.work.ensure(wb)); RC(b.npts.ensure((size_t)nl)); RC(b.xyz.ensure((size_t)3 * np)); RC(b.nout.ensure(3));
+        RC(h2d(b.npts.p, npts + l0, sizeof(int32_t) * (size_t)nl));
+        if (np) RC(h2d(b.xyz.p, xyz + 3 * p0, sizeof(float) * 3 * (size_t)np));
+        RC(fibd_fixel_assign(b.xyz.p, b.npts.p, nl, np, nx, ny, nz, nvec, d_ovec, d_f, d_mask, f_thresh, cos2, b.fx_ids.p + p0, b.nout.p, b.work.p, wb,
+                             nullptr));
+        int64_t got[2] = {0, 0};
+        RC(d2h(got, b.nout.p, sizeof got));
+        FIB_CHECK(got[0] >= 0, FIB_ERR_INVALID, "internal error: the device refused a chunk the host accepted");
+        total[0] += got[0]; total[1] += got[1];
+        p0 += np; l0 = c.l1;
+    }
+    RC(h2d(b.fx_state.p + 5, total, sizeof total));
+    std::vector<uint32_t> start(q0 ? q0 : nullptr, q0 ? q0 + nlines : nullptr);
+    if (!q0) start.assign((size_t)nlines, 1u << 20);
+    if (nlines) { RC(h2d(b.fx_q.p, start.data(), sizeof(uint32_t) * (size_t)nlines)); RC(h2d(b.fx_npts.p, npts, sizeof(int32_t) * (size_t)nlines)); }
+    size_t wb = 0;
+    RC(fibd_fixel_fit_work_size(nlines, &wb));
+    RC(b.work.ensure(wb));
+    RC(fibd_fixel_fit(b.fx_ids.p, b.fx_npts.p, nlines, npoints, b.fx_aq.p, (int64_t)nfix, niter, b.fx_q.p, b.fx_w.p, b.fx_td.p, b.fx_cost.p, b.fx_state.p,
+                      b.fx_tdq.p, b.fx_nline.p, b.work.p, wb, nullptr));
+    int64_t state[FIB_FIXEL_STATE_SLOTS];
+    RC(d2h(state, b.fx_state.p, sizeof state));
+    if (nlines) { RC(d2h(q, b.fx_q.p, sizeof(uint32_t) * (size_t)nlines)); RC(d2h(weights, b.fx_w.p, sizeof(float) * (size_t)nlines)); }
+    RC(d2h(td, b.fx_td.p, sizeof(float) * nfix));
+    RC(d2h(cost, b.fx_cost.p, sizeof(double) * ((size_t)niter + 1)));
+    memcpy(mu, &state[1], sizeof(double));
+    for (int i = 0; i < 5; i++) counts[i] = state[5 + i];
     return FIB_OK;
 } FIB_API_CATCH
 

@@ -794,6 +794,98 @@ int fibd_str_centroids(const float *lines, int64_t nlines, int K, const int32_t 
                        int flags, double *sums, uint32_t *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Tractogram weights: fit line weights to fixel amplitudes (NOT in the reference)       */
+/* ------------------------------------------------------------------------------------ */
+/* A line count depends on seeding density, bundle length and curvature; a WEIGHT per line, chosen so that the weighted track density
+ * of every fibre population matches that population's amplitude, does not (what SIFT2, COMMIT and LiFE are for).  These definitions
+ * are this project's own; they are the contract.  The fit is a fixed number of ISRA steps (the multiplicative iteration for
+ * non-negative least squares), NOT SIFT2's line search: no decision depends on the data.
+ *
+ * INPUTS.  PACKED LINES exactly as for the tract maps above (xyz float32 [npoints][3], 1-based voxel coordinates, 4-byte alignment
+ * suffices; npts int32 [nlines]); the VOXEL OF A POINT, the INSIDE test and lin(v) are the ones defined there; npts is INVALID as
+ * defined there.  The PEAK FIELD is the arrays fibd_stream_field takes: ovec[k] planar float32 [3][nvox], f[k] float32 [nvox],
+ * k < nvec <= 3 (host arrays of nvec device pointers); mask uint8 [nvox] or NULL.  nvec * nvox < 2^31 and npoints < 2^31, else
+ * FIB_ERR_UNSUPPORTED (fixel ids are int32).  f_thresh >= 0 (amplitudes are positive), else FIB_ERR_INVALID.
+ *
+ * FIXEL.  phi = k * nvox + lin(v).  It EXISTS iff the mask is NULL or non-zero at v, f[k][v] is finite and > f_thresh, and the three
+ * components of ovec[k][v] are finite and not all zero.  The directions are taken as unit vectors; they are not renormalised.
+ *
+ * FIXEL OF A POINT.  A line with npts >= 2 has a tangent at every point: t_i = p_{i+1} - p_{i-1}, one-sided at the two ends
+ * (t_0 = p_1 - p_0, t_{n-1} = p_{n-1} - p_{n-2}), float32, component by component.  For every existing fixel k of the point's voxel
+ *   d_k = (t_x*u_x + t_y*u_y) + t_z*u_z       float32, every operation rounded on its own, no fused multiply-add.
+ * The point takes the k with the largest |d_k|: the candidates are compared in the order k = 0, 1, 2 with a strict >, so a tie goes
+ * to the smallest k and a NaN d_k is never taken.  The point KEEPS that fixel iff
+ *   d_k*d_k >= cos2 * ((t_x*t_x + t_y*t_y) + t_z*t_z)      by the same float32 rules; cos2 is a float32 the caller computes
+ * (cos^2 of the angle threshold).  A point is UNASSIGNED (fixel id -1) if it is outside, has a non-finite or all-zero tangent,
+ * belongs to a line with npts < 2, or has no kept fixel.  n_{s,phi} = the number of points of line s assigned to phi.  Counts stand
+ * for lengths: the input must have a UNIFORM STEP (fibd_stream_run, fibd_prob_run and fibd_str_resample write uniform steps).
+ *
+ * FIXED POINT, so that every sum is an integer sum.  A weight is a uint32 q in units of 2^-20: w = q * 2^-20, 0 <= w < 4096.  Every
+ * line starts at q = 2^20, or at the caller's q0.
+ *   a_scale = 2^30 / max f       float64; the max over the EXISTING fixels (a maximum has no order); 0 when no fixel exists
+ *   Aq_phi  = rint(f_phi * a_scale) as uint64 (f widened to float64, one product, rint ties to even); 0 where no fixel exists
+ *   TDq_phi = sum_s q_s * n_{s,phi}    uint64, by vector atomic adds on uint64 in any order; one add covers a run of consecutive
+ *             points of a line in the same fixel (runs are cut every 16 points of a line)
+ *   N_s = sum_i Aq_{phi(i)} over the assigned points of line s, once;  D_s = sum_i TDq_{phi(i)}, every iteration; both uint64
+ *   mu  = (double(sum Aq) / a_scale) / (double(sum TDq0) * 2^-20)   from the initial weights, float64, fixed for the whole call;
+ *         0 when no fixel exists or sum TDq0 = 0
+ * UPDATE (ISRA), float64, every operation rounded on its own, integer-to-double conversions round to nearest:
+ *   w' = ((q * 2^-20) * (double(N_s) / a_scale)) / (mu * (double(D_s) * 2^-20))
+ *   q' = rint(min(w', 4096 - 2^-20) * 2^20)
+ * A line with no assigned point, or with D_s = 0, gets q' = 0.  niter is fixed.  The sums are exact while every TDq < 2^44 and every
+ * line has at most 2^20 points; an update adds to `overflow` the number of ASSIGNED POINTS whose gathered TDq is >= 2^44 (summed over
+ * the iterations), and beyond that the uint64 sums wrap as uint64 sums do -- never silently: the Python tier raises on overflow != 0.
+ *
+ * OUTPUTS.  q uint32 [nlines]; weights float32 [nlines] = float32(q) * 2^-20 (one rounding); td float32 [nvec][nvox] =
+ * float32((double(TDq) * 2^-20) * mu), the fitted density on the scale of f, 0 where no fixel exists; cost float64 [niter + 1],
+ * cost[j] = sum_phi (mu * (double(TDq) * 2^-20) - double(Aq) / a_scale)^2 after j updates (a term with Aq = 0 takes 0 for the
+ * quotient).  Everything but cost is bit-exact.  The ORDER of the cost sum is free: it is within n * 2^-53 * sum|t| of the exact sum
+ * of its n terms t; the kernels add it in a fixed order, so two runs, and the device and host forms, give the same bytes.
+ * STATE: FIB_FIXEL_STATE_SLOTS slots of 8 bytes in device memory:
+ *   [0] a_scale (float64)  [1] mu (float64)  [2] sum Aq  [3] sum TDq0  [4] the bits of max f  [5] points unassigned, -1 for an
+ *   INVALID npts  [6] lines without an assigned point (empty lines included)  [7] lines at the clamp (q = 2^32 - 1)
+ *   [8] lines at q = 0  [9] overflow  [10..15] reserved.   [7], [8] describe the final q.
+ * INVALID npts (device forms): slot [5] is -1, no id is written, nothing is added and no weight is updated (q = q0). */
+#define FIB_FIXEL_STATE_SLOTS 16
+#define FIB_FIXEL_COST_WORK_BYTES 2048
+/* All: every array is a device pointer (ovec / f: host arrays of nvec device pointers), asynchronous on `stream`, no allocation and
+ * no synchronisation inside, no workgroup waits for another.  `work` of the line entries: fibd_str_work_size(nlines) bytes.
+ * quantise: zero-fills state, then writes slots [0], [2], [4] and aq uint64 [nvec * nvox]. */
+int fibd_fixel_quantise(int32_t nvec, int64_t nvox, const float *const *ovec, const float *const *f, const uint8_t *mask, float f_thresh,
+                        uint64_t *aq, void *state, void *stream);
+/* assign: ids int32 [npoints]; counts int64 [2] = {points unassigned or -1, lines without an assigned point} (state slots [5], [6]) */
+int fibd_fixel_assign(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz, int32_t nvec,
+                      const float *const *ovec, const float *const *f, const uint8_t *mask, float f_thresh, float cos2, int32_t *ids,
+                      int64_t *counts, void *work, size_t work_bytes, void *stream);
+/* td: zero-fills tdq uint64 [nfixels] and scatters q (uint32 [nlines]) along the ids; an id outside [0, nfixels) adds nothing */
+int fibd_fixel_td(const int32_t *ids, const int32_t *npts, int64_t nlines, int64_t npoints, const uint32_t *q, int64_t nfixels,
+                  uint64_t *tdq, void *work, size_t work_bytes, void *stream);
+/* mu: slots [3] and [1] from the TDq of the initial weights */
+int fibd_fixel_mu(const uint64_t *tdq, int64_t nfixels, void *state, void *stream);
+/* update: one ISRA step of q in place; first != 0: N_s is made and kept in nline (uint64 [nlines]), else read from it */
+int fibd_fixel_update(const int32_t *ids, const int32_t *npts, int64_t nlines, int64_t npoints, const uint64_t *aq, const uint64_t *tdq,
+                      int64_t nfixels, int first, void *state, uint64_t *nline, uint32_t *q, void *work, size_t work_bytes, void *stream);
+/* cost: one float64 in device memory; work: FIB_FIXEL_COST_WORK_BYTES */
+int fibd_fixel_cost(const uint64_t *aq, const uint64_t *tdq, int64_t nfixels, const void *state, double *cost, void *work, size_t work_bytes,
+                    void *stream);
+/* output: weights, td and slots [7], [8] from the final q and TDq */
+int fibd_fixel_output(const uint32_t *q, int64_t nlines, const uint64_t *tdq, int64_t nfixels, void *state, float *weights, float *td,
+                      void *stream);
+/* fit: everything behind quantise and assign on ids that stay resident -- the first scatter, mu, cost[0], then niter times update,
+ * scatter, cost -- and output.  q holds the start weights and receives the final ones.  work: fibd_fixel_fit_work_size(nlines). */
+int fibd_fixel_fit_work_size(int64_t nlines, size_t *bytes);
+int fibd_fixel_fit(const int32_t *ids, const int32_t *npts, int64_t nlines, int64_t npoints, const uint64_t *aq, int64_t nfixels, int niter,
+                   uint32_t *q, float *weights, float *td, double *cost, void *state, uint64_t *tdq, uint64_t *nline, void *work,
+                   size_t work_bytes, void *stream);
+/* the whole fit on device arrays: quantise, assign, fit, with ids, Aq, TDq and N_s in the caller's work area
+ * (fibd_str_weights_work_size bytes: 4 B a point, 16 B a fixel, 16 B a line and the scan).  q0 uint32 [nlines] or NULL. */
+int fibd_str_weights_work_size(int64_t nlines, int64_t npoints, int32_t nvec, int64_t nvox, size_t *bytes);
+int fibd_str_weights(const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz, int32_t nvec,
+                     const float *const *ovec, const float *const *f, const uint8_t *mask, float f_thresh, float cos2, int niter,
+                     const uint32_t *q0, uint32_t *q, float *weights, float *td, double *cost, void *state, void *work, size_t work_bytes,
+                     void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Probabilistic tracking: ODF-sampled streamlines (NOT in the reference)                */
 /* ------------------------------------------------------------------------------------ */
 /* Streamlines whose direction at every step is DRAWN from the ODF of the voxel ahead, restricted to a cone around the direction of
@@ -1274,6 +1366,15 @@ int fib_str_select(int device, const float *xyz, const int32_t *npts, int64_t nl
 int fib_str_connectome(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
                        const float volres[3], const int32_t *labels, const int32_t *remap, int64_t nremap, int nnodes, int flags,
                        uint32_t *cmat, double *wmat, int32_t *assign, int64_t *n_lines);
+/* host-buffer form of the tractogram weights (fibd_str_weights above): every array is host memory (ovec / f: nvec pointers to host
+ * arrays).  The points go to the device once, in chunks cut at line boundaries (2^22 points; FIBERS_FIXEL_POINTS=<n> overrides, in the
+ * product build too, as FIBERS_WARP_POINTS does), only to make the fixel ids; the ids, q, TDq and the field stay resident for the
+ * iterations.  q0 may be NULL.  *mu = state slot [1]; counts int64 [5] = state slots [5..9] (points unassigned, lines without an
+ * assigned point, lines at the clamp, lines at q = 0, overflow).  Everything it writes equals the device form's output byte for byte.
+ * npts < 0 or sum(npts) != npoints: FIB_ERR_INVALID before anything is written.  device = FIB_DEVICE_ALL: FIB_ERR_UNSUPPORTED. */
+int fib_str_weights(int device, const float *xyz, const int32_t *npts, int64_t nlines, int64_t npoints, int nx, int ny, int nz,
+                    int32_t nvec, const float *const *ovec, const float *const *f, const uint8_t *mask, float f_thresh, float cos2,
+                    int niter, const uint32_t *q0, uint32_t *q, float *weights, float *td, double *mu, double *cost, int64_t *counts);
 /* host-buffer forms of the bundle tools (fibd_str_resample / fibd_str_assign / fibd_str_centroids above): every array is host memory.
  * The lines go to the device in chunks cut at line boundaries; the models, and sums / counts, stay resident for the call.  Everything
  * fib_str_resample and fib_str_assign write equals the device form's output byte for byte (a line's result depends on the line

@@ -876,6 +876,39 @@ function str_connectome(tr::Tract{Float32}, labels::Array{Int32,3}; ids=sort(uni
   return Cm, (lengths ? map((w, c) -> c > 0 ? w / c : 0.0, W, Cm) : nothing), ids, assign
 end
 
+# ---- tractogram weights (NOT in the reference; "Tractogram weights" in include/fibers_hip.h) ----------------------------------------
+"""str_weights(tr, peak, f; mask, f_thresh, ang_thresh, niter, q0) -> (weights, q, td, mu, cost, counts) — a weight per line such that the
+weighted track density of every fixel (one peak in one voxel) matches the peak's amplitude.  `peak`: up to three `Array{Float32,4}`
+[nx,ny,nz,3] (e.g. `gqi.peak[k].vol`), `f`: their amplitudes `Array{Float32,3}`.  The lines must have a uniform step (point counts
+stand for lengths).  `niter` steps of ISRA from the weight 1 (or `q0`, UInt32 in units of 2^-20), not SIFT2's line search.  `counts` =
+(points unassigned, lines without an assigned point, lines at the clamp, lines at q = 0, overflow); a non-zero overflow is an error."""
+function str_weights(tr::Tract{Float32}, peak::Vector{Array{Float32,4}}, f::Vector{Array{Float32,3}};
+                     mask::Union{Array{UInt8,3},Nothing}=nothing, f_thresh::Real=0.03, ang_thresh::Real=45, niter::Integer=50,
+                     q0::Union{Vector{UInt32},Nothing}=nothing, device::Integer=0)
+  nvec = length(peak)
+  (1 <= nvec <= 3 && length(f) == nvec) || error("one to three orientation volumes and one amplitude volume for each")
+  dims = size(f[1])
+  xyz, npts = str_packed(tr)
+  nl = length(npts)
+  (isnothing(q0) || length(q0) == nl) || error("q0 must hold one weight per line")
+  q = Vector{UInt32}(undef, nl)
+  w = Vector{Float32}(undef, nl)
+  td = Array{Float32,4}(undef, dims[1], dims[2], dims[3], nvec)
+  cost = Vector{Float64}(undef, niter + 1)
+  mu = Ref{Float64}(0)
+  counts = zeros(Int64, 5)
+  pv = Ptr{Float32}[pointer(p) for p in peak]
+  pf = Ptr{Float32}[pointer(a) for a in f]
+  cos2 = Float32(cosd(Float64(ang_thresh))^2)
+  GC.@preserve xyz npts peak f pv pf mask q0 q w td cost counts fib_check(ccall((:fib_str_weights, libfibers), Cint,
+      (Cint, Ptr{Float32}, Ptr{Int32}, Int64, Int64, Cint, Cint, Cint, Int32, Ptr{Ptr{Float32}}, Ptr{Ptr{Float32}}, Ptr{UInt8}, Cfloat, Cfloat,
+       Cint, Ptr{UInt32}, Ptr{UInt32}, Ptr{Float32}, Ptr{Float32}, Ref{Float64}, Ptr{Float64}, Ptr{Int64}),
+      device, xyz, npts, nl, size(xyz, 2), dims[1], dims[2], dims[3], nvec, pv, pf, isnothing(mask) ? Ptr{UInt8}(C_NULL) : pointer(mask),
+      f_thresh, cos2, niter, isnothing(q0) ? Ptr{UInt32}(C_NULL) : pointer(q0), q, w, td, mu, cost, counts))
+  counts[5] == 0 || error("str_weights: $(counts[5]) gathered track densities reached 2^44 units, the integer sums are no longer exact")
+  return w, q, td, mu[], cost, counts
+end
+
 # ---- bundle tools (NOT in the reference; "Bundle tools" in include/fibers_hip.h) -----------------------------------------------------
 const FIB_CENTROIDS_ACCUMULATE = 0x100
 
