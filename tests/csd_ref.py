@@ -73,7 +73,9 @@ def rounded(t):
 
 def rec(s, X, B, Y, tau=0.1, niter=50, dtype=np.float64, perm=None):
     """s: float32 [nvox, nshell] shell samples; X, B, Y: float32 tables.  Returns dict(sh [nvox, n], odf [nvox, nreg], niter [nvox],
-    margin [nvox] (inf for a skipped voxel)) in `dtype`; a voxel without a positive sample is skipped (zeros)."""
+    margin [nvox] (inf for a skipped voxel)) in `dtype`; a voxel without a positive sample is skipped (zeros).  setmin, setmax [nvox]:
+    the smallest and the largest number of directions in the set over the voxel's passes (-1 for a skipped voxel): a kernel may sum
+    the set's rows or, where the set is the larger side (2 count > nreg), subtract the complement's, and these say which it met."""
     s = np.asarray(s, f32)
     X, B, Y = (np.asarray(a, f32).astype(dtype) for a in (X, B, Y))
     if perm is not None:
@@ -86,6 +88,7 @@ def rec(s, X, B, Y, tau=0.1, niter=50, dtype=np.float64, perm=None):
     odf = np.zeros((nvox, nreg), dtype)
     nit = np.zeros(nvox, np.int32)
     margin = np.full(nvox, np.inf)
+    setmin, setmax = np.full(nvox, -1, np.int64), np.full(nvox, -1, np.int64)
     for v in range(nvox):
         sv = s[v].astype(dtype)
         if not (s[v] > 0).any():
@@ -100,6 +103,8 @@ def rec(s, X, B, Y, tau=0.1, niter=50, dtype=np.float64, perm=None):
             with np.errstate(invalid="ignore", divide="ignore"):
                 margin[v] = min(margin[v], float(np.min(np.abs(a - thr)) / np.max(np.abs(a))))
             cur = a < thr
+            count = int(cur.sum())
+            setmin[v], setmax[v] = (count if setmin[v] < 0 else min(setmin[v], count)), max(setmax[v], count)
             if prev is not None and np.array_equal(cur, prev):
                 break
             Bs = B[cur]
@@ -109,7 +114,7 @@ def rec(s, X, B, Y, tau=0.1, niter=50, dtype=np.float64, perm=None):
             prev = cur
         sh[v] = f
         odf[v] = np.maximum(Y @ f, 0)
-    return dict(sh=sh, odf=odf, niter=nit, margin=margin)
+    return dict(sh=sh, odf=odf, niter=nit, margin=margin, setmin=setmin, setmax=setmax)
 
 
 def peaks(odf, verts, faces, npeak=3):

@@ -19,6 +19,12 @@ CASES = [((6, 5, 4), 16, 3, 2),       # M > N
          ((9, 8, 7), 64, 7, 4),
          ((3, 3, 3), 20, 3, 2),       # every voxel shares one patch, c runs over all 27 rows
          ((6, 5, 4), 2, 3, 1)]
+# More output voxels than the kernel has persistent workgroups (DN_MAXWG = 512 in csrc/denoise.hip, a voxel a ticket): every workgroup
+# goes round its loop at least twice.  Kept out of CASES, whose parametrisations stay as they are; (case, estimators held on the GPU).
+LARGE_CASES = [((13, 13, 13), 16, 3, 2),     # 2197 voxels = 4.3 x 512; M = 27 > N, r = 16
+               ((13, 13, 13), 40, 3, 3),     # M < N, r = 27 odd: the phantom index is live
+               ((11, 10, 10), 130, 5, 4)]    # 1100 voxels; r = 125, the longest replay
+LARGE_HELD = [(LARGE_CASES[0], "exp1"), (LARGE_CASES[0], "exp2"), (LARGE_CASES[1], "exp2"), (LARGE_CASES[2], "exp2")]
 SEED = 20
 
 

@@ -177,6 +177,32 @@ def test_restatement_orders_and_types(fj, tables):
     assert list(r1["niter"]) == [1, 1, 0]
 
 
+def test_restatement_reports_the_set_sizes(fj, tables):
+    """setmin / setmax of `rec`: with a threshold above every amplitude the set is all nreg directions on every pass, with one below
+    every amplitude it is empty (thr = tau B[0,0] f0[0] and f0[0] > 0; the second pass repeats the set, so one solve); a skipped voxel
+    reports -1; the permuted order reports the same sizes; a single fibre at tau = 0.1 leaves most directions, not all, under the
+    threshold (a sparse fODF); and the sizes bracket the first pass's and the last pass's own counts"""
+    bval, bvec, t = tables
+    V = fj.sphere_724.vertices
+    nreg = t["B"].shape[0]
+    s = np.stack([csd_ref.signal(bval, bvec, t["frames"], [V[i]], [1.0], *RESP) for i in (3, 90)]).astype(np.float32)
+    s = np.concatenate([s, -np.abs(s[:1])])
+    r = csd_ref.rec(s, t["X"], t["B"], t["Y"], tau=1e6)
+    assert list(r["setmin"]) == [nreg, nreg, -1] and list(r["setmax"]) == [nreg, nreg, -1] and list(r["niter"]) == [1, 1, 0]
+    r = csd_ref.rec(s, t["X"], t["B"], t["Y"], tau=-1e6)
+    assert list(r["setmin"]) == [0, 0, -1] and list(r["setmax"]) == [0, 0, -1] and list(r["niter"]) == [1, 1, 0]
+    r = csd_ref.rec(s, t["X"], t["B"], t["Y"])
+    rp = csd_ref.rec(s, t["X"], t["B"], t["Y"], perm=np.random.default_rng(4).permutation(len(t["frames"])))
+    assert np.array_equal(r["setmin"], rp["setmin"]) and np.array_equal(r["setmax"], rp["setmax"])
+    assert np.all(r["setmin"] <= r["setmax"]) and np.all(2 * r["setmax"][:2] > nreg) and np.all(r["setmax"][:2] < nreg)
+    one = csd_ref.rec(s, t["X"], t["B"], t["Y"], niter=1)                 # the first pass alone
+    assert np.array_equal(one["setmin"], one["setmax"]) and np.all(r["setmin"][:2] <= one["setmin"][:2]) and np.all(one["setmax"][:2] <= r["setmax"][:2])
+    # the count is that of the set the odf shows: after the last pass, the directions below thr are those the constraint holds down
+    a = t["B"].astype(np.float64) @ r["sh"][0]
+    thr = np.float64(np.float32(0.1)) * np.float64(t["B"][0, 0]) * np.linalg.lstsq(t["X"][:, :15].astype(np.float64), s[0].astype(np.float64), rcond=None)[0][0]
+    assert r["setmin"][0] <= int((a < thr).sum()) <= r["setmax"][0]
+
+
 def test_response_from_a_tensor_fit(fj):
     shape = (4, 3, 2)
     mk = lambda v: fj.MRI(np.full(shape + (1,), v, np.float32))    # noqa: E731

@@ -142,6 +142,79 @@ def test_launch_shapes_and_voxel_kinds(fj, torch_, nvox):
         print("300 voxels at lmax 8, 84 frames: d(odf) = %.3g, smallest margin %.3g" % (d, margin))
 
 
+K = 61           # distinct voxels of the large call: prime, so a wave's successive voxels (a stride of 8 x the grid apart) differ in kind
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+@pytest.mark.parametrize("lmax,name,ndir", [(8, "sphere_724", 84), (6, "sphere_642", 61), (2, "sphere_362", 7)])
+def test_more_voxels_than_one_round_of_the_grid(fj, torch_, lmax, name, ndir):
+    """csd_kernel (csrc/csd.hip) runs min(cdiv(nvox, 8), CUs x (B in LDS ? 1 : 2)) workgroups of CSD_NW = 8 waves, a voxel a wave a
+    round (the grid rule of fibd_csd_rec): with nvox = 2 cap + 8 + 3 every wave takes a second voxel, some a third, and the last
+    workgroup is partial.  Voxel i is a copy of voxel i % 61 of a small call that stays inside the first round and passes `hold`; every
+    seventh is masked out.  The large call must repeat the small one bit for bit, whatever a wave's previous voxel left in its LDS
+    (the factor, fw, sw) and registers; so must the small call again on the plan whose peak buffers the large one has grown.  B is in
+    LDS at lmax 8, read through the cache at 6 and 2 (n0 == n at 2)."""
+    sphere = getattr(fj, name)
+    cu = torch_.cuda.get_device_properties(0).multi_processor_count
+    cap = cu * W * (1 if lmax == 8 else 2)
+    nvox = 2 * cap + W + 3
+    label = "lmax %d, %s, %d frames, %d voxels" % (lmax, name, ndir, nvox)
+    bval, bvec = csd_ref.scheme(ndir, lmax)
+    plan = fj.CsdPlan(bval, bvec, RESP, sphere, lmax=lmax)
+    try:
+        t = plan.tables()
+        grid = min(-(-nvox // W), cu * (1 if lmax == 8 else 2))
+        print("%s: %d CUs, first round of csd_kernel's grid rule = %d voxels (%d workgroups x %d waves), %.2f rounds" % (
+            label, cu, cap, grid, W, nvox / (grid * W)))
+        assert grid * W == cap and nvox > 2 * cap and nvox % W, \
+            "%s does not pass two rounds of %d voxels (csd_kernel's grid rule in fibd_csd_rec, csrc/csd.hip, on %d CUs)" % (label, cap, cu)
+        assert K <= cap
+        s = voxels(bval, bvec, t["frames"], K, 7)
+        dwi = full_dwi(s, t["frames"], len(bval), 8)
+        ones = np.ones(K, np.uint8)
+        small = gpu_csd(fj, torch_, plan, dwi, ones)
+        hold(fj, small, s, ones, t, sphere, label + ": the %d distinct voxels" % K)
+        # both accumulation routes of P are met: the restatement says so, not the seed
+        r = csd_ref.rec(s, t["X"], t["B"], t["Y"])
+        solved = (s > 0).any(1)
+        larger, smaller = 2 * r["setmax"][solved] > plan.nreg, 2 * r["setmin"][solved] <= plan.nreg
+        print("%s: voxels with a pass whose set is the larger side %d, the smaller side %d, of %d solved" % (label, larger.sum(), smaller.sum(), solved.sum()))
+        assert larger.any() and smaller.any(), label + ": one side of the complement switch (2 count > nreg) is never met"
+        idx = np.arange(nvox) % K
+        mask = (np.arange(nvox) % 7 != 3).astype(np.uint8)
+        big = gpu_csd(fj, torch_, plan, dwi[:, idx], mask)
+        inside = mask != 0
+        assert cap % K and (2 * cap) % K                                                      # (successive voxels of a wave do differ)
+        for k in ("sh", "odf", "niter", "peak", "f"):
+            assert not big[k][~inside].any(), "%s: %s is not 0 in a masked voxel" % (label, k)
+            got, want = (np.ascontiguousarray(a, np.float32).view(np.uint32).reshape(nvox, -1) for a in (big[k], small[k][idx]))
+            bad = np.nonzero((got != want).any(1) & inside)[0]
+            assert not bad.size, "%s: %s differs from the small call in %d voxels, the first %s (rounds %s)" % (
+                label, k, bad.size, bad[:8], bad[:8] // cap)
+        again = gpu_csd(fj, torch_, plan, dwi, ones)
+        for k in small:
+            assert _same_bits(again[k], small[k]), "%s: %s of the small call differs after the large one" % (label, k)
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("ndir", [65, 128, 129, 255, 256])
+def test_shell_sizes_up_to_the_limit(fj, torch_, ndir):
+    """the sample load walks lane, lane + 64, ...: one frame past a wave, two and four waves' worth and one frame either side, up to
+    CSD_MAXSHELL = 256 (csrc/csd.hip), where the workgroup's LDS is largest"""
+    run_case(fj, torch_, "lmax 8, %d frames" % ndir, ndir, 8, fj.sphere_724, 13, 800 + ndir)
+
+
+def test_a_shell_past_the_limit_is_refused(fj):
+    bval, bvec = csd_ref.scheme(257, 8)
+    with pytest.raises(fj.FibersError) as e:
+        fj.CsdPlan(bval, bvec, RESP, fj.sphere_724, lmax=8)
+    assert e.value.code == -7 and "257" in str(e.value) and "256" in str(e.value), str(e.value)
+
+
 @pytest.mark.parametrize("kw", [dict(niter=1), dict(niter=2), dict(tau=0.0), dict(lam=0.1), dict(tau=0.3, lam=3.0)],
                          ids=["niter1", "niter2", "tau0", "lambda0.1", "tau0.3-lambda3"])
 def test_iteration_cap_threshold_and_weight(fj, torch_, kw):

@@ -194,6 +194,100 @@ def test_gpu_refusals(fj):
     assert not r.dwi.vol.any() and not r.sigma.vol.any() and np.all(r.rank.vol == 5)
 
 
+# ---- above the cap: more output voxels than persistent workgroups ---------------------------------------------------------------------
+DN_MAXWG = 512                        # csrc/denoise.hip: the persistent workgroups of dwi_denoise_kernel, one output voxel a ticket
+L1, L2, L3 = ref.LARGE_CASES
+_WHOLE = {}
+
+
+def _above_the_cap(nout, what):
+    """the precondition of every test below: each of the DN_MAXWG workgroups takes a second ticket, most a third"""
+    print("%s: %d output voxels over DN_MAXWG = %d workgroups (csrc/denoise.hip): %.1f tickets a workgroup" % (what, nout, DN_MAXWG, nout / DN_MAXWG))
+    assert nout > 2 * DN_MAXWG, "%s: %d output voxels do not send every one of DN_MAXWG = %d workgroups (csrc/denoise.hip) round its loop " \
+                                "twice; resize ref.LARGE_CASES" % (what, nout, DN_MAXWG)
+
+
+def _whole(fj, case, estimator="exp2"):
+    """one device call over the whole volume of a large case, run once and shared; do not modify"""
+    if (case, estimator) not in _WHOLE:
+        _above_the_cap(int(np.prod(case[0])), ref.case_id(case))
+        _WHOLE[case, estimator] = _device(fj, ref.case_volume(case), case[2], estimator)
+    return _WHOLE[case, estimator]
+
+
+@pytest.mark.parametrize("case,estimator", ref.LARGE_HELD, ids=lambda v: v if isinstance(v, str) else ref.case_id(v))
+def test_above_the_workgroup_cap_device_tier_matches_restatement(fj, case, estimator):
+    """2197 and 1100 output voxels against DN_MAXWG = 512 workgroups (csrc/denoise.hip): whatever G, y, lam, step_rot, s_cut, s_sig2
+    and the rotation records keep of a workgroup's previous voxel would show here, by the pass rule of the small cases"""
+    _hold(_whole(fj, case, estimator), case, estimator)
+
+
+def test_above_the_workgroup_cap_host_form_matches_restatement(fj):
+    _above_the_cap(int(np.prod(L1[0])), "host form, " + ref.case_id(L1))
+    r = fj.dwi_denoise(fj.MRI(ref.case_volume(L1)), patch=L1[2], estimator="exp2")
+    _hold((r.dwi.vol, r.sigma.vol[..., 0], r.rank.vol[..., 0]), L1, "exp2")
+
+
+@pytest.mark.parametrize("case,planes", [(L1, 3), (L2, 3), (L3, 4)], ids=lambda v: ref.case_id(v) if isinstance(v, tuple) else "%dplanes" % v)
+def test_whole_volume_equals_slabs_below_the_workgroup_cap(fj, case, planes):
+    """one call with nout > 2 DN_MAXWG (csrc/denoise.hip) against the same volume in z-slabs of at most DN_MAXWG = 512 output voxels,
+    where no workgroup takes a second ticket, each slab holding exactly its halo: dwi, sigma and rank bit for bit"""
+    import torch
+    vol, P = ref.case_volume(case), case[2]
+    nx, ny, nz, N = vol.shape
+    whole = _whole(fj, case)
+    assert nx * ny * planes <= DN_MAXWG, "a slab of %d planes has %d output voxels, more than DN_MAXWG = %d" % (planes, nx * ny * planes, DN_MAXWG)
+    for z0 in range(0, nz, planes):
+        z1 = min(z0 + planes, nz)
+        zin0 = ref.patch_start(z0, nz, P)
+        zin1 = ref.patch_start(z1 - 1, nz, P) + P
+        slab = _planar(np.asfortranarray(vol[:, :, zin0:zin1]))
+        m = torch.ones(nx * ny * (z1 - z0), dtype=torch.uint8, device="cuda")
+        o = fj.denoise.dwi_denoise_device(slab, m, (nx, ny, nz), P, zin0=zin0, z0=z0, z1=z1)
+        for w, k in zip(whole, ("dwi", "sigma", "rank")):
+            got = _host(o[k], (nx, ny, z1 - z0))
+            assert np.array_equal(_bits(got), _bits(w[:, :, z0:z1])), "%s of planes [%d, %d): %d values differ" % (
+                k, z0, z1, np.count_nonzero(_bits(got) != _bits(w[:, :, z0:z1])))
+
+
+def test_a_mask_that_interleaves_the_skip_and_the_solve(fj):
+    """every third voxel (by linear index) and one whole z-plane masked out, above DN_MAXWG = 512 (csrc/denoise.hip): successive tickets
+    alternate between the masked `continue` and a full solve.  Zero outside; inside, the bits of the full mask's run."""
+    vol, P = ref.case_volume(L2), L2[2]
+    nx, ny, nz, N = vol.shape
+    lin = np.arange(nx * ny * nz).reshape((nx, ny, nz), order="F")
+    m = (lin % 3 != 0) & (lin // (nx * ny) != 6)
+    assert not m[:, :, 6].any() and m[1, 0, 0] and not m[0, 0, 0] and m.sum() > 2 * DN_MAXWG
+    full, part = _whole(fj, L2), _device(fj, vol, P, mask=m)
+    for f, p, k in zip(full, part, ("dwi", "sigma", "rank")):
+        assert not p[~m].any(), k + " is not zero outside the mask"
+        assert np.array_equal(_bits(p[m]), _bits(f[m])), "%s: %d values differ inside the mask" % (k, np.count_nonzero(_bits(p[m]) != _bits(f[m])))
+
+
+def test_two_runs_above_the_workgroup_cap_give_identical_bits(fj):
+    """which workgroup draws which ticket differs from run to run; above DN_MAXWG = 512 (csrc/denoise.hip) so does what it solved before"""
+    a, b = _whole(fj, L2), _device(fj, ref.case_volume(L2), L2[2])
+    for u, v in zip(a, b):
+        assert np.array_equal(_bits(u), _bits(v))
+
+
+def test_workspace_above_the_workgroup_cap(fj):
+    """the workspace is DN_MAXWG = 512 (csrc/denoise.hip) rotation records whatever the volume: exactly that size serves, a byte less
+    is refused"""
+    import torch
+    vol, P = ref.case_volume(L2), L2[2]
+    nx, ny, nz, N = vol.shape
+    _above_the_cap(nx * ny * nz, "workspace, " + ref.case_id(L2))
+    n = 28                                                      # r = 27 rounded up to even
+    need = fj.denoise.dwi_denoise_work_size(nx, ny, nz, N, P)
+    assert need == 256 + DN_MAXWG * 24 * (n - 1) * (n // 2) * 8
+    exact = _device(fj, vol, P, work=torch.empty(need, dtype=torch.uint8, device="cuda"))
+    for u, v in zip(_whole(fj, L2), exact):
+        assert np.array_equal(_bits(u), _bits(v))
+    with pytest.raises(fj._dev.ArgError, match="dwi_denoise_work_size"):
+        _device(fj, vol, P, work=torch.empty(need - 1, dtype=torch.uint8, device="cuda"))
+
+
 def test_tensor_fit_of_the_denoised_series(fj):
     """dti_fit(dwi_denoise(dwi).dwi, mask) against dti_fit of the restatement's float32 output: fa to DESIGN.md §5's DTI tolerance"""
     from fibers_jl_amd import phantom

@@ -4,7 +4,8 @@ definitions (tests/fixel_ref.py, pinned by tests/test_fixel_ref.py).  Every sum 
 q, weights, td, mu and all counts are compared BIT FOR BIT.  cost is a float64 sum whose order is free: it is held to
 n * 2^-53 * sum|t| around the exact sum of its terms (math.fsum in the restatement), the bound the header states.
 
-Shapes: a 6 x 5 x 4 volume with nvec 1, 2 and 3; about 150 lines of 0 to 70 points and one line of 300."""
+Shapes: a 6 x 5 x 4 volume with nvec 1, 2 and 3; about 150 lines of 0 to 70 points and one line of 300.  One world of 48 x 40 x 24
+voxels with nvec 3 takes fx_cost past two rounds of its fixed grid."""
 import ctypes as C
 import os
 import sys
@@ -144,6 +145,77 @@ def test_device_tier_bit_for_bit(fj, dev, nvec):
     cost = _check_device_result(r, ref, "nvec %d" % nvec)
     assert cost[-1] < cost[0]
     again = fj.fixel.str_weights_device(dx, dn, SHAPE, ov, f, m, F_THRESH, 45, niter=6)     # the same call twice: the same bytes
+    for k in ("q", "weights", "td", "cost", "state"):
+        assert _same_bits(r[k].cpu().numpy(), again[k].cpu().numpy()), k
+
+
+BIG_SHAPE, BIG_NVEC = (48, 40, 24), 3
+FX_COST_GRID, TM_BLOCK = 256, 256      # csrc/fixel.hip: fx_cost's fixed grid and its workgroup, 65 536 fixels a round
+
+
+def _big_world():
+    """_world's field and lines on 48 x 40 x 24 voxels with three peaks: random peak fields (some amplitudes at or below the threshold),
+    a mask with holes, about 200 random walks and the hub lines.  Most fixels exist, so every round of a loop over the fixels adds to
+    the cost."""
+    rng = np.random.default_rng(77)
+    fld = Field(BIG_SHAPE, BIG_NVEC)
+    nvox = fld.nvox
+    for k in range(BIG_NVEC):
+        u = 0.35 * rng.standard_normal((3, nvox))
+        u[k] += 1
+        fld.ovec[k][:] = (u / np.linalg.norm(u, axis=0)).astype(np.float32)
+        fld.f[k][:] = (0.02 + 0.6 * rng.random(nvox) / (k + 1)).astype(np.float32)
+    hub = fld.lin((24, 20, 12))
+    fld.ovec[0][:, hub] = (1, 0, 0)
+    fld.f[0][hub] = 0.5
+    fld.f[1][fld.lin((2, 1, 1))] = np.nan
+    fld.ovec[2][:, fld.lin((48, 40, 24))] = 0                                          # the last fixel of all does not exist
+    mask = np.ones(nvox, np.uint8)
+    mask[rng.integers(0, nvox, 3000)] = 0
+    mask[hub] = 1
+    lines = [[], [(24, 20, 12)], [(23.6, 20, 12), (24.4, 20, 12)]]
+    for _ in range(200):
+        n = int(rng.integers(0, 71))
+        step = float(rng.choice([0.05, 0.25, 0.5, 1.0]))
+        p = np.array([1, 1, 1]) + rng.random(3) * (np.array(BIG_SHAPE) - 1)
+        d = rng.standard_normal(3) + 3 * np.eye(3)[int(rng.integers(0, 3))]
+        d /= np.linalg.norm(d)
+        pts = []
+        for _i in range(n):
+            pts.append(tuple(p))
+            d = d + 0.3 * rng.standard_normal(3)
+            d /= np.linalg.norm(d)
+            p = p + step * d
+        lines.append(pts)
+    for j in range(30):
+        y = 20 + 0.4 * (j / 29.0 - 0.5)
+        lines.append([(x, y, 12) for x in np.arange(22.0, 27.01, 0.25)])
+    xyz, npts = pack(lines)
+    return fld, mask, xyz, npts
+
+
+def test_more_fixels_than_two_rounds_of_the_cost_grid(fj, dev):
+    """fx_cost (csrc/fixel.hip) runs a fixed grid of FX_COST_GRID = 256 workgroups of TM_BLOCK = 256 threads, 65 536 fixels a round:
+    138 240 fixels are two whole rounds and a partial third.  Every integer quantity bit for bit and each cost within n 2^-53 sum|t| of
+    the restatement's exact sum, as for the small worlds; the same call twice gives the same bytes, cost included."""
+    import torch
+    fld, mask, xyz, npts = _big_world()
+    nfix, per_round = BIG_NVEC * fld.nvox, FX_COST_GRID * TM_BLOCK
+    print("%d fixels over fx_cost's %d x %d = %d a round: %.2f rounds" % (nfix, FX_COST_GRID, TM_BLOCK, per_round, nfix / per_round))
+    assert nfix > 2 * per_round and nfix % per_round, \
+        "%d fixels do not pass two rounds of FX_COST_GRID x TM_BLOCK = %d (csrc/fixel.hip) with a partial third" % (nfix, per_round)
+    ref = fx.weights(xyz, npts, BIG_SHAPE, fld.ovec, fld.f, mask, F_THRESH, fx.cos2_of(45), 2)
+    terms = fx.cost_terms(ref["aq"], ref["tdq"], ref["mu"], ref["a_scale"])
+    rounds = [terms[r * per_round:(r + 1) * per_round].sum() for r in range(3)]
+    print("the last cost by rounds of the grid: %s of %.6g; bound %.3g" % (rounds, ref["cost"][-1], ref["cost_bound"][-1]))
+    assert min(rounds) > 1000 * ref["cost_bound"][-1]                                   # a round left out or added twice is far outside the bound
+    assert (ref["ids"] >= 0).sum() > 1000 and len(set((ref["ids"][ref["ids"] >= 0] // fld.nvox).tolist())) == BIG_NVEC
+    ov, f, m = _dev_field(fld, mask, dev)
+    dx, dn = torch.from_numpy(xyz).to(dev), torch.from_numpy(npts).to(dev)
+    r = fj.fixel.str_weights_device(dx, dn, BIG_SHAPE, ov, f, m, F_THRESH, 45, niter=2)
+    cost = _check_device_result(r, ref, "%d fixels" % nfix)
+    assert cost.size == 3
+    again = fj.fixel.str_weights_device(dx, dn, BIG_SHAPE, ov, f, m, F_THRESH, 45, niter=2)
     for k in ("q", "weights", "td", "cost", "state"):
         assert _same_bits(r[k].cpu().numpy(), again[k].cpu().numpy()), k
 

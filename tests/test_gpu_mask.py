@@ -213,6 +213,66 @@ def test_histogram_and_otsu(fj, name):
         assert got_info["n_above"] == 1 and got_mask.reshape(-1, order="F")[-1] == 1
 
 
+VM_T, VM_MAX_BLOCKS = 256, 2048        # csrc/volmask.hip: the workgroup, and the min(vm_blocks(n), 2048) grid of vm_minmax_kernel / vm_hist_kernel
+BIG_SHAPE = (81, 81, 81)
+
+
+@functools.lru_cache(maxsize=None)
+def _big_b0():
+    """one frame of 81^3 = 531 441 voxels, 7153 more than one round of the capped grid: a positive skewed background, a brighter half
+    (z >= 40) with an enclosed dark cavity across the voxel where the second round starts, and -- all past that voxel -- voxels brighter
+    still (enough of them to move Otsu's k*), the finite extremes, a NaN, a +Inf and a -Inf"""
+    rng = np.random.default_rng(12)
+    n, per_round = int(np.prod(BIG_SHAPE)), VM_T * VM_MAX_BLOCKS
+    flat = rng.gamma(2.0, 20.0, n) + 1.0
+    flat[np.arange(n) // (81 * 81) >= 40] += 400.0
+    flat[per_round:] += 500.0
+    v = flat.astype(np.float32).reshape(BIG_SHAPE, order="F")
+    x, y, z = per_round % 81, (per_round // 81) % 81, per_round // (81 * 81)
+    assert (z, 1 <= x < 80, 1 <= y < 80) == (79, True, True)
+    v[x - 1:x + 2, y - 1:y + 2, 78:80] = 0.5                  # the cavity: closed by z = 77 and the face plane z = 80
+    f = v.reshape(-1, order="F")
+    assert np.shares_memory(f, v)
+    f[per_round + 100], f[per_round + 2000] = 0.25, 1500.0    # lo and hi
+    f[per_round + 300], f[per_round + 301], f[per_round + 4000] = np.nan, np.inf, -np.inf
+    v.setflags(write=False)
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def _big_ref(flags):
+    return ref.mask_from_b0(_big_b0(), numpass=0, flags=flags, dilate_passes=0)
+
+
+@pytest.mark.parametrize("flags", [0, 3], ids=["threshold", "largest+holes"])
+def test_more_voxels_than_one_round_of_the_capped_grid(fj, flags):
+    """vm_minmax_kernel and vm_hist_kernel (csrc/volmask.hip) run min(vm_blocks(n), 2048) workgroups of VM_T = 256 threads and stride on:
+    524 288 voxels a round.  The extremes and the non-finite values lie in the second round, and its voxels move k*: lo, hi, kstar, the
+    counts and the mask are the restatement's bit for bit only if both loops go round (the test asserts that the first round alone gives
+    other extremes and another k*)."""
+    import torch
+    b0 = _big_b0()
+    n, per_round = b0.size, VM_T * VM_MAX_BLOCKS
+    print("%d voxels over min(vm_blocks, %d) x %d = %d a round: %.3f rounds" % (n, VM_MAX_BLOCKS, VM_T, per_round, n / per_round))
+    assert n > per_round, "%d voxels stay inside one round of the 2048 x VM_T = %d of vm_minmax_kernel / vm_hist_kernel (csrc/volmask.hip)" % (n, per_round)
+    want_mask, want_info = _big_ref(flags)
+    first = b0.reshape(-1, order="F")[:per_round]
+    r1 = ref.finite_range(first)
+    assert (r1[0], r1[1]) != (want_info["lo"], want_info["hi"]) and want_info["lo"] == np.float32(0.25) and want_info["hi"] == np.float32(1500.0)
+    b1 = ref.bins(first, want_info["lo"], want_info["hi"])
+    k1 = ref.otsu(np.bincount(b1[b1 >= 0], minlength=256))
+    print("lo, hi of the first round %s, of the volume %s; k* of the first round's histogram %d, of the volume's %d" % (
+        r1, (want_info["lo"], want_info["hi"]), k1, want_info["kstar"]))
+    assert k1 != want_info["kstar"], "the histogram of the first round alone gives the same k*: vm_hist_kernel's second round would not show"
+    assert want_info["status"] == 0 and 0 < want_info["n_above"] < n
+    if flags == 3:
+        # the holes: the cavity's 18 voxels, the voxel at lo, and the NaN with the +Inf beside it (the -Inf and hi lie on the face z = 80)
+        assert want_info["n_filled"] == 18 + 1 + 2 and want_info["n_components"] > 1 and want_info["n_kept"] < want_info["n_above"]
+    o = fj.mask.dwi_mask_device(_dev(b0).reshape(1, -1), BIG_SHAPE, [0], numpass=0, keep_largest=bool(flags & 1), fill_holes=bool(flags & 2), dilate=0)
+    torch.cuda.synchronize()
+    _hold(_host(o["mask"], BIG_SHAPE), fj.mask.info_dict(o["info"]), want_mask, want_info)
+
+
 # ---- components, holes, dilation ------------------------------------------------------------------------------------------------------
 def _serpentine():
     m = np.zeros((16, 16, 4), bool)
