@@ -12,6 +12,10 @@ from .dki import DKI, DkiPlan, dki_design, dki_fit, dki_fit_device  # noqa: F401
 # (the device tier of csd_rec is reached through the module: csd.csd_rec_device)
 from . import csd  # noqa: F401
 from .csd import CSD, CsdPlan, csd_design, csd_rec, csd_response, csd_write  # noqa: F401
+# (the device tier of msmt_rec likewise: msmt.msmt_rec_device)
+from . import msmt  # noqa: F401
+from .msmt import (MSMT, MsmtPlan, MsmtResponse, msmt_design, msmt_rec, msmt_response, msmt_shells, msmt_wm_response,  # noqa: F401
+                   msmt_write)
 # (the device tier of dwi_denoise is reached through the module: denoise.dwi_denoise_device)
 from . import denoise  # noqa: F401
 from .denoise import Denoised, dwi_denoise  # noqa: F401

@@ -48,6 +48,16 @@ class CsdOut(C.Structure):
     _fields_ = [("sh", C.c_void_p), ("odf", C.c_void_p), ("niter", C.c_void_p), ("peak", C.c_void_p * 3), ("f", C.c_void_p * 3)]
 
 
+class MsmtParams(C.Structure):
+    _fields_ = [("lmax", C.c_int), ("niso", C.c_int), ("b0_thresh", C.c_float), ("b_tol", C.c_float), ("lam", C.c_float),
+                ("lam_iso", C.c_float), ("tau", C.c_float), ("niter", C.c_int)]
+
+
+class MsmtOut(C.Structure):
+    _fields_ = [("sh", C.c_void_p), ("iso", C.c_void_p * 2), ("odf", C.c_void_p), ("niter", C.c_void_p), ("peak", C.c_void_p * 3),
+                ("f", C.c_void_p * 3)]
+
+
 FIB_MASK_KEEP_LARGEST, FIB_MASK_FILL_HOLES = 1, 2
 
 
@@ -109,6 +119,12 @@ _PROTOS = {
     "fib_csd_plan_destroy": (None, [vp]),
     "fib_csd_plan_tables": (i32, [vp, vp, C.POINTER(i32), vp, vp, vp, vp]),
     "fibd_csd_rec": (i32, [vp, vp, vp, i64, C.POINTER(CsdOut), vp]),
+    "fib_msmt_wm_response": (i32, [f32, f32, f32, vp, i32, i32, vp]),
+    "fib_msmt_design": (i32, [vp, vp, i32, vp, i32, C.POINTER(MsmtParams), vp, vp, i32, vp, C.POINTER(i32), vp, vp, vp, vp, C.POINTER(i32)]),
+    "fib_msmt_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, C.POINTER(MsmtParams), vp, vp, i32, C.POINTER(vp)]),
+    "fib_msmt_plan_destroy": (None, [vp]),
+    "fib_msmt_plan_tables": (i32, [vp, vp, C.POINTER(i32), vp, vp, vp, vp]),
+    "fibd_msmt_rec": (i32, [vp, vp, vp, i64, C.POINTER(MsmtOut), vp]),
     "fib_gqi_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, f32, C.POINTER(vp)]),
     "fib_dsi_plan_create": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, i32, C.POINTER(vp)]),
     "fib_gqi_plan_create_fmt": (i32, [i32, vp, vp, i32, vp, i32, vp, i32, f32, i32, C.POINTER(vp)]),
@@ -247,6 +263,8 @@ _PROTOS = {
     "fib_adc_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
     "fib_dki_fit": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, C.POINTER(DkiParams), C.POINTER(DkiOut)]),
     "fib_csd_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(CsdParams), C.POINTER(CsdOut)]),
+    "fib_msmt_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(MsmtParams), vp, vp, i32,
+                           C.POINTER(MsmtOut)]),
     "fib_gqi_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, P3, P3]),
     "fib_dsi_rec": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, P3, P3]),
     "fib_rumba_plan_create": (i32, [i32, vp, vp, i32, vp, i32, f32, f32, f32, f32, C.POINTER(vp)]),

@@ -607,6 +607,52 @@ extern "C" int fib_csd_rec(int device, const float *dwi, int nx, int ny, int nz,
                                  });
 } FIB_API_CATCH
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// msmt_rec
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int fib_msmt_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
+                            const void *mask, int mask_dtype, const float *bval, const float *bvec,
+                            const float *verts, int nverts, const int32_t *faces, int nfaces, const fib_msmt_params *params,
+                            const float *wm_R, const float *iso_r, int nshells, const fib_msmt_out *out) try {
+    FitCall c;
+    const int niso = params ? std::min(std::max(params->niso, 0), 2) : 0;
+    RC(fit_call(c, device, bval, nvol, bvec != nullptr, dwi && mask && out && params && wm_R, nx, ny, nz, mask_dtype,
+                out && out->sh && out->odf && out->niter && out->peak[0] && out->peak[1] && out->peak[2] && out->f[0] && out->f[1] && out->f[2] &&
+                    (niso < 1 || out->iso[0]) && (niso < 2 || out->iso[1]),
+                "NULL output volume", verts && faces && nverts >= 2 && nverts % 2 == 0 && nfaces > 0));
+    // the refusals of the design come before any device is touched, and give the output rows their counts
+    int rank = 0;
+    RC(fib_msmt_design(bval, bvec, nvol, verts, nverts, params, wm_R, iso_r, nshells, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &rank));
+    const int nwm = (params->lmax + 1) * (params->lmax + 2) / 2, nreg = nverts / 2, nl = params->lmax / 2 + 1;
+    const std::vector<Rows> ins = {{dwi, nullptr, nvol}};
+    std::vector<Rows> outs = {{nullptr, out->sh, nwm}};
+    for (int t = 0; t < niso; t++) outs.push_back({nullptr, out->iso[t], 1});
+    for (const Rows &r : std::vector<Rows>{{nullptr, out->odf, nreg}, {nullptr, out->niter, 1},
+                                           {nullptr, out->peak[0], 3}, {nullptr, out->peak[1], 3}, {nullptr, out->peak[2], 3},
+                                           {nullptr, out->f[0], 1}, {nullptr, out->f[1], 1}, {nullptr, out->f[2], 1}}) outs.push_back(r);
+    std::string key;
+    key_add(key, "msmt", 4);
+    key_add(key, bval, sizeof(float) * nvol);
+    key_add(key, bvec, sizeof(float) * 3 * nvol);
+    key_add(key, verts, sizeof(float) * 3 * nverts);
+    key_add(key, faces, sizeof(int32_t) * 3 * nfaces);
+    key_add(key, params, sizeof *params);
+    key_add(key, wm_R, sizeof(float) * nshells * nl);
+    key_add(key, iso_r, niso ? sizeof(float) * niso * nshells : 0);
+    return fit_run<fib_msmt_plan>(c, ins, mask, outs,
+                                  [&](DevState &d, fib_msmt_plan **p) {
+                                      return cached_plan<fib_msmt_plan, fib_msmt_plan_destroy>(d, key, [&](fib_msmt_plan **q) {
+                                          return fib_msmt_plan_create(d.device, bval, bvec, nvol, verts, nverts, faces, nfaces, params, wm_R, iso_r,
+                                                                      nshells, q); }, p);
+                                  },
+                                  [&](const fib_msmt_plan *plan, const float *din, const uint8_t *dm, int64_t nv, float *b, hipStream_t st) -> int {
+                                      float *is = b + (int64_t)nwm * nv, *od = is + (int64_t)niso * nv, *pk = od + (int64_t)(nreg + 1) * nv;
+                                      fib_msmt_out dev{b, {niso > 0 ? is : nullptr, niso > 1 ? is + nv : nullptr}, od, od + (int64_t)nreg * nv,
+                                                       {pk, pk + 3 * nv, pk + 6 * nv}, {pk + 9 * nv, pk + 10 * nv, pk + 11 * nv}};
+                                      return fibd_msmt_rec(plan, din, dm, nv, &dev, st);
+                                  });
+} FIB_API_CATCH
+
 extern "C" int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigvec, float *eigval) try {
     FIB_CHECK(S && eigvec && eigval, FIB_ERR_INVALID, "NULL argument");
     FIB_CHECK(nvox > 0, FIB_ERR_INVALID, "nvox must be positive");

@@ -53,7 +53,7 @@ def _raise_on_overflow(n):
 
 
 def _field(peak, f):
-    """(peak list, f list) from lists of MRI / arrays, or from a GQI / DSI / CSD result (its .peak and .qa / .f)"""
+    """(peak list, f list) from lists of MRI / arrays, or from a GQI / DSI / CSD / MSMT result (its .peak and .qa / .f)"""
     if f is None:
         res = peak
         peak = res.peak
@@ -66,7 +66,7 @@ def str_weights(tr: Tract, peak, f=None, mask=None, f_thresh: float = 0.03, ang_
                 device: int = 0) -> TractWeights:
     """A weight for every line of `tr` such that the weighted track density of every fixel matches its amplitude.  `peak` / `f`: lists
     of `MRI` (orientation volumes [nx, ny, nz, 3] and their amplitudes, as `stream` takes them; at most 3), or a `GQI` / `DSI` / `CSD`
-    result as `peak` alone, whose `.peak` and `.qa` / `.f` are used.  A fixel exists where the mask is non-zero, the amplitude is
+    / `MSMT` result as `peak` alone, whose `.peak` and `.qa` / `.f` are used.  A fixel exists where the mask is non-zero, the amplitude is
     finite and above `f_thresh` and the direction is finite and not zero; a point belongs to the fixel of its voxel best aligned with
     the line's tangent if that lies within `ang_thresh` degrees.  Point counts stand for lengths: the lines must have a UNIFORM STEP
     (`stream`, `prob_stream` and `str_resample` write uniform steps).  The fit is `niter` steps of ISRA (the multiplicative update of

@@ -313,7 +313,7 @@ def write_struct(obj, basename):
                 mri_write(v, "%s_%s%d.nii.gz" % (basename, name, k))
 
 
-dti_write = gqi_write = dsi_write = csd_write = write_struct
+dti_write = gqi_write = dsi_write = csd_write = msmt_write = write_struct
 
 
 def rumba_write(rumba, basename):

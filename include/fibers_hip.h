@@ -256,6 +256,77 @@ int fib_csd_plan_tables(const fib_csd_plan *plan, int32_t *frames, int *nshell, 
  * voxel.  The plan holds the peak finder's scratch of the call: one call at a time per plan. */
 int fibd_csd_rec(const fib_csd_plan *plan, const float *dwi, const uint8_t *mask, int64_t nvox, const fib_csd_out *out, void *stream);
 
+/* ---- Multi-shell multi-tissue deconvolution (not in the reference; this section and DESIGN.md §5 are the definition) ----
+ * After Jeurissen et al. 2014: the signal of ALL shells is decomposed into a white-matter fODF and isotropic tissue fractions.  Where this
+ * section is silent, "Constrained spherical deconvolution" above applies unchanged: basis, column order, float64 arithmetic from the
+ * float32 loads on, outputs rounded once.
+ * Shells: b is taken as float32.  Frames with b <= b0_thresh form shell 0 (it may be empty).  The other frames are walked in ascending b,
+ *   ties in frame order: a frame joins the current shell while b <= (1 + 2 b_tol) b_first (float64 arithmetic on the float32 values),
+ *   b_first the smallest b of that shell; otherwise it opens a new shell.  nshells counts shell 0.  bbar_s = the float64 mean of the shell's
+ *   float32 b values (0 for an empty shell 0).  More than 8 shells above b0_thresh, or more than 512 frames in all, is FIB_ERR_UNSUPPORTED;
+ *   a frame of a shell >= 1 with a zero bvec row is FIB_ERR_INVALID.  Every frame of the series is read: there is no unused frame.
+ * Tissues: tissue 0 is white matter, anisotropic, n_wm = (lmax + 1)(lmax + 2) / 2 coefficients, lmax in {2, 4, 6, 8}; then niso in
+ *   {0, 1, 2} isotropic tissues (by convention GM, then CSF), one coefficient each.  n = n_wm + niso <= 47; column order: the WM harmonics,
+ *   then the isotropic tissues.
+ * Responses are tables, not a model: wm_R [nshells][lmax / 2 + 1] row-major holds R_l per shell (the R_l of the section above),
+ *   iso_r [niso][nshells] row-major the tissue's mean signal in each shell; both float32.  A table for another number of shells than the
+ *   walk finds is FIB_ERR_INVALID.
+ * Tables, built in float64 from those and rounded once to float32:
+ *   X [nvol x n]: a shell-0 row is [Y_00 R_0(0), 0, ..], whatever its bvec says; a row of shell s >= 1 is Y(bvec) diag(R_l(s)); column
+ *     n_wm + t is iso_r[t][shell(frame)].
+ *   Y [nreg x n]: the basis at the first-half vertices, zero isotropic columns.
+ *   B [(nreg + niso) x n]: row i < nreg is Y_i lambda (sum over frames of R_0(shell(frame))) / nreg (with one shell and no b0 frame the
+ *     scaling of the section above); row nreg + t is lambda_iso (sum over frames of iso_r[t][shell(frame)]) e_{n_wm + t}.
+ *   nvol < n, or an X whose rank (fib_dki_design's rule) is below n, is FIB_ERR_INVALID: this refuses two isotropic tissues on a series
+ *   of fewer than three distinct shells (shell 0 counted).
+ * Per voxel (skipped, all outputs 0, when the mask is 0 or no sample is > 0), with s all nvol samples:
+ *   f = the least-squares solution on the WM columns of l <= 4 together with the isotropic columns, every other coefficient 0;
+ *   thr_i = tau B[0,0] f[0] for i < nreg, 0 for the isotropic rows;
+ *   repeat up to niter times:  a = B f;  set = {i : a_i < thr_i};  from the second pass on, stop if the set equals the previous one;
+ *     solve (X'X + sum_{i in set} b_i b_i') f = X's by Cholesky.
+ *   sh = f[0 : n_wm];  iso[t] = f[n_wm + t], NOT clamped (a negative fraction is diagnostic);  odf = max(Y f, 0);  niter = the number
+ *   of solves;  peak[k], f[k] as in the section above. */
+typedef struct fib_msmt_plan fib_msmt_plan;
+typedef struct {
+    int lmax;                /* 2, 4, 6 or 8 */
+    int niso;                /* 0, 1 or 2 isotropic tissues */
+    float b0_thresh;         /* 50 */
+    float b_tol;             /* 0.05 */
+    float lambda;            /* weight of the WM constraint rows (1) */
+    float lambda_iso;        /* weight of the isotropic constraint rows (1) */
+    float tau;               /* WM threshold as a fraction of the initial mean amplitude (0) */
+    int niter;               /* most solves per voxel (50) */
+} fib_msmt_params;
+/* sh [n_wm][nvox], iso[t] [nvox] for t < niso (the others are not read), odf [nreg][nvox], niter [nvox], peak[k] [3][nvox], f[k] [nvox] */
+typedef struct {
+    float *sh;
+    float *iso[2];
+    float *odf, *niter;
+    float *peak[3];
+    float *f[3];
+} fib_msmt_out;
+/* Host only: R [nshells][lmax / 2 + 1] of a prolate tensor (lambda_para, lambda_perp) with b = 0 signal s0 at each bbar[s], by the 64-point
+ * quadrature of the section above in float64, rounded once. */
+int fib_msmt_wm_response(float lambda_para, float lambda_perp, float s0, const double *bbar, int nshells, int lmax, float *R);
+/* Host only (no device needed).  shell [nvol] receives the shell of every frame, *nshells their number, bbar [9] their mean b; they are
+ * filled even when the series is refused.  With wm_R NULL only this shell walk is made (verts and iso_r are not read).  Otherwise
+ * X [nvol x n], B [(nreg + niso) x n], Y [nreg x n] column-major and *rank are filled whenever nshells_in matches and nvol >= n.  Any
+ * output pointer may be NULL.  verts [nverts x 3] column-major. */
+int fib_msmt_design(const float *bval, const float *bvec, int nvol, const float *verts, int nverts, const fib_msmt_params *params,
+                    const float *wm_R, const float *iso_r, int nshells_in, int32_t *shell, int *nshells, double *bbar,
+                    float *X, float *B, float *Y, int *rank);
+/* faces [nfaces x 3] column-major, 1-based: the peak finder's neighbour table.  Tessellations of more than 384 directions are
+ * FIB_ERR_UNSUPPORTED. */
+int fib_msmt_plan_create(int device, const float *bval, const float *bvec, int nvol, const float *verts, int nverts,
+                         const int32_t *faces, int nfaces, const fib_msmt_params *params, const float *wm_R, const float *iso_r,
+                         int nshells_in, fib_msmt_plan **plan);
+void fib_msmt_plan_destroy(fib_msmt_plan *plan);
+/* host copies of the plan's tables, as fib_msmt_design returns them; any pointer may be NULL */
+int fib_msmt_plan_tables(const fib_msmt_plan *plan, int32_t *shell, int *nshells, double *bbar, float *X, float *B, float *Y);
+/* dwi [nvol][nvox] planar, mask uint8 [nvox].  Every output is written in every voxel.  The plan holds the peak finder's scratch of the
+ * call: one call at a time per plan. */
+int fibd_msmt_rec(const fib_msmt_plan *plan, const float *dwi, const uint8_t *mask, int64_t nvox, const fib_msmt_out *out, void *stream);
+
 /* ---- Marchenko-Pastur PCA denoising (not in the reference; this section and DESIGN.md §5 are the definition) ----
  * Inputs: dwi float32 [N][nvox] planar, x fastest, N >= 2 frames; a uint8 mask; a patch edge P in {3, 5, 7}; an estimator.  Every
  *   dimension of the volume must be >= P (FIB_ERR_INVALID otherwise).
@@ -1282,6 +1353,12 @@ int fib_dki_fit(int device, const float *dwi, int nx, int ny, int nz, int nvol,
 int fib_csd_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
                 const void *mask, int mask_dtype, const float *bval, const float *bvec,
                 const float *verts, int nverts, const int32_t *faces, int nfaces, const fib_csd_params *params, const fib_csd_out *out);
+/* msmt_rec: fibd_msmt_rec on host arrays, sharded and chunked like fib_csd_rec (FIB_DEVICE_ALL: the device set); the same missing-table
+ * errors, the refusals of fib_msmt_design. */
+int fib_msmt_rec(int device, const float *dwi, int nx, int ny, int nz, int nvol,
+                 const void *mask, int mask_dtype, const float *bval, const float *bvec,
+                 const float *verts, int nverts, const int32_t *faces, int nfaces, const fib_msmt_params *params,
+                 const float *wm_R, const float *iso_r, int nshells, const fib_msmt_out *out);
 /* adc_fit(dwi::MRI, mask::MRI) (dti.jl:164) */
 /* host-buffer form of fibd_st_eigen (structens.jl:13-37) */
 int fib_st_eigen(int device, const float *const S[6], int64_t nvox, float *eigvec, float *eigval);

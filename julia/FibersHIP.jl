@@ -170,6 +170,77 @@ function csd_rec(dwi::MRI, mask::MRI, response::NTuple{3,<:Real}, odf_dirs::ODF=
   return CSD(SH, O, peak, f, NI)
 end
 
+# layout: fib_msmt_params sizeof 32: lmax@0 niso@4 b0_thresh@8 b_tol@12 lambda@16 lambda_iso@20 tau@24 niter@28
+struct FibMsmtParams
+  lmax::Cint; niso::Cint; b0_thresh::Cfloat; b_tol::Cfloat; lambda::Cfloat; lambda_iso::Cfloat; tau::Cfloat; niter::Cint
+end
+
+# layout: fib_msmt_out sizeof 88: sh@0 iso@8 odf@24 niter@32 peak@40 f@64
+struct FibMsmtOut
+  sh::Ptr{Float32}; iso::NTuple{2,Ptr{Float32}}; odf::Ptr{Float32}; niter::Ptr{Float32}
+  peak::NTuple{3,Ptr{Float32}}; f::NTuple{3,Ptr{Float32}}
+end
+
+"Container for outputs of a multi-tissue deconvolution: WM harmonic coefficients, isotropic fractions (GM, CSF; not clamped), WM fibre ODF,
+ its three peaks with their amplitudes, solves per voxel"
+struct MSMT
+  sh::MRI; iso::Vector{MRI}; odf::MRI; peak::Vector{MRI}; f::Vector{MRI}; niter::MRI
+end
+
+"msmt_shells(bval) — the shell of every frame (0-based; shell 0 = b <= b0_thresh) and the mean b of every shell"
+function msmt_shells(bval::Vector{Float32}; b0_thresh::Real=50f0, b_tol::Real=0.05f0)
+  nvol = length(bval)
+  bvec = ones(Float32, nvol, 3); shell = zeros(Int32, nvol); bbar = zeros(Float64, 9); ns = Ref{Cint}(0)
+  par = Ref(FibMsmtParams(8, 0, b0_thresh, b_tol, 1f0, 1f0, 0f0, 1))
+  fib_check(ccall((:fib_msmt_design, libfibers), Cint,
+                  (Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Float32}, Cint, Ref{FibMsmtParams}, Ptr{Float32}, Ptr{Float32}, Cint,
+                   Ptr{Int32}, Ref{Cint}, Ptr{Float64}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cint}),
+                  bval, bvec, nvol, C_NULL, 0, par, C_NULL, C_NULL, 0, shell, ns, bbar, C_NULL, C_NULL, C_NULL, C_NULL))
+  return shell, bbar[1:ns[]]
+end
+
+"msmt_wm_response(lambda_para, lambda_perp, s0, bbar; lmax) — R_l of a prolate tensor at every shell: [lmax / 2 + 1, nshells]
+ (one column per shell: the row-major table of the C ABI)"
+function msmt_wm_response(lambda_para::Real, lambda_perp::Real, s0::Real, bbar::Vector{Float64}; lmax::Integer=8)
+  R = zeros(Float32, div(lmax, 2) + 1, length(bbar))
+  fib_check(ccall((:fib_msmt_wm_response, libfibers), Cint, (Cfloat, Cfloat, Cfloat, Ptr{Float64}, Cint, Cint, Ptr{Float32}),
+                  lambda_para, lambda_perp, s0, bbar, length(bbar), lmax, R))
+  return R
+end
+
+"msmt_rec(dwi, mask, wm_R, iso_r, odf_dirs) — multi-shell multi-tissue deconvolution of every frame (not in the reference;
+ include/fibers_hip.h).  wm_R [lmax / 2 + 1, nshells] as msmt_wm_response returns it; iso_r [nshells, niso]: the mean signal of every
+ isotropic tissue (GM, then CSF) per shell, niso = 0, 1 or 2"
+function msmt_rec(dwi::MRI, mask::MRI, wm_R::Matrix{Float32}, iso_r::Matrix{Float32}, odf_dirs::ODF=sphere_724; lmax::Integer=8,
+                  b0_thresh::Real=50f0, b_tol::Real=0.05f0, lambda::Real=1f0, lambda_iso::Real=1f0, tau::Real=0f0, niter::Integer=50,
+                  device::Integer=0)
+  isempty(dwi.bval) && error("Missing b-value table from input DWI structure")
+  isempty(dwi.bvec) && error("Missing gradient table from input DWI structure")
+  nx, ny, nz, nvol = size(dwi.vol)
+  nshells = size(wm_R, 2); niso = size(iso_r, 2)
+  size(wm_R, 1) == div(lmax, 2) + 1 || error("wm_R must be [lmax / 2 + 1, nshells]")
+  (niso <= 2 && (niso == 0 || size(iso_r, 1) == nshells)) || error("iso_r must be [nshells, niso] with niso <= 2")
+  nwm = div((lmax + 1) * (lmax + 2), 2)
+  nreg = div(size(odf_dirs.vertices, 1), 2)
+  SH = MRI(mask, nwm, Float32); O = MRI(mask, nreg, Float32); NI = MRI(mask, 1, Float32)
+  iso = [MRI(mask, 1, Float32) for _ in 1:niso]
+  peak = [MRI(mask, 3, Float32) for _ in 1:3]; f = [MRI(mask, 1, Float32) for _ in 1:3]
+  faces = Int32.(odf_dirs.faces); verts = odf_dirs.vertices; vol = dwi.vol::Array{Float32,4}; m = mask.vol
+  par = Ref(FibMsmtParams(lmax, niso, b0_thresh, b_tol, lambda, lambda_iso, tau, niter))
+  GC.@preserve vol m SH O NI iso peak f faces verts wm_R iso_r begin
+    isop = ntuple(t -> t <= niso ? pointer(iso[t].vol) : Ptr{Float32}(C_NULL), 2)
+    out = Ref(FibMsmtOut(pointer(SH.vol), isop, pointer(O.vol), pointer(NI.vol),
+                         (pointer(peak[1].vol), pointer(peak[2].vol), pointer(peak[3].vol)),
+                         (pointer(f[1].vol), pointer(f[2].vol), pointer(f[3].vol))))
+    fib_check(ccall((:fib_msmt_rec, libfibers), Cint,
+                    (Cint, Ptr{Float32}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32},
+                     Ptr{Float32}, Cint, Ptr{Int32}, Cint, Ref{FibMsmtParams}, Ptr{Float32}, Ptr{Float32}, Cint, Ref{FibMsmtOut}),
+                    device, vol, nx, ny, nz, nvol, m, FIB_DTYPE[eltype(m)] | FIB_MASK_OUTPUTS_ZEROED, dwi.bval, dwi.bvec,
+                    verts, size(verts, 1), faces, size(faces, 1), par, wm_R, iso_r, nshells, out))
+  end
+  return MSMT(SH, iso, O, peak, f, NI)
+end
+
 "find_peaks(odf, odf_dirs) — find_peaks!(W) (gqi.jl:180-201) for a whole ODF volume [nx,ny,nz,nvert]:
  returns (isort_top [nx,ny,nz,3] 1-based first-half vertex rows, 0 where absent; nvalid [nx,ny,nz])"
 function find_peaks(odf::MRI, odf_dirs::ODF=sphere_642; device::Integer=0)
